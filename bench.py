@@ -19,6 +19,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "vae-channel-dynamics_amd", "src"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -277,6 +278,51 @@ class Job:
         self.trainer = self.monitor = self.classifier = self.nudger = self.w = self.x = self.eps = None
 
 
+# --dump-outputs: elements kept per output (float32); larger outputs are written as a fixed, seeded sample of this size.
+# The caps add up to 40 MB; with the small outputs beside them the dump stays inside 64 MB.
+DUMP_CAP = {"reconstruction": 1 << 22, "moments": 1 << 20, "latents": 1 << 20, "params": 1 << 21, "grads": 1 << 21}
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 42
+
+
+def _dump_sample(t: torch.Tensor, cap: int, seed: int):
+    """float32 host copy of `t` in its logical shape when it has at most `cap` elements, else the elements of the flattened
+    tensor at `cap` sorted indices drawn without replacement by a generator seeded with `seed` (the same for every run)"""
+    if t.numel() <= cap:
+        return t.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), size=cap, replace=False))
+    return t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def capture_outputs(job):
+    """what a caller of the timed path holds after its last step, as float32 host arrays in the layouts the wrapper's callers
+    see (NCHW activations, parameters and their .grad in named_parameters order), not the engine's internal ones: the loss
+    scalars [mse, kl, total], the gradient norm, the reconstruction, the encoder moments and the sampled latents of that
+    step, the updated parameters and their gradients, and the tracker statistics when the last step ran the tracker"""
+    res, vae = job.trainer.last, job.w.vae
+    params = [p for _, p, _, _ in vae.arena.entries]
+    out = {"loss": res["scalars"].detach().float().cpu().numpy(),
+           "grad_norm": job.trainer.optimizer.grad_norm().reshape(1).float().cpu().numpy()}
+    for i, key in enumerate(("reconstruction", "moments", "latents")):
+        out[key] = _dump_sample(res[key].permute(0, 3, 1, 2), DUMP_CAP[key], DUMP_SEED + i)
+    out["params"] = _dump_sample(torch.cat([p.detach().reshape(-1) for p in params]), DUMP_CAP["params"], DUMP_SEED + 3)
+    out["grads"] = _dump_sample(torch.cat([p.grad.reshape(-1) for p in params]), DUMP_CAP["grads"], DUMP_SEED + 3)  # params' indices
+    if job.monitor is not None and job.tracking_on:
+        for layer, metrics in job.monitor.get_data_for_step(job.trainer.global_step).items():
+            for metric, v in metrics.items():
+                if isinstance(v, (torch.Tensor, np.ndarray)):
+                    out[f"tracker.{layer}.{metric}"] = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES, {k: a.nbytes for k, a in out.items()}
+    return out
+
+
+def write_outputs(outputs, d):
+    os.makedirs(d, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+    return {"dir": d, "files": sorted(n + ".npy" for n in outputs), "bytes": sum(a.nbytes for a in outputs.values())}
+
+
 def _pmc_file(tag):
     """HBM bytes from the committed rocprofv3 --pmc passes (separate runs of this command; offline), newest round first"""
     for tfile in (f"r04_hbm_traffic_{tag}.json", f"r03_hbm_traffic_{tag}.json"):
@@ -422,7 +468,13 @@ def main():
                          "rank must make the self-launching parent return non-zero)")
     ap.add_argument("--checkpoint-decoder", action="store_true",
                     help="training.gradient_checkpointing: decoder (BASELINE configs[4], 1024x1024): decoder segments keep only their inputs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed on rank 0 (loss, gradient norm, reconstruction, "
+                         "moments, latents, parameters and gradients; seeded samples of the large ones, under 64 MB in all) as "
+                         "DIR/<name>.npy (float32).  Inputs and weights are seeded: the same arguments give the same inputs every run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -475,6 +527,9 @@ def main():
     dt, step_ms = job.timed_region(args.steps)
     sc = job.trainer.last["scalars"].cpu().tolist()
     comm = job.comm_block(args.steps) if job.dist_on else None
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any further step overwrites the engine's buffers
+        dumped = write_outputs(capture_outputs(job), args.dump_outputs)
 
     # ---- profiled region (rank 0 records two HIP events around every kernel launch, on the launch stream): roofline + kernels
     summ, prof_dt, prof_steps = None, None, 0
@@ -534,6 +589,8 @@ def main():
             "roofline": roof, "step_flops": step_flops, "hbm_step": hbm, "tracker_overhead": tracker,
             "bf16_configs2": bf16_leg, "cpu_baseline": cpu, "comm": comm, "kernels": kernels,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if selftest:
             line["rccl_selftest"] = "one-rank process group: the collectives of the N > 1 path ran as identities (see comm)"
         print(json.dumps(line))

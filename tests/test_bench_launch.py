@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -50,3 +52,52 @@ def test_workload_labels_name_the_right_baseline_config():
     assert "nudge every 100" in bench.workload_label("bf16", 512, 8, False, 100, True)
     assert bench.workload_label("bf16", 1024, 2, True, 0, True).startswith("BASELINE configs[4]")
     assert bench.workload_label("f32", 512, 8, False, 0, True).startswith("off-baseline")
+
+
+def test_dump_sample_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: small outputs are written whole in their shape, large ones as the same seeded sample every run"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    a = bench._dump_sample(small, 12, 1)
+    assert a.dtype == np.float32 and a.shape == (3, 4) and (a == small.numpy()).all()
+    big = torch.randn(10000)
+    s1, s2, s3 = bench._dump_sample(big, 100, 7), bench._dump_sample(big, 100, 7), bench._dump_sample(big, 100, 8)
+    assert s1.shape == (100,) and (s1 == s2).all() and not (s1 == s3).all()
+    assert np.isin(s1, big.numpy()).all() and len(np.unique(s1)) == 100
+    info = bench.write_outputs({"loss": np.zeros(3, np.float32), "params": s1}, str(tmp_path / "d"))
+    assert info["files"] == ["loss.npy", "params.npy"] and info["bytes"] == 412
+    assert (np.load(tmp_path / "d" / "params.npy") == s1).all()
+    assert sum(bench.DUMP_CAP.values()) * 4 <= bench.DUMP_MAX_BYTES
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_same_outputs_every_run(cuda, tmp_path):
+    """two runs with the same arguments: the same files, bit for bit, and ms_per_step / steps as asked"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--res", "64", "--batch", "2",
+                            "--no-cpu-baseline", "--no-profile", "--no-extra-legs", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and len(line["step_ms"]) == 3 and line["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == line["dump_outputs"]["files"]
+        assert {"loss.npy", "grad_norm.npy", "reconstruction.npy", "moments.npy", "latents.npy", "params.npy", "grads.npy"} <= set(files)
+        dumps.append({f: np.load(d / f) for f in files})
+    assert dumps[0].keys() == dumps[1].keys()
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert np.array_equal(a, dumps[1][f]), f
+    assert dumps[0]["reconstruction.npy"].shape == (2, 3, 64, 64)
+    assert np.allclose(dumps[0]["loss.npy"][2], dumps[0]["loss.npy"][0] + 1e-6 * dumps[0]["loss.npy"][1], rtol=1e-5)
