@@ -1,0 +1,50 @@
+"""Kernel selection pinned on the host: every pure dispatch query of libvaehip (kernel names, epilogue chunk counts, split
+plans, capability answers) over the case grid of tests/golden/make_dispatch_table.py must give what the committed table
+records.  Fake pointers, no launch: runs without a GPU."""
+import json
+import os
+import re
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import make_dispatch_table as mdt  # noqa: E402
+
+FAMILIES = ["conv3_upwino", "conv3_wino4", "conv3_wino", "conv3_wide_bf16<*,2>", "conv3_wide_bf16<*,3>", "conv3_tile_bf16",
+            "conv3_tile", "conv_thin_bf16", "conv_smallk", "conv_thinn_bf16", "conv_smalln", "conv1_bf16", "igemm_rows_bf16",
+            "igemm_rows", "wgrad3_dma_bf16", "wgrad3_tile_bf16", "wgrad3_tile", "wgrad_thin_bf16", "wgrad_smallk", "wgrad_bf16",
+            "wgrad"]
+
+
+def _family(name):
+    m = re.match(r"(\w+?)_kernel(<.*>)?$", name)
+    assert m, name
+    fam = m.group(1)
+    if fam == "conv3_wide_bf16":
+        fam += "<*," + m.group(2).rstrip(">").split(",")[-1] + ">"
+    return fam
+
+
+def test_dispatch_table_matches_golden():
+    with open(os.path.join(HERE, "golden", "dispatch_table.json")) as f:
+        golden = json.load(f)
+    got = mdt.build_table()
+    assert sorted(got) == sorted(golden), "the case grid changed: regenerate tests/golden/dispatch_table.json on purpose"
+    diff = [k for k in sorted(golden) if got[k] != golden[k]]
+    assert not diff, f"{len(diff)} cases differ, e.g. " + "; ".join(f"{k}: {got[k]} != {golden[k]}" for k in diff[:5])
+    assert json.loads(mdt.dumps(got)) == golden
+
+    # coverage: the grid cannot shrink silently
+    names = [v[0] for k, v in golden.items() if not k.startswith("geom|")]
+    seen = {_family(n) for n in names}
+    missing = [f for f in FAMILIES if f not in seen]
+    assert not missing, missing
+    positions = {v[5] for k, v in golden.items() if k.startswith(("wgrad|", "wphase|", "gemm_tn"))}
+    assert {9, 16} <= positions
+    opts = {o for k in golden for o in k.rsplit("|", 1)[1].split(",") if o}
+    assert opts == set(mdt.OPTIONS)
+    # the stride-2 bf16 weight gradient under no_wgrad_dma
+    assert any(k.startswith("wgrad|c3s2") and k.endswith("|no_wgrad_dma") and "dma" not in v[0] for k, v in golden.items())
+    assert any(k.startswith("wgrad|c3s2") and "dma" in v[0] for k, v in golden.items())
+    assert {1} <= {v[0] for k, v in golden.items() if k.startswith("geom|")}
+    assert len(golden) > 1000

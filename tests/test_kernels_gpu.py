@@ -842,7 +842,7 @@ WINO_CASES = [(2, 32, 32, 128, 128), (1, 64, 64, 256, 128), (2, 16, 32, 512, 512
 
 
 def _wino_kernel(xf, H, W, N, f4):
-    """name of the Winograd instantiation that serves a 3x3 stride-1 launch with N output channels (csrc/igemm.hip: F(4x4,3x3)
+    """name of the Winograd instantiation that serves a 3x3 stride-1 launch with N output channels (csrc/dispatch.cpp: F(4x4,3x3)
     on whole 16 x 32 tiles with whole 64-channel blocks unless the library option "no_wino4" is set, else F(2x2,3x3))"""
     if f4 and H % 16 == 0 and W % 32 == 0 and N % 64 == 0:
         return f"conv3_wino4_kernel<{xf}>", (H // 16) * (W // 32)

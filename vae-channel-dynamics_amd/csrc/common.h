@@ -9,25 +9,6 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define VAE_CHECK(cond, ...)                 \
-  do {                                       \
-    if (!(cond)) {                           \
-      vae_set_error(__VA_ARGS__);            \
-      return VAE_EINVAL;                     \
-    }                                        \
-  } while (0)
-
-#define VAE_LAUNCH_CHECK(name)                                                 \
-  do {                                                                         \
-    hipError_t e_ = hipGetLastError();                                         \
-    if (e_ != hipSuccess) {                                                    \
-      vae_set_error("%s: launch failed: %s", name, hipGetErrorString(e_));     \
-      return VAE_ELAUNCH;                                                      \
-    }                                                                          \
-  } while (0)
-
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-
 __device__ __forceinline__ float silu_f(float u) {
   // u * sigmoid(u); v_exp_f32 + v_rcp_f32 (1 ulp), ~1e-7 relative; __frcp_rn would expand to a full IEEE division
   return u * __builtin_amdgcn_rcpf(1.0f + __expf(-u));
@@ -171,7 +152,6 @@ __device__ __forceinline__ MeanM2 mm2_wave_group(MeanM2 a, int cpg, float n0) {
 // ---------------------------------------------------------------------------------------
 // operand staging helpers shared by the contraction kernels
 // ---------------------------------------------------------------------------------------
-constexpr int SS_HALF = 512;  // floats of GroupNorm scale (and of shift) kept in LDS per workgroup
 
 // Unvectorised guarded load (channel counts that are not a multiple of 4, unaligned rows): element by element.  The
 // vectorised paths use the buffer-descriptor loads below instead.
@@ -191,7 +171,6 @@ __device__ __forceinline__ f32x4 load4s(const float* p, bool ok, int c, int C) {
 // of at the LDS write a pipeline step later.  Build the descriptor from wave-uniform values only.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned BUF_OOB = 0xFFFFFFF0u;
-constexpr size_t BUF_MAX = 0xFFFFFFF0u;  // bytes one descriptor can cover
 #define VAE_BUF_RSRC(ptr, bytes) \
   __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(ptr)), 0, (unsigned)(bytes), 0x00020000)
 #define VAE_BUF_LOAD4(rsrc, off) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rsrc), (off), 0, 0))

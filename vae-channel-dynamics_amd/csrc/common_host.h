@@ -1,9 +1,33 @@
 // Host-side declarations shared by every translation unit of libvaehip (no device code).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <hip/hip_runtime_api.h>
 #include "../../include/vaehip.h"
 
 void vae_set_error(const char* fmt, ...);
+
+#define VAE_CHECK(cond, ...)                 \
+  do {                                       \
+    if (!(cond)) {                           \
+      vae_set_error(__VA_ARGS__);            \
+      return VAE_EINVAL;                     \
+    }                                        \
+  } while (0)
+
+#define VAE_LAUNCH_CHECK(name)                                                 \
+  do {                                                                         \
+    hipError_t e_ = hipGetLastError();                                         \
+    if (e_ != hipSuccess) {                                                    \
+      vae_set_error("%s: launch failed: %s", name, hipGetErrorString(e_));     \
+      return VAE_ELAUNCH;                                                      \
+    }                                                                          \
+  } while (0)
+
+static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+constexpr int SS_HALF = 512;             // floats of GroupNorm scale (and of shift) kept in LDS per workgroup
+constexpr size_t BUF_MAX = 0xFFFFFFF0u;  // bytes one buffer descriptor can cover
 
 // process-wide kernel-selection switches (error.cpp): VAEHIP_FLAT_CONV / VAEHIP_NO_WINO / VAEHIP_NO_WIDE are read once at
 // load time; vae_set_option changes them afterwards (tests compare two algorithms that way)

@@ -604,17 +604,16 @@ __global__ __launch_bounds__(NT) void wgrad3_dma_bf16_kernel(vae_wgrad_args p, i
 
 }  // namespace
 
-bool wgrad3_tile_bf16_dma(const vae_wgrad_args& a);
 // the stride-2 downsampler convolutions (3x3, padding (0,1,0,1)) on the LDS-DMA kernel: 1 x 32-pixel units
 static bool wgrad3_s2_geom(const vae_wgrad_args& a) {
   const vae_conv_geom& g = a.g;
   return g.mode == VAE_MODE_FWD && g.taps == 9 && g.stride == 2 && g.pad_t == 0 && g.pad_l == 0 && g.Hs == 2 * g.Ho && g.Ws == 2 * g.Wo &&
          a.tapmask == 0 && a.y_step <= 1;
 }
-bool wgrad3_tile_bf16_eligible(const vae_wgrad_args& a, bool vec) {
+bool wgrad3_tile_bf16_eligible(const vae_wgrad_args& a, bool vec, bool dma) {
   const vae_conv_geom& g = a.g;
   if (vec && a.batch == 1 && wgrad3_s2_geom(a)) {
-    if (!wgrad3_tile_bf16_dma(a) || a.M <= 32 || a.N % BNT != 0 || g.Wo % TW != 0) return false;
+    if (!dma || a.M <= 32 || a.N % BNT != 0 || g.Wo % TW != 0) return false;
     return (size_t)g.Ho * g.Wo * a.ldy * 4u < BUF_MAX && (size_t)g.Hs * g.Ws * g.Cs * 4u < BUF_MAX;
   }
   if (!vec || a.batch != 1 || g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return false;
@@ -628,14 +627,32 @@ bool wgrad3_tile_bf16_eligible(const vae_wgrad_args& a, bool vec) {
   return true;
 }
 // the LDS-DMA kernel: both operands as 16-byte-aligned bf16 images whose rows are whole 16-byte pieces
-bool wgrad3_tile_bf16_dma(const vae_wgrad_args& a) {
+bool wgrad3_dma_bf16_operands(const vae_wgrad_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.X16 == nullptr || a.dY16 == nullptr || a.xf != VAE_XF_NONE || vae_opt().no_wgrad_dma) return false;
+  if (a.X16 == nullptr || a.dY16 == nullptr || a.xf != VAE_XF_NONE) return false;
   if (a.M % 8 != 0 || a.ldy % 8 != 0 || g.Cs % 8 != 0 || !aligned16(a.X16) || !aligned16(a.dY16)) return false;
   return true;
 }
 int64_t wgrad3_tile_bf16_units(const vae_conv_geom& g) { return (int64_t)g.B * (g.stride == 2 ? g.Ho : g.Ho / TH) * (g.Wo / TW); }
 int wgrad3_tile_bf16_columns(const vae_wgrad_args& a) { return ((a.M + BMT - 1) / BMT) * (a.N / BNT); }
+
+int launch_wgrad3_dma_bf16(const vae_wgrad_args& a, hipStream_t st) {  // both operands as bf16 images: staged by LDS-DMA
+  const vae_conv_geom& g = a.g;
+  const int tx = g.Wo / TW, ty = g.Ho / TH;
+  const int64_t nunits = wgrad3_tile_bf16_units(g);
+  dim3 grid((unsigned)wgrad3_tile_bf16_columns(a), (unsigned)a.nsplit, 1);
+  if (g.stride == 2) {
+    VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<false, 2>), DMA_LDS, "wgrad3_dma_bf16");
+    hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<false, 2>), grid, dim3(NT), DMA_LDS, st, a, tx, g.Ho, nunits);
+  } else if (g.mode == VAE_MODE_UP2X) {
+    VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<true, 1>), DMA_LDS, "wgrad3_dma_bf16");
+    hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<true, 1>), grid, dim3(NT), DMA_LDS, st, a, tx, ty, nunits);
+  } else {
+    VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<false, 1>), DMA_LDS, "wgrad3_dma_bf16");
+    hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<false, 1>), grid, dim3(NT), DMA_LDS, st, a, tx, ty, nunits);
+  }
+  return 0;
+}
 
 int launch_wgrad3_tile_bf16(const vae_wgrad_args& a, hipStream_t st) {
   const vae_conv_geom& g = a.g;
@@ -646,19 +663,6 @@ int launch_wgrad3_tile_bf16(const vae_wgrad_args& a, hipStream_t st) {
   const bool y16 = a.dY16 != nullptr;
 #define WG3(UPV, XFV, X16V) do { if (y16) hipLaunchKernelGGL((wgrad3_tile_bf16_kernel<UPV, XFV, X16V, true>), grid, dim3(NT), 0, st, a, tx, ty, nunits); \
                                 else hipLaunchKernelGGL((wgrad3_tile_bf16_kernel<UPV, XFV, X16V, false>), grid, dim3(NT), 0, st, a, tx, ty, nunits); } while (0)
-  if (wgrad3_tile_bf16_dma(a)) {  // both operands as bf16 images: staged by LDS-DMA
-    if (g.stride == 2) {
-      VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<false, 2>), DMA_LDS, "wgrad3_dma_bf16");
-      hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<false, 2>), grid, dim3(NT), DMA_LDS, st, a, tx, g.Ho, nunits);
-    } else if (up) {
-      VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<true, 1>), DMA_LDS, "wgrad3_dma_bf16");
-      hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<true, 1>), grid, dim3(NT), DMA_LDS, st, a, tx, ty, nunits);
-    } else {
-      VAE_RESERVE_LDS((wgrad3_dma_bf16_kernel<false, 1>), DMA_LDS, "wgrad3_dma_bf16");
-      hipLaunchKernelGGL((wgrad3_dma_bf16_kernel<false, 1>), grid, dim3(NT), DMA_LDS, st, a, tx, ty, nunits);
-    }
-    return 0;
-  }
   if (a.X16 != nullptr) {  // transformed bf16 activation image (xf == NONE checked by the caller)
     if (up) WG3(true, VAE_XF_NONE, true); else WG3(false, VAE_XF_NONE, true);
     return 0;
