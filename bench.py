@@ -5,10 +5,15 @@ N MI355X GPUs of one node.  One process per GPU (torch.distributed / RCCL when N
 Workload at every N (weak scaling) = BASELINE.json configs[1]: SDXL-VAE, 256x256 synthetic RGB,
 batch 16 per GPU, fp32, ActivityMonitor on the 3 shipped layers + classifier, no intervention.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with two extra objects:
-  roofline     -- dominant contraction kernel: executed MFMA TFLOP/s (HIP events over the timed region) vs the dense MFMA
-                  peak (frac <= 1) + the algorithmic (direct-convolution) rate; step_flops gives the same split per step
-  cpu_baseline -- the CPU oracle (plain PyTorch restatement of the reference path) on a bounded sample
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the
+headline (value, ms_per_step, the per-step medians, loss, peak memory, comm when N > 1).  --full adds what takes runs of its
+own, after the headline region:
+  profiled_region / roofline / step_flops / kernels -- the same loop with HIP events around every launch: the dominant
+                  contraction kernel's executed MFMA TFLOP/s vs the dense MFMA peak (frac <= 1) + the algorithmic
+                  (direct-convolution) rate; step_flops gives the same split per step
+  tracker_overhead -- trackers registered vs removed, interleaved A/B
+  bf16_configs2  -- BASELINE configs[2]'s per-GPU shape in bf16 mode
+  cpu_baseline   -- the CPU oracle (plain PyTorch restatement of the reference path) on a bounded sample
 """
 import argparse
 import json
@@ -443,14 +448,17 @@ def main():
     ap.add_argument("--res", type=int, default=RES)
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 = BASELINE configs[1] (the metric); bf16 = configs[2]-style compute (bf16 MFMA, fp32 accumulate, bf16 activation storage)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also run the profiled region (roofline, step_flops, kernels), the tracker-overhead "
+                         "A/B, the bf16 configs[2] leg and the CPU oracle baseline; a plain run prints the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--act-fp32", action="store_true",
                     help="bf16 mode A/B switch: keep activations and their gradients as fp32 tensors with bf16 images beside them (round 2's "
                          "layout) instead of storing them as bf16")
     ap.add_argument("--no-tracking", action="store_true", help="A/B switch for the tracker-overhead measurement")
-    ap.add_argument("--no-profile", action="store_true", help="skip the profiled region (per-kernel HIP-event timing)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profiled region (per-kernel HIP-event timing)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="headline (+ profiled region) only: skip the tracker-overhead A/B and the bf16 configs[2] leg")
+                    help="with --full: headline (+ profiled region) only: skip the tracker-overhead A/B and the bf16 configs[2] leg")
     ap.add_argument("--nudge-interval", type=int, default=0,
                     help="InterventionHandler (gentle nudge x1.10, cap 1.5) every K steps inside the timed loop (BASELINE configs[3]: 100)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl", help="nccl = RCCL over xGMI (the product path)")
@@ -475,6 +483,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run is the headline alone: every leg that costs runs of its own is off
+        args.no_profile = args.no_extra_legs = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -523,7 +533,7 @@ def main():
         job.trainer.exposed_comm_ms()  # discard the warm-up's wait events (first-step RCCL initialisation included)
 
     # ---- the headline region: EXACTLY --steps steps between barrier + synchronize; one event per step (for the median), no
-    # per-kernel events (those run in the profiled region below, whose cost is printed next to this one)
+    # per-kernel events (those run in the profiled region below with --full, whose cost is printed next to this one)
     dt, step_ms = job.timed_region(args.steps)
     sc = job.trainer.last["scalars"].cpu().tolist()
     comm = job.comm_block(args.steps) if job.dist_on else None
@@ -569,7 +579,7 @@ def main():
         line = {
             "metric": f"images/sec SDXL-VAE train step @{R}x{R} (tracking {'off' if args.no_tracking else 'on'})",
             "value": round(world * B * args.steps / dt, 3), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": label, "global_batch": world * B, "resolution": R, "parallelism": f"dp{world}"},

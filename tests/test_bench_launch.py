@@ -101,3 +101,26 @@ def test_bench_dumps_the_same_outputs_every_run(cuda, tmp_path):
         assert np.array_equal(a, dumps[1][f]), f
     assert dumps[0]["reconstruction.npy"].shape == (2, 3, 64, 64)
     assert np.allclose(dumps[0]["loss.npy"][2], dumps[0]["loss.npy"][0] + 1e-6 * dumps[0]["loss.npy"][1], rtol=1e-5)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_full_adds_the_legs(cuda):
+    """a plain run times the steps and prints the headline only; --full adds the profiled region and the tracker A/B (the
+    bf16 configs[2] leg only runs at the metric's shape, the CPU baseline is skipped here for time)"""
+    common = ["--steps", "3", "--warmup", "1", "--res", "64", "--batch", "2"]
+    lines = {}
+    for mode in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + mode, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[bool(mode)] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines[False], lines[True]
+    for line in (plain, full):
+        assert line["steps"] == 3 and line["warmup"] == 1 and len(line["step_ms"]) == 3 and line["ms_per_step"] > 0
+        assert line["unit"] == "images/sec" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert plain["full"] is False and full["full"] is True
+    for key in ("profiled_region", "roofline", "step_flops", "tracker_overhead", "bf16_configs2", "cpu_baseline"):
+        assert plain[key] is None, key
+    assert plain["kernels"] == {}
+    assert full["profiled_region"]["steps"] == 3 and full["roofline"]["kernel"] and full["kernels"]
+    assert full["tracker_overhead"]["steps_per_arm"] > 0
+    assert full["bf16_configs2"] is None and full["cpu_baseline"] is None
