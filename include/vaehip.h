@@ -269,6 +269,16 @@ int vae_gn_track_partial(const void* x, int32_t x_bf16, const float* scale, cons
                          int32_t C, int32_t nchunk, float* ws, void* stream);
 /* out[c] = (sum over rows of ws[r][c]) * inv_count ; fixed order                   */
 int vae_track_final(const float* ws, int32_t rows, int32_t C, float inv_count, float* out, void* stream);
+/* moments of y = XF(x) for the ActivityMonitor's other metrics (monitor.py:56-80), csrc/track.hip.  x: NHWC, pixel stride
+ * ld >= C elements (a channel-prefix view is read in place), fp32 or bf16 (x_bf16); scale / shift: [B][ld] rows, read only when
+ * xf != VAE_XF_NONE.  Every chunk of ceil(HW / nchunk) pixels must be non-empty.
+ * partial: ws [C][B * nchunk][4] = {sum|y|, sum(y - K), sum((y - K)^2), K} per (c, b, chunk), K = y at the chunk's first pixel */
+int vae_moments_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
+                        int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float* ws, void* stream);
+/* final: Chan merges in fp64, fixed order; chan [C][2] doubles (scratch); out [C + 2] = per-channel mean |y|, the mean of
+ * all B*HW*C elements, their unbiased (N - 1) std                                   */
+int vae_moments_final(const float* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* chan, float* out,
+                      void* stream);
 /* GroupNorm(+SiLU) backward.  g = dL/d(XF(gn(x))): fp32, or bf16 when g_bf16 != 0 (bf16 mode stores the dgrad outputs of
  * the halo-tile kernels as bf16, vae_igemm_args.out_bf16).
  * stage 1: ws [B][nchunk][C][2] partial sums of du and du*xhat                     */

@@ -1,0 +1,240 @@
+// Whole-tensor moments for the ActivityMonitor metrics that are not the fused mean |A| (monitor.py:56-80): per-channel mean |y|,
+// the mean and the unbiased std of y = XF(x), for an NHWC activation stored as fp32 or bf16, with an optional GroupNorm(+SiLU)
+// transform applied on the fly (no gn_apply) and any pixel stride ld >= C (a channel-prefix view is read in place).
+//
+// Partial pass: one workgroup per (pixel chunk, image, tile of 256 channel units), lanes across channels as in
+// gn_track_partial_kernel.  Each (b, chunk, c) cell leaves sum|y|, sum(y - K), sum((y - K)^2) and K, where the pivot K is y at
+// the chunk's first pixel: inside a chunk the shifted sums of all lanes share one pivot and simply add, and nothing of the form
+// sum(y^2) - n mean^2 is ever formed in fp32.  Final pass: the cells of each channel are turned into (mean, M2) and merged in fp64
+// with Chan's formula (one workgroup per channel), then the channels are merged the same way (one workgroup).  Every reduction is
+// a fixed-order loop or LDS tree: no atomics, repeated launches are bitwise identical.
+#include "common.h"
+
+namespace {
+
+// W consecutive channels of one pixel, stored as fp32 or bf16 (bf16: the upper half of an fp32, as load4x in norm.hip)
+template <int W, bool XBF>
+__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
+  if constexpr (W == 4 && !XBF) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
+    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+  } else if constexpr (W == 4) {
+    const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + off);
+    v[0] = __builtin_bit_cast(float, r.x << 16);
+    v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
+    v[2] = __builtin_bit_cast(float, r.y << 16);
+    v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
+  } else {
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+      if constexpr (!XBF) v[e] = reinterpret_cast<const float*>(base)[off + e];
+      else v[e] = __builtin_bit_cast(float, (unsigned)reinterpret_cast<const unsigned short*>(base)[off + e] << 16);
+    }
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void apply_xf(float (&v)[W], const float (&sc)[W], const float (&sh)[W], int xf) {
+  if (xf == VAE_XF_NONE) return;
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    const float u = v[e] * sc[e] + sh[e];  // the arithmetic of gn_apply_kernel
+    v[e] = (xf == VAE_XF_AFFINE_SILU) ? silu_f(u) : u;
+  }
+}
+
+// ws: [C][B * nchunk] cells of {sum|y|, sum(y - K), sum((y - K)^2), K}
+template <int W, bool XBF>
+__global__ __launch_bounds__(256) void moments_partial_kernel(const void* __restrict__ x, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, int xf, int HW, int C, int ld,
+                                                              int nchunk, float* __restrict__ ws) {
+  __shared__ float red[3][W][256];
+  const int nu = C / W;                          // channel units of W channels
+  const int u0 = blockIdx.z * 256;
+  const int nut = min(256, nu - u0);             // units of this workgroup
+  const int PR = 256 / nut;                      // pixel rows of the workgroup
+  const int ul = threadIdx.x % nut, pr = threadIdx.x / nut;
+  const int c0 = (u0 + ul) * W;
+  const int chunk = blockIdx.x, b = blockIdx.y;
+  const int per = (HW + nchunk - 1) / nchunk;
+  const int p0 = chunk * per, p1 = min(HW, p0 + per);  // p0 < HW: the host makes every chunk non-empty
+  float sc[W], sh[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    sc[e] = xf != VAE_XF_NONE ? scale[(int64_t)b * ld + c0 + e] : 1.f;
+    sh[e] = xf != VAE_XF_NONE ? shift[(int64_t)b * ld + c0 + e] : 0.f;
+  }
+  const int64_t xb = (int64_t)b * HW * ld + c0;
+  float K[W];
+  load_units<W, XBF>(x, xb + (int64_t)p0 * ld, K);
+  apply_xf<W>(K, sc, sh, xf);
+  float sa[W], s1[W], s2[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e) sa[e] = s1[e] = s2[e] = 0.f;
+  if (pr < PR) {
+    int pix = p0 + pr;
+    // four loads in flight per lane, then the same per-element order as the single-pixel tail
+    for (; pix + 3 * PR < p1; pix += 4 * PR) {
+      float v[4][W];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) load_units<W, XBF>(x, xb + (int64_t)(pix + k * PR) * ld, v[k]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        apply_xf<W>(v[k], sc, sh, xf);
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+          const float d = v[k][e] - K[e];
+          sa[e] += fabsf(v[k][e]);
+          s1[e] += d;
+          s2[e] += d * d;
+        }
+      }
+    }
+    for (; pix < p1; pix += PR) {
+      float v[W];
+      load_units<W, XBF>(x, xb + (int64_t)pix * ld, v);
+      apply_xf<W>(v, sc, sh, xf);
+#pragma unroll
+      for (int e = 0; e < W; ++e) {
+        const float d = v[e] - K[e];
+        sa[e] += fabsf(v[e]);
+        s1[e] += d;
+        s2[e] += d * d;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    red[0][e][threadIdx.x] = sa[e];
+    red[1][e][threadIdx.x] = s1[e];
+    red[2][e][threadIdx.x] = s2[e];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nut) {
+    const int64_t rows = (int64_t)gridDim.y * nchunk;
+    const int64_t row = (int64_t)b * nchunk + chunk;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+      f32x4 t = {0.f, 0.f, 0.f, K[e]};
+      for (int r = 0; r < PR; ++r) {
+        const int i = r * nut + threadIdx.x;
+        t[0] += red[0][e][i];
+        t[1] += red[1][e][i];
+        t[2] += red[2][e][i];
+      }
+      *reinterpret_cast<f32x4*>(ws + ((int64_t)(c0 + e) * rows + row) * 4) = t;
+    }
+  }
+}
+
+struct Mom { double n, m, M2; };
+__device__ __forceinline__ Mom mom_merge(Mom a, Mom b) {
+  if (b.n == 0.0) return a;
+  if (a.n == 0.0) return b;
+  const double n = a.n + b.n, d = b.m - a.m;
+  return Mom{n, a.m + d * (b.n / n), a.M2 + b.M2 + d * d * (a.n * b.n / n)};
+}
+
+// fixed LDS tree over 256 lanes; lane 0 ends with the merge of all
+__device__ __forceinline__ Mom mom_block(Mom a, double (*red)[256]) {
+  red[0][threadIdx.x] = a.n;
+  red[1][threadIdx.x] = a.m;
+  red[2][threadIdx.x] = a.M2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const Mom r = mom_merge(Mom{red[0][threadIdx.x], red[1][threadIdx.x], red[2][threadIdx.x]},
+                              Mom{red[0][threadIdx.x + o], red[1][threadIdx.x + o], red[2][threadIdx.x + o]});
+      red[0][threadIdx.x] = r.n;
+      red[1][threadIdx.x] = r.m;
+      red[2][threadIdx.x] = r.M2;
+    }
+    __syncthreads();
+  }
+  return Mom{red[0][0], red[1][0], red[2][0]};
+}
+
+// one workgroup per channel: out[c] = mean |y|; chan[c] = (mean, M2) of the channel
+__global__ __launch_bounds__(256) void moments_channel_kernel(const float* __restrict__ ws, int B, int HW, int nchunk,
+                                                              double* __restrict__ chan, float* __restrict__ out) {
+  __shared__ double red[3][256];
+  const int c = blockIdx.x;
+  const int rows = B * nchunk;
+  const int per = (HW + nchunk - 1) / nchunk;
+  Mom a{0.0, 0.0, 0.0};
+  double sa = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(ws + ((int64_t)c * rows + r) * 4);
+    const int p0 = (r % nchunk) * per;
+    const double n = (double)(min(HW, p0 + per) - p0);
+    const double s1 = t[1], dm = s1 / n;
+    sa += (double)t[0];
+    a = mom_merge(a, Mom{n, (double)t[3] + dm, fmax((double)t[2] - s1 * dm, 0.0)});
+  }
+  const Mom m = mom_block(a, red);
+  // sum |y|: a second tree over the same LDS (the moments of lane 0 are in registers now)
+  __syncthreads();
+  red[0][threadIdx.x] = sa;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[0][threadIdx.x] += red[0][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[c] = (float)(red[0][0] / ((double)B * (double)HW));
+    chan[2 * c] = m.m;
+    chan[2 * c + 1] = m.M2;
+  }
+}
+
+// one workgroup: out[C] = mean, out[C + 1] = unbiased std over all B * HW * C elements (NaN when there is one element, as torch)
+__global__ __launch_bounds__(256) void moments_total_kernel(const double* __restrict__ chan, int C, double n_each,
+                                                            float* __restrict__ out) {
+  __shared__ double red[3][256];
+  Mom a{0.0, 0.0, 0.0};
+  for (int c = threadIdx.x; c < C; c += 256) a = mom_merge(a, Mom{n_each, chan[2 * c], chan[2 * c + 1]});
+  const Mom m = mom_block(a, red);
+  if (threadIdx.x == 0) {
+    out[C] = (float)m.m;
+    out[C + 1] = (float)sqrt(m.M2 / (m.n - 1.0));
+  }
+}
+
+}  // namespace
+
+extern "C" int vae_moments_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
+                                   int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float* ws, void* stream) {
+  VAE_CHECK(x && ws && B > 0 && HW > 0 && C > 0 && ld >= C && nchunk > 0, "moments_partial: bad args");
+  VAE_CHECK(xf == VAE_XF_NONE || xf == VAE_XF_AFFINE || xf == VAE_XF_AFFINE_SILU, "moments_partial: xf=%d", xf);
+  VAE_CHECK(xf == VAE_XF_NONE || (scale && shift), "moments_partial: xf needs scale and shift");
+  const int per = (HW + nchunk - 1) / nchunk;
+  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
+            "moments_partial: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", nchunk, HW);
+  VAE_CHECK(aligned16(ws), "moments_partial: unaligned workspace");
+  // four channels per lane where the rows allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
+  const uintptr_t amask = x_bf16 ? 7u : 15u;
+  const bool vec = C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & amask) == 0;
+  const int W = vec ? 4 : 1;
+  const int tiles = (C / W + 255) / 256;
+  const dim3 grid(nchunk, B, tiles);
+  hipStream_t s = (hipStream_t)stream;
+#define MPK(WW, BF) hipLaunchKernelGGL((moments_partial_kernel<WW, BF>), grid, dim3(256), 0, s, x, scale, shift, xf, HW, C, ld, nchunk, ws)
+  if (vec) { if (x_bf16) MPK(4, true); else MPK(4, false); }
+  else { if (x_bf16) MPK(1, true); else MPK(1, false); }
+#undef MPK
+  VAE_LAUNCH_CHECK("moments_partial");
+  return VAE_OK;
+}
+
+extern "C" int vae_moments_final(const float* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* chan, float* out,
+                                 void* stream) {
+  VAE_CHECK(ws && chan && out && B > 0 && HW > 0 && C > 0 && nchunk > 0 && (int64_t)B * nchunk <= 0x7fffffff,
+            "moments_final: bad args");
+  VAE_CHECK(aligned16(ws), "moments_final: unaligned workspace");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(moments_channel_kernel, dim3(C), dim3(256), 0, s, ws, B, HW, nchunk, chan, out);
+  VAE_LAUNCH_CHECK("moments_final");
+  hipLaunchKernelGGL(moments_total_kernel, dim3(1), dim3(256), 0, s, chan, C, (double)B * (double)HW, out);
+  VAE_LAUNCH_CHECK("moments_final");
+  return VAE_OK;
+}

@@ -16,6 +16,13 @@ the buffered forwards (monitor.py:181-182); `full_activation_map` keeps only the
 (monitor.py:166-167).
 Deliberate fix: under data parallelism the buffered vectors are averaged across ranks in step()
 (the reference classifies rank-0-local statistics, train.py:311).
+
+`tracking.device_metrics: true` (opt-in) serves every other engine target with a 4-D capture point and any subset of the
+four metrics from the device as well (`device_layers`): one moments vector per forward (ops.moments: per-channel mean
+|A|, mean, unbiased std) on the tensor the hook would have received, and a `full_activation_map` snapshot on the first
+forward after the last step() only (step() keeps only that one).  step() makes one transfer per layer and aggregates
+exactly as the hook path does; the scalars stay rank-local like the hook path's, the mean |A| vectors are averaged
+across ranks like the fused ones.
 """
 import logging
 from collections import defaultdict
@@ -70,6 +77,14 @@ def compute_metrics(tensor: torch.Tensor, metrics: List[str]) -> Dict[str, Any]:
     return out
 
 
+class _Moments:
+    """a buffered per-forward moments vector of a device-served layer (resolved to host values in step())"""
+    __slots__ = ("t",)
+
+    def __init__(self, t: torch.Tensor):
+        self.t = t
+
+
 class ActivityMonitor:
     def __init__(self, model: torch.nn.Module, tracking_config: Dict[str, Any]):
         self.model = model
@@ -79,11 +94,14 @@ class ActivityMonitor:
         self.processed_data_by_step = defaultdict(dict)
         self.hooks: list = []
         self.fused_layers: List[str] = []
+        self.device_layers: List[str] = []
+        self.device_metrics = bool(self.config.get("device_metrics", False))
         self.sync_across_ranks = bool(self.config.get("sync_across_ranks", True))
         if self.config.get("enabled", False):
             self._register_hooks()
             logger.info(f"ActivityMonitor initialized for {len(self.target_layers_config)} target(s) "
-                        f"({len(self.fused_layers)} fused on device).")
+                        f"({len(self.fused_layers)} fused on device"
+                        + (f", {len(self.device_layers)} device-served" if self.device_metrics else "") + ").")
         else:
             logger.info("ActivityMonitor is disabled in config.")
 
@@ -92,6 +110,25 @@ class ActivityMonitor:
         def sink(vec: torch.Tensor):
             self.hook_collected_buffer[layer_id][FUSED_METRIC].append(vec)
         return sink
+
+    def _device_sink(self, layer_id: str, metrics: List[str]) -> Callable:
+        """engine sink of a device-served layer: buffers device tensors only, one entry per metric in config order (the
+        order compute_metrics appends in); the moments vector is shared by the metrics it serves"""
+        def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor]):
+            buf = self.hook_collected_buffer[layer_id]
+            for name in metrics:
+                if name == "full_activation_map":
+                    if fmap is not None:
+                        buf[name].append(fmap)
+                else:
+                    buf[name].append(_Moments(mom))
+        return sink
+
+    def _map_due(self, layer_id: str) -> Callable[[], bool]:
+        """a snapshot is taken while the buffer holds none: the first forward after the last step() (step() keeps values[0])"""
+        def due():
+            return not self.hook_collected_buffer.get(layer_id, {}).get("full_activation_map")
+        return due
 
     def _hook(self, layer_id: str, metrics: List[str], point: str) -> Callable:
         def fn(module, hook_input, hook_output=None):
@@ -126,6 +163,13 @@ class ActivityMonitor:
                     self.hooks.append(engine.add_tracker(layer, point, self._sink(layer_id)))
                     self.fused_layers.append(layer_id)
                     logger.info(f"Registered FUSED device tracker for layer: {name} ({point})")
+                elif self.device_metrics and engine is not None and metrics and \
+                        all(m in KNOWN_METRICS for m in metrics) and engine.metric_trackable(layer):
+                    mlist = list(dict.fromkeys(metrics))
+                    self.hooks.append(engine.add_tracker(layer, point, self._device_sink(layer_id, mlist), metrics=mlist,
+                                                         map_due=self._map_due(layer_id)))
+                    self.device_layers.append(layer_id)
+                    logger.info(f"Registered DEVICE metric tracker for layer: {name} ({point}): {mlist}")
                 elif point == "input":
                     self.hooks.append(layer.register_forward_pre_hook(self._hook(layer_id, metrics, point)))
                     logger.info(f"Registered FORWARD PRE-HOOK for layer: {name} (input)")
@@ -142,26 +186,61 @@ class ActivityMonitor:
             h.remove()
         self.hooks = []
         self.fused_layers = []
+        self.device_layers = []
 
     # ------------------------------------------------------------------ aggregation
+    def _rank_average(self, stacked: torch.Tensor) -> torch.Tensor:
+        """[forwards, C] device vectors -> their average over the ranks (the identity without data parallelism)"""
+        if self.sync_across_ranks and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            # ranks must have buffered the same number of forwards (train.py makes them skip batches together)
+            n = torch.tensor([stacked.shape[0], -stacked.shape[0]], device=stacked.device, dtype=torch.int64)
+            torch.distributed.all_reduce(n, op=torch.distributed.ReduceOp.MAX)
+            if int(n[0]) != -int(n[1]):
+                raise RuntimeError(f"ActivityMonitor: ranks buffered different numbers of forwards "
+                                   f"({stacked.shape[0]} here, {int(n[0])} max, {-int(n[1])} min); the per-rank "
+                                   f"tracker vectors cannot be averaged")
+            torch.distributed.all_reduce(stacked)
+            stacked = stacked / torch.distributed.get_world_size()
+        return stacked
+
     def _to_host(self, values: list) -> list:
         """device vectors of the fused path -> list of np.float32 arrays with ONE transfer."""
         if values and all(isinstance(v, torch.Tensor) and v.is_cuda for v in values):
-            stacked = torch.stack(values)
-            if self.sync_across_ranks and torch.distributed.is_available() and torch.distributed.is_initialized() \
-                    and torch.distributed.get_world_size() > 1:
-                # ranks must have buffered the same number of forwards (train.py makes them skip batches together)
-                n = torch.tensor([stacked.shape[0], -stacked.shape[0]], device=stacked.device, dtype=torch.int64)
-                torch.distributed.all_reduce(n, op=torch.distributed.ReduceOp.MAX)
-                if int(n[0]) != -int(n[1]):
-                    raise RuntimeError(f"ActivityMonitor: ranks buffered different numbers of forwards "
-                                       f"({stacked.shape[0]} here, {int(n[0])} max, {-int(n[1])} min); the per-rank "
-                                       f"tracker vectors cannot be averaged")
-                torch.distributed.all_reduce(stacked)
-                stacked = stacked / torch.distributed.get_world_size()
-            host = stacked.cpu().numpy()
+            host = self._rank_average(torch.stack(values)).cpu().numpy()
             return [host[i] for i in range(host.shape[0])]
         return values
+
+    def _device_to_host(self, metric_data: Dict[str, list]):
+        """a device-served layer's buffer -> the host values the hook path would have buffered, in place: ONE transfer of
+        the stacked moments vectors (mean |A| part averaged across ranks like the fused vectors, mean / std rank-local
+        like the hook path's), one of the full-map snapshot (NCHW view with the channels_last strides of the hook's clone)"""
+        moms: Dict[int, int] = {}  # id of a buffered moments vector -> its row
+        stack = []
+        for values in metric_data.values():
+            for v in values:
+                if isinstance(v, _Moments) and id(v.t) not in moms:
+                    moms[id(v.t)] = len(stack)
+                    stack.append(v.t)
+        host = None
+        if stack:
+            stacked = torch.stack(stack)
+            if FUSED_METRIC in metric_data:
+                part = stacked[:, :-2].contiguous()
+                avg = self._rank_average(part)
+                if avg is not part:
+                    stacked = torch.cat([avg, stacked[:, -2:]], dim=1)
+            host = stacked.cpu().numpy()
+        for metric, values in metric_data.items():
+            for i, v in enumerate(values):
+                if isinstance(v, _Moments):
+                    row = host[moms[id(v.t)]]
+                    if metric == FUSED_METRIC:
+                        values[i] = row[:-2]
+                    else:
+                        values[i] = np.asarray(row[-2] if metric == "mean_activation" else row[-1], dtype=np.float32)
+                elif isinstance(v, torch.Tensor) and v.is_cuda:
+                    values[i] = v.cpu().permute(0, 3, 1, 2)
 
     def step(self, global_step: int) -> Dict[str, Any]:
         if not self.config.get("enabled", False):
@@ -170,6 +249,10 @@ class ActivityMonitor:
             return {}
         log: Dict[str, Any] = {}
         processed: Dict[str, Dict[str, Any]] = {}
+        for metric_data in self.hook_collected_buffer.values():
+            if any(isinstance(v, _Moments) or (m == "full_activation_map" and isinstance(v, torch.Tensor) and v.is_cuda)
+                   for m, values in metric_data.items() for v in values):
+                self._device_to_host(metric_data)
         for layer_id, metric_data in self.hook_collected_buffer.items():
             processed[layer_id] = {}
             for metric, values in metric_data.items():

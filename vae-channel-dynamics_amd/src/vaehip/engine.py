@@ -7,7 +7,9 @@ never touch HBM.  The torch.nn hook protocol the reference's plugins rely on
 (monitor.py:126-133, sdxl_vae_wrapper.py:104-107) is honoured: a module that carries foreign
 forward hooks gets its input/output materialised and the hooks are called synchronously;
 the shipped metric `mean_abs_activation_per_channel` (monitor.py:66) is served by fused
-device-side reductions instead (add_tracker), without any tensor or host sync.
+device-side reductions instead (add_tracker), without any tensor or host sync.  add_tracker(metrics=...) serves any
+subset of the four ActivityMonitor metrics at a 4-D capture point the same way: one moments pass (ops.moments) per
+forward on the tensor a hook would have received, and a full-map snapshot only when the caller says one is due.
 """
 from __future__ import annotations
 
@@ -22,6 +24,8 @@ from . import ops
 from .ops import XF_AFFINE, XF_AFFINE_SILU, XF_NONE, Stats
 
 _TRACK_C = {4, 8, 16, 32, 64, 128, 256, 512, 1024}
+MOMENT_METRICS = ("mean_abs_activation_per_channel", "mean_activation", "std_activation")  # one ops.moments vector
+DEVICE_METRICS = MOMENT_METRICS + ("full_activation_map",)
 
 
 class _TrackHandle:
@@ -34,10 +38,20 @@ class _TrackHandle:
             lst.remove(self._f)
 
 
+class _MetricTracker:
+    """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward"""
+
+    def __init__(self, metrics, sink, map_due):
+        self.moments = any(m in MOMENT_METRICS for m in metrics)
+        self.full_map = "full_activation_map" in metrics
+        self.sink, self.map_due = sink, map_due
+
+
 class Engine:
     def __init__(self, vae: nn.Module):
         self._vae = weakref.ref(vae)
         self._trackers: Dict[int, Dict[str, List[Callable]]] = {}
+        self._mtrackers: Dict[int, Dict[str, List[_MetricTracker]]] = {}
         self._gtarget: Optional[torch.Tensor] = None
         self.reducer = None  # optional DP bucket reducer with .ready(low_offset)
         self._low: Dict[int, int] = {}
@@ -111,17 +125,62 @@ class Engine:
             self.reducer.ready(self._low[k])
 
     # ------------------------------------------------------------------ trackers and hooks
-    def add_tracker(self, module: nn.Module, point: str, sink: Callable[[torch.Tensor], None]):
-        """fused `mean_abs_activation_per_channel` for `module`'s input or output: sink(tensor[C]) per forward."""
+    def add_tracker(self, module: nn.Module, point: str, sink: Callable, metrics: Optional[List[str]] = None,
+                    map_due: Optional[Callable[[], bool]] = None):
+        """metrics None: fused `mean_abs_activation_per_channel` for `module`'s input or output: sink(tensor[C]) per forward.
+        metrics: any subset of DEVICE_METRICS on a module that metric_trackable() accepts: sink(moments, fmap) per forward,
+        with moments = ops.moments(tensor) (None when only the full map is asked for) and fmap an fp32 NHWC copy of the
+        tensor when `full_activation_map` is asked for and map_due() (default: always) says a snapshot is wanted, else None."""
         assert point in ("input", "output")
-        self._trackers.setdefault(id(module), {}).setdefault(point, []).append(sink)
-        return _TrackHandle(self._trackers, id(module), point, sink)
+        if metrics is None:
+            self._trackers.setdefault(id(module), {}).setdefault(point, []).append(sink)
+            return _TrackHandle(self._trackers, id(module), point, sink)
+        bad = [m for m in metrics if m not in DEVICE_METRICS]
+        if bad or not metrics:
+            raise ValueError(f"device trackers serve {DEVICE_METRICS}, not {list(metrics)}")
+        if not self.metric_trackable(module):
+            raise ValueError(f"{type(module).__name__}: no 4-D capture point the engine can reduce")
+        t = _MetricTracker(metrics, sink, map_due)
+        self._mtrackers.setdefault(id(module), {}).setdefault(point, []).append(t)
+        return _TrackHandle(self._mtrackers, id(module), point, t)
+
+    @staticmethod
+    def metric_trackable(module: nn.Module) -> bool:
+        """modules whose input and output the engine holds as NHWC activations (not Linear: a [B, T, C] tensor's channel
+        axes differ; not the SiLU / dropout fused into a convolution; not the root, whose call is torch's own)"""
+        from . import autoencoder as A
+        return isinstance(module, (A.HipConv2d, A.HipGroupNorm, A.ResnetBlock2D, A.Attention, A.UNetMidBlock2D,
+                                   A.DownEncoderBlock2D, A.UpDecoderBlock2D, A.Downsample2D, A.Upsample2D, A.Encoder,
+                                   A.Decoder))
 
     def _tracked(self, m, point):
         if self._replay:
             return None
         d = self._trackers.get(id(m))
         return d.get(point) if d else None
+
+    def _mtracked(self, m, point):
+        if self._replay:
+            return None
+        d = self._mtrackers.get(id(m))
+        return d.get(point) if d else None
+
+    @staticmethod
+    def _emit(ts: List[_MetricTracker], x: torch.Tensor, st: Optional[Stats] = None, xf: int = XF_NONE,
+              make_map: Optional[Callable[[], torch.Tensor]] = None):
+        """serve device trackers from y = XF(x): one moments pass shared by all of them; a full map only for those whose
+        snapshot is due (make_map: the materialised y when xf is not XF_NONE, else a copy of x)"""
+        mom = ops.moments(x, st, xf) if any(t.moments for t in ts) else None
+        fmap = None
+        for t in ts:
+            f = None
+            if t.full_map and (t.map_due is None or t.map_due()):
+                if fmap is None:
+                    fmap = make_map() if make_map is not None else ops.map_snapshot(x)
+                    if not fmap.is_contiguous():
+                        fmap = ops.map_snapshot(fmap)
+                f = fmap
+            t.sink(mom if t.moments else None, f)
 
     def _mean_abs(self, t: torch.Tensor) -> torch.Tensor:
         B, Cc = t.shape[0], t.shape[-1]
@@ -145,7 +204,8 @@ class Engine:
             return t.reshape(t.shape[0], -1, t.shape[-1])
         return t.permute(0, 3, 1, 2)
 
-    def _pre(self, m, make_in):
+    def _pre(self, m, make_in, src=None):
+        """src: (x, xf, st) with make_in() == XF(x): device trackers read x and the GroupNorm statistics instead"""
         sinks = self._tracked(m, "input")
         if (m._forward_pre_hooks and not self._replay) or sinks:
             t = make_in()
@@ -155,6 +215,12 @@ class Engine:
                     s(v)
             for h in list(m._forward_pre_hooks.values()):
                 h(m, (self._present(m, t),))
+        mts = self._mtracked(m, "input")
+        if mts:
+            if src is None or src[1] == XF_NONE:
+                self._emit(mts, make_in() if src is None else src[0])
+            else:
+                self._emit(mts, src[0], src[2], src[1], make_map=make_in)
 
     def _post(self, m, make_in, out: torch.Tensor, tracked_already=False):
         sinks = None if tracked_already else self._tracked(m, "output")
@@ -162,6 +228,9 @@ class Engine:
             v = self._mean_abs(out)
             for s in sinks:
                 s(v)
+        mts = None if tracked_already else self._mtracked(m, "output")
+        if mts:
+            self._emit(mts, out)
         if m._forward_hooks and not self._replay:
             tin = self._present(m, make_in())
             for h in list(m._forward_hooks.values()):
@@ -182,6 +251,9 @@ class Engine:
             v = ops.gn_track(x, st)
             for s in sinks:
                 s(v)
+        mts = self._mtracked(norm, "output")
+        if mts:
+            self._emit(mts, x, st, XF_AFFINE, make_map=lambda: ops.gn_apply(x, st, XF_AFFINE))
         if norm._forward_hooks and not self._replay:
             self._post(norm, lambda: x, ops.gn_apply(x, st, XF_AFFINE), tracked_already=True)
         return st
@@ -199,9 +271,11 @@ class Engine:
                 cache["t"] = t if t.shape[-1] == ci else t[..., :ci]
             return cache["t"]
 
-        self._pre(m, make_in)
+        ci = m.weight.shape[1]
+        self._pre(m, make_in, src=(x if x.shape[-1] == ci else x[..., :ci], xf, st))
         sinks = self._tracked(m, "output")
-        fuse_res = res is not None and not m._forward_hooks and not sinks
+        mts = self._mtracked(m, "output")
+        fuse_res = res is not None and not m._forward_hooks and not sinks and not mts
         tb = None
         if sinks:
             ho, wo = ops.out_hw(kind, x.shape[1], x.shape[2])
@@ -224,6 +298,8 @@ class Engine:
             v = ops.track_final(tb, y.shape[0] * y.shape[1] * y.shape[2])
             for s in sinks:
                 s(v)
+        if mts:
+            self._emit(mts, y)
         if m._forward_hooks:
             self._post(m, make_in, y, tracked_already=True)
         if res is not None and not fuse_res:

@@ -85,6 +85,8 @@ SIGNATURES = {
     "vae_bf16_act_image_ok": [C.POINTER(ConvGeom), i32, i32],
     "vae_gn_track_partial": [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp],
     "vae_track_final": [vp, i32, i32, f32, vp, vp],
+    "vae_moments_partial": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],
+    "vae_moments_final": [vp, i32, i32, i32, i32, vp, vp, vp],
     "vae_gn_bwd_partial": [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "vae_gn_bwd_final": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "vae_gn_bwd_apply": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],

@@ -905,6 +905,46 @@ def gn_track(x: torch.Tensor, st: Stats) -> torch.Tensor:
     return out
 
 
+def moments(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE) -> torch.Tensor:
+    """the other ActivityMonitor metrics of y = XF(x) in one read of x, no tensor materialised: a device vector of C + 2 fp32
+    values, [per-channel mean |y| (as gn_track), mean of y, unbiased std of y (torch.Tensor.std)].  x: NHWC, fp32 or bf16
+    storage, channels contiguous; a channel-prefix view of a wider buffer (x4[..., :3]) is read in place.  stats: the
+    GroupNorm whose per-(b, c) scale / shift XF applies (rows as wide as the buffer's pixel stride)."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"moments: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"moments: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    if (stats is None) != (xf == XF_NONE):
+        raise ValueError("moments: a GroupNorm transform (xf) needs its stats and stats need an xf")
+    if stats is not None:
+        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
+            raise ValueError(f"moments: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
+    HW = H * W
+    units = Cc // 4 if Cc % 4 == 0 else Cc
+    pr = max(1, 256 // min(256, units))
+    tiles = (units + 255) // 256
+    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
+    per = (HW + nch - 1) // nch
+    nch = (HW + per - 1) // per  # every chunk non-empty
+    dev = x.device
+    ws = torch.empty((Cc, B * nch, 4), device=dev, dtype=torch.float32)
+    chan = torch.empty((Cc, 2), device=dev, dtype=torch.float64)
+    out = torch.empty((Cc + 2,), device=dev, dtype=torch.float32)
+    lib.call("vae_moments_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
+             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_moments_final", _p(ws), B, HW, Cc, nch, _p(chan), _p(out), _stream())
+    return out
+
+
+def map_snapshot(t: torch.Tensor) -> torch.Tensor:
+    """fp32 NHWC device copy of an activation (full_activation_map): bf16 storage widened by vae_unpack_bf16"""
+    if t.dtype == torch.bfloat16:
+        return to_f32(t)
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def conv_track_buffer(M: int, Co: int, device) -> torch.Tensor:
     return torch.empty(((M + 127) // 128, Co), device=device, dtype=torch.float32)
 
