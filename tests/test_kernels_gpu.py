@@ -108,8 +108,11 @@ def test_conv_fwd_dgrad_wgrad(cuda, kind, B, H, W, Ci, Co):
     assert _rel(gb.cpu(), br.grad) < 3e-5
 
 
-@pytest.mark.parametrize("C,H,W,silu", [(128, 16, 16, True), (256, 8, 8, True), (512, 4, 4, True), (512, 6, 10, False),
-                                         (128, 8, 32, True), (512, 4, 32, True), (256, 4, 64, False)])  # last 3: halo-tile kernel
+GN_FUSED_CASES = [(128, 16, 16, True), (256, 8, 8, True), (512, 4, 4, True), (512, 6, 10, False),
+                  (128, 8, 32, True), (512, 4, 32, True), (256, 4, 64, False)]  # last 3: halo-tile kernel
+
+
+@pytest.mark.parametrize("C,H,W,silu", GN_FUSED_CASES)
 def test_gn_fused_conv_and_backward(cuda, C, H, W, silu):
     """GroupNorm(+SiLU) fused into the conv operand load; GN backward; tracker reduction."""
     from vaehip import ops
@@ -174,7 +177,10 @@ def test_conv_track_epilogue(cuda):
     assert float(((tr.cpu() - ref).abs() / ref).max()) < 1e-5
 
 
-@pytest.mark.parametrize("z,M,N,K", [(2, 64, 64, 512), (3, 100, 36, 40), (1, 256, 512, 256)])
+GEMM_CASES = [(2, 64, 64, 512), (3, 100, 36, 40), (1, 256, 512, 256)]
+
+
+@pytest.mark.parametrize("z,M,N,K", GEMM_CASES)
 def test_batched_gemms(cuda, z, M, N, K):
     from vaehip import ops
     gen = torch.Generator().manual_seed(z * 100 + M)
@@ -333,10 +339,13 @@ def packed_weights():
 
 
 # (5,128,128,128,128): 640 tiles on 512 persistent workgroups -- some run two tiles through the cross-tile pipeline
+BF16_CONV_CASES = [("c3", 2, 8, 32, 128, 128), ("c3", 1, 4, 64, 256, 512), ("c3", 2, 12, 32, 512, 256),
+                   ("c3", 1, 4, 32, 96, 160), ("c3up", 2, 4, 16, 128, 256),
+                   ("c3", 2, 64, 64, 128, 128), ("c3", 5, 128, 128, 128, 128), ("c3", 3, 36, 96, 256, 128)]
+
+
 @pytest.mark.parametrize("packed", [False, True])
-@pytest.mark.parametrize("kind,B,H,W,Ci,Co", [("c3", 2, 8, 32, 128, 128), ("c3", 1, 4, 64, 256, 512), ("c3", 2, 12, 32, 512, 256),
-                                              ("c3", 1, 4, 32, 96, 160), ("c3up", 2, 4, 16, 128, 256),
-                                              ("c3", 2, 64, 64, 128, 128), ("c3", 5, 128, 128, 128, 128), ("c3", 3, 36, 96, 256, 128)])
+@pytest.mark.parametrize("kind,B,H,W,Ci,Co", BF16_CONV_CASES)
 def test_bf16_conv_fwd_dgrad(cuda, bf16_mode, packed_weights, packed, kind, B, H, W, Ci, Co):
     from vaehip import ops
     gen = torch.Generator().manual_seed(99 + Ci + Co)
@@ -547,12 +556,15 @@ def test_groupnorm_statistics_from_conv_epilogue(cuda, packed_weights, mode, kin
         ops.PRECISION = ops.PREC_F32
 
 
+UPCONV_PHASE_CASE = (2, 4, 32, 128, 128)
+
+
 def test_upconv_phase_decomposition(cuda):
     """conv3x3(nearest_upsample_2x(x)) == four phase convolutions on x with the effective kernels of
     vae_upconv_phase_weights: checks the effective kernels themselves and that the phase path is the one that runs."""
     from vaehip import ops
     gen = torch.Generator().manual_seed(77)
-    B, H, W, Ci, Co = 2, 4, 32, 128, 128
+    B, H, W, Ci, Co = UPCONV_PHASE_CASE
     x = torch.randn(B, Ci, H, W, generator=gen)
     w = torch.randn(Co, Ci, 3, 3, generator=gen) / math.sqrt(9 * Ci)
     we = ops.upconv_phase_weights(_to_dev_ohwi(w).permute(0, 2, 3, 1)).cpu()      # [4, Co, 3, 3, Ci]
@@ -590,7 +602,10 @@ def test_upconv_phase_decomposition(cuda):
 
 # (2,4,32,...): the 128-pixel halo-tile kernel with a tap mask; (7,32,64,128,256) and (3,64,64,256,256): >= 192 tiles of 8x32 pixels
 # on the low-resolution grid -- the wide-tile kernel's 2x2 tap blocks on a bf16 image of x / of dy (strided views)
-@pytest.mark.parametrize("B,H,W,Ci,Co", [(2, 4, 32, 128, 128), (7, 32, 64, 128, 256), (3, 64, 64, 256, 256)])
+BF16_UPCONV_PHASE_CASES = [(2, 4, 32, 128, 128), (7, 32, 64, 128, 256), (3, 64, 64, 256, 256)]
+
+
+@pytest.mark.parametrize("B,H,W,Ci,Co", BF16_UPCONV_PHASE_CASES)
 def test_bf16_upconv_phase_decomposition(cuda, bf16_mode, packed_weights, B, H, W, Ci, Co):
     """bf16 mode: the upsampler's forward and dgrad as four phase convolutions; the effective kernels (sums of fp32 taps) are
     rounded to bf16 once, so the reference rounds the SUMS, not the taps."""
@@ -805,7 +820,10 @@ def test_groupnorm_statistics_with_large_mean(cuda, ratio):
     assert _rel(st_f.mean, zg.mean(-1)) < 1e-6
 
 
-@pytest.mark.parametrize("B,C,H,W", [(2, 512, 60, 60), (1, 128, 148, 148), (2, 256, 72, 72), (1, 512, 120, 120)])
+GN_RAGGED_CASES = [(2, 512, 60, 60), (1, 128, 148, 148), (2, 256, 72, 72), (1, 512, 120, 120)]
+
+
+@pytest.mark.parametrize("B,C,H,W", GN_RAGGED_CASES)
 def test_groupnorm_statistics_ragged_chunk_plans(cuda, B, C, H, W):
     """feature maps whose pixel count the chunk plan does not divide (resolutions 480 / 576 / 960: trailing chunks start
     beyond H*W and are empty): statistics, the normalised tensor and the backward against torch.group_norm"""
