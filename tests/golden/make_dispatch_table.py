@@ -107,7 +107,7 @@ def upwino_dgrad_args(B, H, W, Ci, Co):
 
 
 def phase_args(B, H, W, Ci, Co, dgrad, prec, tapmask, step):
-    """one phase convolution of an upsampler on the low-resolution grid (ops._phase_args)"""
+    """one phase convolution of an upsampler on the low-resolution grid (ops._upconv_phase_fwd / _upconv_phase_dgrad)"""
     if not dgrad:
         g = ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, FWD)
         a = conv_args(g, B * H * W, Co, Ci, Co, 9 * Ci, 1, Ci, prec)

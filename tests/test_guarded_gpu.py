@@ -10,7 +10,8 @@ vaehip.ops swapped for the pool's proxy (GUARDED run: NaN bytes before and behin
   (a) no guard byte of any block changed;
   (b) every operand is bytewise what it was, except the ones an op is documented to update in place (INPLACE below);
   (c) no tensor the pool handed out during the op still holds a poisoned element -- results, tensors attached to results
-      (_gstat, _gnb, _b16) and workspaces alike, except the regions named in EXEMPT;
+      (_gstat, _gnb, _b16) and workspaces alike, without exception: vaehip/ops.py asks the library before it allocates, so every
+      tensor it allocates is written by a launch;
   (d) every result of the guarded run is torch.equal to the plain run's.  The plain run's values are what the parity tests
       (test_kernels_gpu.py, test_act16_gpu.py, ...) hold against their references, so no tolerance is introduced here;
   (e) both runs recorded the same kernel names: the guarded run exercised the instantiations production allocation does.
@@ -53,24 +54,6 @@ INPLACE = {
     "pack_bf16": ("dst",),
     "sumpool": ("out",),
 }
-
-# (c): tensors left unwritten by design: (op, tensor = allocation site in the block's label, region, why, condition on the
-# recorded kernel names and the report).  All three are results that ops.py allocates BEFORE it asks the library whether the
-# kernel serves the launch and drops, without any launch, when it does not (the replacement path allocates its own): nobody
-# can read them.  The readers were checked in vaehip/ops.py (_upconv_wino_fwd / _upconv_wino_dgrad return None right after
-# _wino() does; conv_fwd returns the re-entered call's tensor).  Only a wholly unwritten tensor qualifies, and a tensor
-# returned to the caller never does (_check).
-EXEMPT = [
-    ("conv_fwd c3up", "ops._upconv_wino_fwd:", "whole tensor",
-     "vae_wino_ok refused the 9-position upsampler kernel: no conv3_upwino_kernel<false> launch, conv_fwd goes on to the phase path",
-     lambda names, u: "conv3_upwino_kernel<false>" not in names),
-    ("conv_dgrad c3up", "ops._upconv_wino_dgrad:", "whole tensor",
-     "vae_wino_ok refused the 9-position upsampler kernel: no conv3_upwino_kernel<true> launch, conv_dgrad goes on to the phase path",
-     lambda names, u: "conv3_upwino_kernel<true>" not in names),
-    ("conv_fwd bf16 storage", "ops.conv_fwd:", "whole tensor",
-     "vae_conv_io16_ok refused bf16 storage for the serving kernel: conv_fwd re-enters itself with fp32 copies and returns to_bf16() of that",
-     lambda names, u: u.label.endswith("bfloat16")),
-]
 
 SEEN = set()     # kernel families recorded over the guarded runs (test_every_kernel_family_ran_guarded)
 EXTRA_FAMILIES = ["wgrad3_wino", "wgrad3_upwino", "wgrad_wino_reduce"]
@@ -120,22 +103,6 @@ def _flatten(res):
     return out
 
 
-def _exempt(u, names, returned=()):
-    if u.count != u.numel or u.label in returned:
-        return False
-    return any(u.label.startswith(site) and cond(names, u) for _op, site, _region, _why, cond in EXEMPT)
-
-
-def _labels(pool, tensors):
-    out = set()
-    for r in tensors:
-        try:
-            out.add(pool.block_of(r).label)
-        except KeyError:
-            pass
-    return out
-
-
 def _once(pool, operands, outputs, fn, mode, options, offsets, modules):
     from vaehip import ops
     dev = torch.device("cuda")
@@ -176,7 +143,7 @@ def _check(cid, operands, fn, *, outputs=None, mode="f32", options=None, inplace
     SEEN.update(_fam(n) for n in names)
     viol = pool.violations()
     changed = pool.changed()
-    unwritten = [u for u in pool.unwritten_report() if not _exempt(u, names, _labels(pool, rg))]
+    unwritten = pool.unwritten_report()
     print(f"{cid} [{mode}{' ' + str(options) if options else ''}]: {len(pool.blocks)} blocks, kernels {names}; "
           f"violations {viol}; changed {changed}; unwritten {unwritten}")
     assert viol == [], (cid, viol)                                                                   # (a)
@@ -648,7 +615,7 @@ def test_guarded_engine_step(cuda, mode, ckpt):
             ops.PROFILER = None
             SEEN.update(_fam(n) for n in names)
             viol, changed = pool.violations(), pool.changed()
-            unwritten = [u for u in pool.unwritten_report() if not _exempt(u, names)]
+            unwritten = pool.unwritten_report()
             print(f"engine {mode} ckpt={ckpt}: {len(pool.blocks)} blocks, {len(names)} launches; violations {viol}; changed {changed}; "
                   f"unwritten {unwritten}")
             assert viol == [] and changed == [] and unwritten == [], (viol, changed, unwritten)
@@ -664,7 +631,7 @@ def test_guarded_engine_step(cuda, mode, ckpt):
             opt = tr.optimizer
             assert any(b.tensor.data_ptr() == opt.exp_avg.data_ptr() for b in pool.blocks), "AdamW state is not guarded"
             viol = pool.violations()
-            unwritten = [u for u in pool.unwritten_report() if not _exempt(u, names)]
+            unwritten = pool.unwritten_report()
             print(f"engine {mode} ckpt={ckpt} + 2 train steps: {len(pool.blocks)} blocks; violations {viol}; unwritten {unwritten}")
             assert viol == [] and unwritten == [], (viol, unwritten)
             for name, buf in (("arena.flat", arena.flat), ("arena.grad", arena.grad), ("exp_avg", opt.exp_avg), ("exp_avg_sq", opt.exp_avg_sq)):
@@ -778,6 +745,5 @@ def test_misaligned_wgrad(cuda, kind, B, H, W, Ci, Co, xf, which, mode):
 # ------------------------------------------------------------------------------------------------- coverage (last)
 def test_every_kernel_family_ran_guarded(cuda):
     """the union of kernel names recorded over the guarded runs of this module contains every family the dispatcher knows"""
-    print(f"exemptions from the unwritten-element check: {len(EXEMPT)}")
     missing = [f for f in FAMILIES + EXTRA_FAMILIES if f not in SEEN]
     assert not missing, (missing, sorted(SEEN))

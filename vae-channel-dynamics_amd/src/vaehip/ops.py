@@ -17,10 +17,6 @@ PREC_F32, PREC_BF16 = 0, 1
 # arithmetic of the conv contractions (set by the engine from training.mixed_precision); tensors stay fp32
 PRECISION = PREC_F32
 
-
-# GroupNorm statistics of a conv output from that conv's epilogue (conv_fwd(gstat_groups=)); False = always re-read the tensor
-FUSED_GN_STATS = True
-
 # bf16 image of a parameter arena (base address of the fp32 arena, its size in bytes, base address of the image):
 # weights that live inside the arena are handed to the bf16 kernels as `Wh` (set by the engine per forward)
 WEIGHTS16: Optional[Tuple[int, int, int]] = None
@@ -222,6 +218,56 @@ def _fwd_geom(kind: str, B: int, H: int, W: int, Cs: int) -> ConvGeom:
     raise ValueError(kind)
 
 
+# The conv entry points decide (every library query), then allocate, then launch, so a query may concern an output, or a bf16
+# image, that does not exist yet.  This placeholder stands for such a tensor: one this module will allocate itself.  The
+# library's answers depend on a pointer only through null / non-null and its 16-byte alignment, and the module's own
+# allocations are at least 256-byte aligned (torch's device allocator; tests/guarded.py ALIGN).  It is never dereferenced,
+# and every site replaces it by the real pointer before it launches.
+_UNALLOCATED = C.c_void_p(256)
+
+
+def _rows_args(g: ConvGeom, Co: int, Ci: int, taps: int, dgrad: bool, *, xf: int = XF_NONE, alpha: float = 1.0, st: Optional[int] = None,
+               z: int = 1, zstrides=(0, 0, 0)) -> IgemmArgs:
+    """rows-form argument block over the row grid of `g` (pointers, views and storage flags are the caller's): forward
+    (N = Co, contraction over Ci, OHWI weights read k-contiguous) or dgrad (N = Ci, contraction over Co, the same weights read
+    n-contiguous).  st: tap stride of the weights (Ci); z, zstrides: the batched GEMMs' count and A / W / C strides."""
+    a = IgemmArgs()
+    a.g = g
+    a.M = g.B * g.Ho * g.Wo
+    if dgrad:
+        a.N, a.K, a.ldc = Ci, Co, Ci
+        a.sn, a.sk = 1, taps * Ci
+    else:
+        a.N, a.K, a.ldc = Co, Ci, Co
+        a.sn, a.sk = taps * Ci, 1
+    a.st = Ci if st is None else st
+    a.batch, (a.sAb, a.sWb, a.sCb) = z, zstrides
+    a.xf, a.alpha, a.prec = xf, alpha, PRECISION
+    return a
+
+
+def _wgrad_args(g: ConvGeom, Co: int, Ci: int, *, xf: int = XF_NONE, alpha: float = 1.0, z: int = 1, zstrides=(0, 0, 0)) -> WgradArgs:
+    """wgrad-form argument block ([Co, taps, Ci] = dY^T @ patches(X) over the pixels of `g`, one split until a plan says
+    otherwise); z, zstrides: the batched GEMMs' count and dY / X / out strides"""
+    a = WgradArgs()
+    a.g = g
+    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, g.B * g.Ho * g.Wo, 1
+    a.batch, (a.sYb, a.sXb, a.sOb) = z, zstrides
+    a.xf, a.alpha, a.prec = xf, alpha, PRECISION
+    return a
+
+
+def _reduce_splits(partial, bpart, ns: int, n: int, Co: int, wout, bout):
+    """fixed-order sums over the ns splits of a weight gradient: the slab partial [ns, n] into wout (None: one split, the kernel
+    wrote wout itself) and the bias slab bpart [ns, Co] (None: no bias gradient) into bout"""
+    if partial is not None and bpart is not None:  # one launch for both reductions
+        lib.call("vae_reduce_splits2", _p(partial), ns, n, _p(wout), _p(bpart), Co, _p(bout), _stream())
+    elif partial is not None:
+        lib.call("vae_reduce_splits", _p(partial), ns, n, _p(wout), _stream())
+    elif bpart is not None:
+        lib.call("vae_reduce_splits", _p(bpart), ns, Co, _p(bout), _stream())
+
+
 # bf16 mode stores activations as bf16 (round 3): every conv output with at least ACT16_MIN_C channels, the residual stream
 # and the gradients of both -- what autocast keeps for the reference (src/train.py:147-154).  GroupNorm statistics, tracker
 # sums, the loss, the narrow tensors (image, latents, moments) and the parameters stay fp32.  False = fp32 storage with bf16
@@ -278,14 +324,11 @@ def act_image32_ok(kind: str, x_shape, Co: int, Ci: int) -> bool:
     return H % 8 == 0 and W % 16 == 0 and Ci % 32 == 0 and Co % 64 == 0 and Cs == Ci
 
 
-# bf16 mode with fp32 storage (ACT_BF16 = False) keeps gradients that only feed bf16 kernels as bf16 images (the dgrad outputs
-# of the halo-tile kernels and the GroupNorm-backward outputs).  False = fp32 gradients everywhere (the round-1 behaviour).
-GRAD_IMAGES = True
-
-
 def grad_image_ok(kind: str, x_shape, Co: int, Ci: int) -> bool:
-    """bf16 mode: may the OUTPUT gradient of this layer (forward input x_shape) be handed to its dgrad and wgrad as a bf16 image?"""
-    if PRECISION != PREC_BF16 or WEIGHTS16 is None or kind != "c3" or not GRAD_IMAGES:
+    """bf16 mode: may the OUTPUT gradient of this layer (forward input x_shape) be handed to its dgrad and wgrad as a bf16 image?
+    (bf16 mode with fp32 storage, ACT_BF16 = False, keeps gradients that only feed bf16 kernels as bf16 images: the dgrad
+    outputs of the halo-tile kernels and the GroupNorm-backward outputs)"""
+    if PRECISION != PREC_BF16 or WEIGHTS16 is None or kind != "c3":
         return False
     B, H, W, Cs = x_shape
     g = _fwd_geom(kind, B, H, W, Cs)
@@ -312,10 +355,13 @@ def gn_apply_bf16(x: torch.Tensor, st: "Stats", xf: int) -> torch.Tensor:
 WINOGRAD = True
 
 
-def _wino(a: IgemmArgs, dev):
-    """transformed weights for the launch `a` describes when the Winograd kernel serves it (a.Wu is set), else None"""
-    if not WINOGRAD or PRECISION != PREC_F32 or not lib.query("vae_wino_ok", C.byref(a)):
-        return None
+def _wino_ok(a: IgemmArgs) -> bool:
+    """does a Winograd kernel serve the launch `a` describes?"""
+    return WINOGRAD and PRECISION == PREC_F32 and bool(lib.query("vae_wino_ok", C.byref(a)))
+
+
+def _wino_weights(a: IgemmArgs, dev):
+    """transformed weights for a launch _wino_ok accepted (a.Wu is set)"""
     wu = torch.empty((int(lib.query("vae_wino_weight_floats", C.byref(a))),), device=dev, dtype=torch.float32)
     lib.call("vae_wino_weights", C.byref(a), _p(wu), _stream())
     a.Wu = _p(wu)
@@ -340,28 +386,6 @@ def upconv_phase_weights(wv: torch.Tensor) -> torch.Tensor:
     return we
 
 
-def _phase_args(x_lo_shape, Co, Ci, dgrad: bool) -> IgemmArgs:
-    """argument block of one phase convolution on the low-resolution grid (pointers / views filled by the caller)"""
-    B, H, W, _ = x_lo_shape
-    a = IgemmArgs()
-    if not dgrad:
-        a.g = ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, MODE_FWD)
-        a.M, a.N, a.K, a.ldc = B * H * W, Co, Ci, Co
-        a.sn, a.sk, a.st = 9 * Ci, 1, Ci
-    else:
-        a.g = ConvGeom(B, H, W, Co, H, W, 9, 1, 1, 1, MODE_DGRAD)
-        a.M, a.N, a.K, a.ldc = B * H * W, Ci, Co, Ci
-        a.sn, a.sk, a.st = 1, 9 * Ci, Ci
-    a.batch, a.sAb, a.sWb, a.sCb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec = XF_NONE, 1.0, PRECISION
-    return a
-
-
-def _phase_weight_ptrs(a: IgemmArgs, we: torch.Tensor, ph: int, we16: Optional[torch.Tensor]):
-    a.W = _p(we[ph])
-    a.Wh = _p(we16[ph]) if we16 is not None else None
-
-
 def _phase_weights(wv):
     """effective kernels of the four phases, and their bf16 image in bf16 mode"""
     we = upconv_phase_weights(wv)
@@ -379,17 +403,13 @@ def _upconv_wino_fwd(x, wv, bias):
         return None
     B, H, W, Cs = x.shape
     Co, _, _, Ci = wv.shape
-    a = IgemmArgs()
-    a.g = ConvGeom(B, H, W, Cs, 2 * H, 2 * W, 9, 1, 1, 1, MODE_UP2X)
-    a.M, a.N, a.K, a.ldc = B * 4 * H * W, Co, Ci, Co
-    a.sn, a.sk, a.st = 9 * Ci, 1, Ci
-    a.batch, a.sAb, a.sWb, a.sCb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec = XF_NONE, 1.0, PRECISION
-    out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.float32)
-    a.A, a.W, a.C, a.bias = _p(x), _p(wv), _p(out), _p(bias)
-    wu = _wino(a, x.device)
-    if wu is None:
+    a = _rows_args(ConvGeom(B, H, W, Cs, 2 * H, 2 * W, 9, 1, 1, 1, MODE_UP2X), Co, Ci, 9, False)
+    a.A, a.W, a.C, a.bias = _p(x), _p(wv), _UNALLOCATED, _p(bias)
+    if not _wino_ok(a):
         return None
+    out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.float32)
+    a.C = _p(out)
+    wu = _wino_weights(a, x.device)  # (kept alive until the launch is enqueued; the allocator orders its reuse on the stream)
     _launch_igemm(a)
     return out
 
@@ -401,17 +421,13 @@ def _upconv_wino_dgrad(dy, wv, in_hw):
     B, Hy, Wy, Co = dy.shape
     H, W = in_hw
     _, _, _, Ci = wv.shape
-    a = IgemmArgs()
-    a.g = ConvGeom(B, Hy, Wy, Co, H, W, 9, 1, 1, 1, MODE_UP2X_DGRAD)
-    a.M, a.N, a.K, a.ldc = B * H * W, Ci, Co, Ci
-    a.sn, a.sk, a.st = 1, 9 * Ci, Ci
-    a.batch, a.sAb, a.sWb, a.sCb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec = XF_NONE, 1.0, PRECISION
-    out = torch.empty((B, H, W, Ci), device=dy.device, dtype=torch.float32)
-    a.A, a.W, a.C = _p(dy), _p(wv), _p(out)
-    wu = _wino(a, dy.device)
-    if wu is None:
+    a = _rows_args(ConvGeom(B, Hy, Wy, Co, H, W, 9, 1, 1, 1, MODE_UP2X_DGRAD), Co, Ci, 9, True)
+    a.A, a.W, a.C = _p(dy), _p(wv), _UNALLOCATED
+    if not _wino_ok(a):
         return None
+    out = torch.empty((B, H, W, Ci), device=dy.device, dtype=torch.float32)
+    a.C = _p(out)
+    wu = _wino_weights(a, dy.device)
     _launch_igemm(a)
     return out
 
@@ -423,39 +439,34 @@ def _upconv_phase_fwd(x, wv, bias, want16: bool):
     Co, _, _, Ci = wv.shape
     if Cs != Ci:
         return None
-    a = _phase_args(x.shape, Co, Ci, False)
-    a.A, a.W = _p(x), _p(wv)
-    a.bias = _p(bias)
-    a.c_step = 2
-    a.Wh = _wh(wv)  # (eligibility of the bf16 kernel: any aligned image will do for the query)
-    a.tapmask = _phase_tapmask(0, 0)
+    a = _rows_args(ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, MODE_FWD), Co, Ci, 9, False)  # one phase, on the low-resolution grid
+    a.A, a.W, a.Wh, a.bias = _p(x), _p(wv), _wh(wv), _p(bias)  # (W / Wh: the layer's own stand for the phase kernels in the queries)
+    a.c_step, a.tapmask = 2, _phase_tapmask(0, 0)
     xb = x.dtype == torch.bfloat16
-    x16 = None
+    use16 = False
     if PRECISION == PREC_BF16 and a.Wh is not None and Cs % 8 == 0:
         # bf16 image of the low-resolution input (a resnet output, no GroupNorm in front): the wide-tile kernel takes the four
-        # phase convolutions as 2x2 tap blocks
-        a.A16 = a.A  # placeholder with the right alignment for the query
-        a.out_bf16 = 1 if want16 else 0
-        ok = bool(lib.query("vae_conv_phase_ok", C.byref(a)))
-        if ok and want16 and not lib.query("vae_conv_io16_ok", C.byref(a)):
+        # phase convolutions as 2x2 tap blocks.  The image is a bf16 x itself, else a copy made below (a misaligned fp32 x is
+        # refused through A: the bf16 halo-tile kernels take 16-byte aligned operands only)
+        a.A16, a.out_bf16 = (_p(x) if xb else _UNALLOCATED), int(want16)
+        use16 = bool(lib.query("vae_conv_phase_ok", C.byref(a)))
+        if use16 and want16 and not lib.query("vae_conv_io16_ok", C.byref(a)):
             a.out_bf16, want16 = 0, False
-        if ok:
-            x16 = x if xb else pack_bf16(x, torch.empty(x.shape, device=x.device, dtype=torch.bfloat16))
-            a.A16 = _p(x16)
-            if not xb:
-                x._b16 = x16  # the layer's weight gradient reads the same image
-        else:
+        if not use16:
             a.A16, a.out_bf16 = None, 0
-    if x16 is None:
+    if not use16:
         if xb or not lib.query("vae_conv_phase_ok", C.byref(a)):
             return None
         want16 = False
+    elif not xb:
+        x._b16 = pack_bf16(x, torch.empty(x.shape, device=x.device, dtype=torch.bfloat16))  # the layer's weight gradient reads the same image
+        a.A16 = _p(x._b16)
     out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
     a.C = _p(out)
     we, we16 = _phase_weights(wv)
     for pa in (0, 1):
         for pb in (0, 1):
-            _phase_weight_ptrs(a, we, pa * 2 + pb, we16)
+            a.W, a.Wh = _p(we[pa * 2 + pb]), None if we16 is None else _p(we16[pa * 2 + pb])
             a.tapmask, a.c_oy, a.c_ox = _phase_tapmask(pa, pb), pa, pb
             _launch_igemm(a)
     return out
@@ -468,30 +479,28 @@ def _upconv_phase_dgrad(dy, wv, in_hw, dy16=None):
     B, Hy, Wy, Co = src.shape
     H, W = in_hw
     _, _, _, Ci = wv.shape
-    a = _phase_args((B, H, W, Ci), Co, Ci, True)
-    a.A, a.W = _p(src), _p(wv)
-    a.a_step = 2
-    a.Wh = _wh(wv)
-    a.tapmask = _phase_tapmask(0, 0)
+    a = _rows_args(ConvGeom(B, H, W, Co, H, W, 9, 1, 1, 1, MODE_DGRAD), Co, Ci, 9, True)  # one phase, on the low-resolution grid
+    a.A, a.W, a.Wh = _p(src), _p(wv), _wh(wv)
+    a.a_step, a.tapmask = 2, _phase_tapmask(0, 0)
     use16 = False
     if PRECISION == PREC_BF16 and a.Wh is not None and Co % 8 == 0:
-        a.A16 = a.A
+        # the image: dy16, else a copy of dy made below (a misaligned fp32 dy is refused through A, as in _upconv_phase_fwd)
+        a.A16 = _p(dy16) if dy16 is not None else _UNALLOCATED
         use16 = bool(lib.query("vae_conv_phase_ok", C.byref(a)))
-        if use16:
-            if dy16 is None:
-                dy16 = pack_bf16(dy, torch.empty(dy.shape, device=dy.device, dtype=torch.bfloat16))
-            a.A16 = _p(dy16)
-        else:
+        if not use16:
             a.A16 = None
     if not use16 and (dy is None or not lib.query("vae_conv_phase_ok", C.byref(a))):
         return None
+    if use16 and dy16 is None:
+        dy16 = pack_bf16(dy, torch.empty(dy.shape, device=dy.device, dtype=torch.bfloat16))
+        a.A16 = _p(dy16)
     out = torch.empty((B, H, W, Ci), device=src.device, dtype=torch.float32)
     a.C = _p(out)
     we, we16 = _phase_weights(wv)
     first = True
     for pa in (0, 1):
         for pb in (0, 1):
-            _phase_weight_ptrs(a, we, pa * 2 + pb, we16)
+            a.W, a.Wh = _p(we[pa * 2 + pb]), None if we16 is None else _p(we16[pa * 2 + pb])
             a.tapmask, a.a_oy, a.a_ox = _phase_tapmask(pa, pb), pa, pb
             a.res = None if first else _p(out)  # the four phases add up
             _launch_igemm(a)
@@ -537,13 +546,8 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
     g = _fwd_geom(kind, B, H, W, Cs)
     if xf != XF_NONE and not lib.query("vae_xf_fusable_rows", C.byref(g), B * g.Ho * g.Wo, Ci):
         x, xf = gn_apply(x, stats, xf), XF_NONE  # tiny spatial size: several batch items per tile
-    if res is not None:
-        _chk_act(res, "conv_fwd.res")
-        assert res.shape == (B, g.Ho, g.Wo, Co)
-        res = _like(res, want16)  # the residual is stored like the output
-    out = torch.empty((B, g.Ho, g.Wo, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
-    a = IgemmArgs()
-    a.A, a.W, a.C, a.bias, a.res = _p(x), _p(wv), _p(out), _p(bias), _p(res)
+    a = _rows_args(g, Co, Ci, taps, False, xf=xf)
+    a.A, a.W, a.Wh, a.C, a.bias, a.track = _p(x), _p(wv), _wh(wv), _UNALLOCATED, _p(bias), _p(track)
     xb = x.dtype == torch.bfloat16
     if a16 is not None:
         a.A16 = _p(a16)
@@ -551,22 +555,22 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
         a.A16 = _p(x)   # a bf16 tensor IS its own image; the dispatcher turns it into a_bf16 for the flat kernels
     elif xb:
         a.a_bf16 = 1    # bf16 storage with a transform on load: the flat / <= 4-channel kernels
-    a.out_bf16, a.res_bf16 = int(want16), _b16(res)
+    a.out_bf16 = int(want16)
+    if res is not None:  # the residual is stored like the output: res itself, or a copy made once the storage is settled
+        _chk_act(res, "conv_fwd.res")
+        assert res.shape == (B, g.Ho, g.Wo, Co)
+        a.res, a.res_bf16 = (_p(res) if _b16(res) == a.out_bf16 else _UNALLOCATED), a.out_bf16
     if xf != XF_NONE:
         assert stats is not None and stats.scale.shape == (B, Cs)
         a.scale, a.shift = _p(stats.scale), _p(stats.shift)
-    a.track = _p(track)
-    a.g = g
-    a.M, a.N, a.K, a.ldc = B * g.Ho * g.Wo, Co, Ci, Co
-    a.sn, a.sk, a.st = taps * Ci, 1, Ci
-    a.batch, a.sAb, a.sWb, a.sCb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec, a.Wh = xf, 1.0, PRECISION, _wh(wv)
     if track is not None:
         assert track.numel() >= ((a.M + 127) // 128) * Co
     if (a.A16 or a.a_bf16 or a.out_bf16 or a.res_bf16) and not lib.query("vae_conv_io16_ok", C.byref(a)):
-        # the kernel serving this launch takes fp32 storage only (unvectorised shapes, a tracked halo-tile output, ...)
+        # the kernel serving this launch takes fp32 storage only (unvectorised shapes, a tracked halo-tile output, ...): fp32
+        # copies.  (The residual still goes through the output's storage first, so an fp32 one is rounded to bf16 as on the
+        # bf16 kernels.)
         x32 = to_f32(a16) if a16 is not None else to_f32(x)
-        y = conv_fwd(x32, w, bias, kind, xf=xf, stats=stats, res=None if res is None else to_f32(res), track=track,
+        y = conv_fwd(x32, w, bias, kind, xf=xf, stats=stats, res=None if res is None else to_f32(_like(res, want16)), track=track,
                      gstat_groups=gstat_groups, out_dtype=torch.float32)
         if not want16:
             return y
@@ -574,8 +578,14 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
         if hasattr(y, "_gstat"):
             y16._gstat = y._gstat
         return y16
-    wu = _wino(a, x.device)  # (kept alive until the launch is enqueued; the allocator orders its reuse on the stream)
-    if gstat_groups and FUSED_GN_STATS:
+    wino = _wino_ok(a)
+    if res is not None:
+        res = _like(res, want16)
+        a.res = _p(res)
+    out = torch.empty((B, g.Ho, g.Wo, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
+    a.C = _p(out)
+    wu = _wino_weights(a, x.device) if wino else None
+    if gstat_groups:  # GroupNorm statistics of the output from this launch's epilogue where the serving kernel has one
         a.gstat_groups = int(gstat_groups)
         nch = lib.query("vae_conv_gstat_chunks", C.byref(a))
         if nch > 0:
@@ -584,9 +594,6 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
             out._gstat = (ws, int(gstat_groups), nch)
     _launch_igemm(a)
     return out
-
-
-GNB_EPILOGUE = True  # GroupNorm-backward partial sums from the dgrad epilogue where the serving kernel has one (vae_conv_gnb_chunks)
 
 
 def _gnb_key(x, st, gamma, beta, silu) -> tuple:
@@ -644,36 +651,30 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, kind: str, in_hw: Tuple[int, i
     mode = MODE_DGRAD
     if kind == "c3s2" and H % 2 == 0 and W % 2 == 0 and (B * H * W // 4) % 128 == 0:
         mode = MODE_DGRAD_S2  # parity-class-major rows: only the taps a class meets are computed (9/4 instead of 9)
-    g = ConvGeom(B, Hy, Wy, Co, Hr, Wr, taps, stride, pad, pad, mode)
-    a = IgemmArgs()
-    src = dy16 if use16 else dy32
-    a.A, a.W = _p(dy32 if dy32 is not None else dy16), _p(wv)  # with A16 the kernel reads the image; A only gives the alignment
+    a = _rows_args(ConvGeom(B, Hy, Wy, Co, Hr, Wr, taps, stride, pad, pad, mode), Co, Ci, taps, True)
+    dev = dy.device
+    a.A, a.W, a.Wh = _p(dy32 if dy32 is not None else dy16), _p(wv), _wh(wv)  # with A16 the kernel reads the image; A only gives the alignment
     a.A16 = _p(dy16) if use16 else None
-    a.g = g
-    a.M, a.N, a.K, a.ldc = B * Hr * Wr, Ci, Co, Ci
-    a.sn, a.sk, a.st = 1, taps * Ci, Ci
-    a.batch, a.sAb, a.sWb, a.sCb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec, a.Wh = XF_NONE, 1.0, PRECISION, _wh(wv)
+    a.C = _UNALLOCATED
     pool = kind == "c3up"  # (the virtual-upsample fallback: the high-resolution gradient is summed 2x2 in fp32)
-    o16 = False
-    if not pool and (want16 or (out_bf16 and not forced and PRECISION == PREC_BF16 and GRAD_IMAGES and kind == "c3")):
-        a.out_bf16 = 1
-        a.C = a.A  # placeholder with the right alignment for the query
-        o16 = bool(lib.query("vae_conv_io16_ok", C.byref(a)))
-        a.out_bf16 = 1 if o16 else 0
+    if not pool and (want16 or (out_bf16 and not forced and PRECISION == PREC_BF16 and kind == "c3")):
+        a.out_bf16 = 1  # (as asked; kept when the kernel serving the launch can write it)
+        a.out_bf16 = int(lib.query("vae_conv_io16_ok", C.byref(a)))
     if a.A16 and not lib.query("vae_conv_io16_ok", C.byref(a)):  # an fp32-only kernel: hand it an fp32 copy of the gradient
         return _like(conv_dgrad(to_f32(dy16), w, kind, in_hw, out_dtype=torch.float32), want16)
-    out = torch.empty((B, Hr, Wr, Ci), device=src.device, dtype=torch.bfloat16 if o16 else torch.float32)
+    wino = _wino_ok(a)
+    out = torch.empty((B, Hr, Wr, Ci), device=dev, dtype=torch.bfloat16 if a.out_bf16 else torch.float32)
     a.C = _p(out)
-    wu = _wino(a, src.device)
-    # (a result that is re-stored as bf16 below drops its attributes: no sums are computed for it)
-    if gnb is not None and GNB_EPILOGUE and not pool and gnb.x.shape == out.shape and not (want16 and out.dtype != torch.bfloat16):
+    wu = _wino_weights(a, dev) if wino else None
+    # GroupNorm-backward partial sums from this launch's epilogue where the serving kernel has one (a result that is re-stored as
+    # bf16 below drops its attributes: no sums are computed for it)
+    if gnb is not None and not pool and gnb.x.shape == out.shape and not (want16 and out.dtype != torch.bfloat16):
         a.gnb_x, a.gnb_x_bf16 = _p(gnb.x), _b16(gnb.x)
         a.gnb_mean, a.gnb_rstd, a.gnb_gamma, a.gnb_beta = _p(gnb.st.mean), _p(gnb.st.rstd), _p(gnb.gamma), _p(gnb.beta)
         a.gnb_groups, a.gnb_silu = int(gnb.groups), int(gnb.silu)
         nch = lib.query("vae_conv_gnb_chunks", C.byref(a))
         if nch > 0:
-            ws = torch.empty((B, nch, Ci, 2), device=src.device, dtype=torch.float32)
+            ws = torch.empty((B, nch, Ci, 2), device=dev, dtype=torch.float32)
             a.gnb_ws = _p(ws)
             # (what the sums belong to: gn_bwd takes them only for exactly this GroupNorm, see _gnb_key)
             out._gnb = (ws, nch, _gnb_key(gnb.x, gnb.st, gnb.gamma, gnb.beta, gnb.silu))
@@ -681,7 +682,7 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, kind: str, in_hw: Tuple[int, i
             a.gnb_x = None
     _launch_igemm(a)
     if pool:
-        pooled = torch.empty((B, H, W, Ci), device=src.device, dtype=torch.float32)
+        pooled = torch.empty((B, H, W, Ci), device=dev, dtype=torch.float32)
         lib.call("vae_sumpool2x2", _p(out), B, H, W, Ci, _p(pooled), _stream())
         out = pooled
     if want16 and out.dtype != torch.bfloat16:
@@ -699,31 +700,30 @@ def _upconv_phase_wgrad(dy, x, gv, bgrad_out, dy16=None) -> bool:
     if Cs != Ci:
         return False
     xb = x.dtype == torch.bfloat16
-    a = WgradArgs()
+    a = _wgrad_args(ConvGeom(B, H, W, Cs, H, W, 9, 1, 1, 1, MODE_FWD), Co, Ci)  # one phase, on the low-resolution grid
     a.dY, a.X = _p(dy if dy is not None else dy16), _p(x)
-    a.g = ConvGeom(B, H, W, Cs, H, W, 9, 1, 1, 1, MODE_FWD)
-    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, B * H * W, 1
-    a.batch, a.sYb, a.sXb, a.sOb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec = XF_NONE, 1.0, PRECISION
     a.y_step, a.tapmask = 2, _phase_tapmask(0, 0)
     if not lib.query("vae_wgrad_phase_ok", C.byref(a)):
         return False
-    keep = []
-    if PRECISION == PREC_BF16 and Cs % 8 == 0 and Co % 8 == 0:
+    images = PRECISION == PREC_BF16 and Cs % 8 == 0 and Co % 8 == 0
+    x16 = None
+    if images:  # the images that exist already; the plan is asked about the others as copies made below
         x16 = x if xb else getattr(x, "_b16", None)
-        if x16 is None:
-            x16 = pack_bf16(x, torch.empty(x.shape, device=x.device, dtype=torch.bfloat16))
-        if dy16 is None:
-            dy16 = pack_bf16(dy, torch.empty(dy.shape, device=dy.device, dtype=torch.bfloat16))
-            dy._b16 = dy16  # the dgrad that follows reads the same image
-        keep = [x16, dy16]
-        a.X16, a.dY16 = _p(x16), _p(dy16)
+        a.X16 = _p(x16) if x16 is not None else _UNALLOCATED
+        a.dY16 = _p(dy16) if dy16 is not None else _UNALLOCATED
     elif xb or dy is None:
         return False  # the fp32 halo-tile kernel needs fp32 operands
     ns, fus = C.c_int32(0), C.c_int32(0)
     lib.call("vae_wgrad_plan", C.byref(a), C.byref(ns), C.byref(fus))
     ns = ns.value
     a.nsplit = ns
+    if images:
+        if x16 is None:
+            x16 = pack_bf16(x, torch.empty(x.shape, device=x.device, dtype=torch.bfloat16))
+        if dy16 is None:
+            dy16 = pack_bf16(dy, torch.empty(dy.shape, device=dy.device, dtype=torch.bfloat16))
+            dy._b16 = dy16  # the dgrad that follows reads the same image
+        a.X16, a.dY16 = _p(x16), _p(dy16)
     n = Co * 9 * Ci
     dwe = torch.empty((4, n), device=x.device, dtype=torch.float32)
     dbe = torch.empty((4, Co), device=x.device, dtype=torch.float32) if bgrad_out is not None else None
@@ -739,14 +739,8 @@ def _upconv_phase_wgrad(dy, x, gv, bgrad_out, dy16=None) -> bool:
                 a.partial = _p(partial)
             a.bias_partial = _p(bpart)
             _launch_wgrad(a)
-            if ns > 1 and bpart is not None:
-                lib.call("vae_reduce_splits2", _p(partial), ns, n, _p(dwe[ph]), _p(bpart), Co, _p(dbe[ph]), _stream())
-            elif ns > 1:
-                lib.call("vae_reduce_splits", _p(partial), ns, n, _p(dwe[ph]), _stream())
-            elif bpart is not None:
-                lib.call("vae_reduce_splits", _p(bpart), ns, Co, _p(dbe[ph]), _stream())
+            _reduce_splits(partial, bpart, ns, n, Co, dwe[ph], None if dbe is None else dbe[ph])
     lib.call("vae_upconv_fold_wgrad", _p(dwe), _p(dbe), Co, Ci, _p(gv), _p(bgrad_out), _stream())
-    del keep
     return True
 
 
@@ -795,25 +789,17 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
     assert dy.shape == (B, g.Ho, g.Wo, Co), (dy.shape, (B, g.Ho, g.Wo, Co))
     if (kind == "c3up" and PRECISION == PREC_F32 and WINOGRAD and xf == XF_NONE and x16 is None and dy32 is not None
             and x.dtype == torch.float32):
-        a = WgradArgs()  # the 9-position scheme of csrc/wgrad3_upwino.hip (fp32)
-        a.dY, a.X, a.g = _p(dy32), _p(x), g
-        a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, B * g.Ho * g.Wo, 1
-        a.batch, a.sYb, a.sXb, a.sOb = 1, 0, 0, 0
-        a.xf, a.alpha, a.prec = XF_NONE, 1.0, PRECISION
+        a = _wgrad_args(g, Co, Ci)  # the 9-position scheme of csrc/wgrad3_upwino.hip (fp32)
+        a.dY, a.X = _p(dy32), _p(x)
         if _wgrad_wino(a, gv, bgrad_out, x.device):
             return
     if kind == "c3up" and PHASE_UPCONV and xf == XF_NONE and x16 is None and _upconv_phase_wgrad(dy32, x, gv, bgrad_out, dy16):
         return
-    npix = B * g.Ho * g.Wo
     xb = x.dtype == torch.bfloat16
     use16 = dy16 is not None and (dy32 is None or grad_image_ok(kind, x.shape, Co, Ci))
-    a = WgradArgs()
+    a = _wgrad_args(g, Co, Ci, xf=xf)
     a.dY, a.X = _p(dy32 if dy32 is not None else dy16), _p(x)
     a.dY16 = _p(dy16) if use16 else None
-    a.g = g
-    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, npix, 1
-    a.batch, a.sYb, a.sXb, a.sOb = 1, 0, 0, 0
-    a.xf, a.alpha, a.prec = xf, 1.0, PRECISION
     if x16 is not None:
         a.X16 = _p(x16)
     elif xb and xf == XF_NONE:
@@ -828,7 +814,7 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
     ns, fus = C.c_int32(0), C.c_int32(0)
     lib.call("vae_wgrad_plan", C.byref(a), C.byref(ns), C.byref(fus))
     if xf != XF_NONE and not fus.value:  # tiny spatial size: several batch items per split
-        x = gn_apply(x, stats, xf)
+        x, xf = gn_apply(x, stats, xf), XF_NONE
         a.X, a.xf, a.scale, a.shift, a.x_bf16 = _p(x), XF_NONE, None, None, 0
         lib.call("vae_wgrad_plan", C.byref(a), C.byref(ns), C.byref(fus))
     if (a.X16 or a.dY16 or a.x_bf16) and not lib.query("vae_wgrad_io16_ok", C.byref(a)):
@@ -848,12 +834,7 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
         bpart = torch.empty((ns, Co), device=x.device, dtype=torch.float32)
         a.bias_partial = _p(bpart)
     _launch_wgrad(a)
-    if partial is not None and bpart is not None:  # one launch for both reductions
-        lib.call("vae_reduce_splits2", _p(partial), ns, Co * taps * Ci, _p(gv), _p(bpart), Co, _p(bgrad_out), _stream())
-    elif partial is not None:
-        lib.call("vae_reduce_splits", _p(partial), ns, Co * taps * Ci, _p(gv), _stream())
-    elif bpart is not None:
-        lib.call("vae_reduce_splits", _p(bpart), ns, Co, _p(bgrad_out), _stream())
+    _reduce_splits(partial, bpart, ns, Co * taps * Ci, Co, gv, bgrad_out)
 
 
 # ------------------------------------------------------------------ GroupNorm
@@ -871,7 +852,7 @@ def gn_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, G: int = 
     HW = H * W
     dev = x.device
     fused = getattr(x, "_gstat", None)  # partial sums left by the conv epilogue that produced x (conv_fwd(gstat_groups=G))
-    if fused is not None and fused[1] == G and FUSED_GN_STATS:
+    if fused is not None and fused[1] == G:
         ws, nch = fused[0], fused[2]
     else:
         nch = _gn_nchunk(B, HW, Cc)
@@ -994,14 +975,12 @@ def gn_bwd(x: torch.Tensor, g: torch.Tensor, st: Stats, gamma: torch.Tensor, bet
 
 
 # ------------------------------------------------------------------ batched GEMMs (attention)
-def _gemm_rows(A, Bm, out, M, N, K, sn, sk, alpha, z, sAb, sWb, sCb):
-    a = IgemmArgs()
+def _gemm_rows(A, Bm, out, M, N, K, bkm: bool, alpha, z, sAb, sWb, sCb):
+    """out[z] = alpha * A[z] @ Bm[z]^T (Bm [z,N,K]), or A[z] @ Bm[z] (bkm: Bm [z,K,N]): a one-tap convolution over M pixels in a
+    row, forward or dgrad form.  (PRECISION applies: in bf16 mode scores / context / their gradients run on the bf16 MFMA too)"""
+    a = _rows_args(ConvGeom(1, 1, M, K, 1, M, 1, 1, 0, 0, MODE_FWD), K if bkm else N, N if bkm else K, 1, bkm, alpha=alpha, st=0, z=z,
+                   zstrides=(sAb, sWb, sCb))
     a.A, a.W, a.C = _p(A), _p(Bm), _p(out)
-    a.g = ConvGeom(1, 1, M, K, 1, M, 1, 1, 0, 0, MODE_FWD)
-    a.M, a.N, a.K, a.ldc = M, N, K, N
-    a.sn, a.sk, a.st = sn, sk, 0
-    a.batch, a.sAb, a.sWb, a.sCb = z, sAb, sWb, sCb
-    a.xf, a.alpha, a.prec = XF_NONE, alpha, PRECISION  # bf16 mode: scores / context / their gradients on the bf16 MFMA too
     _launch_igemm(a)
 
 
@@ -1010,7 +989,7 @@ def gemm_nt(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tens
     z, M, K = A.shape
     N = Bm.shape[1]
     out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    _gemm_rows(A, Bm, out, M, N, K, K, 1, alpha, z, M * K, N * K, M * N)
+    _gemm_rows(A, Bm, out, M, N, K, False, alpha, z, M * K, N * K, M * N)
     return out
 
 
@@ -1019,7 +998,7 @@ def gemm_nn(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tens
     z, M, K = A.shape
     N = Bm.shape[2]
     out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    _gemm_rows(A, Bm, out, M, N, K, 1, N, alpha, z, M * K, K * N, M * N)
+    _gemm_rows(A, Bm, out, M, N, K, True, alpha, z, M * K, K * N, M * N)
     return out
 
 
@@ -1028,12 +1007,8 @@ def gemm_tn(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tens
     z, K, M = A.shape
     N = Bm.shape[2]
     out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    a = WgradArgs()
+    a = _wgrad_args(ConvGeom(1, 1, K, N, 1, K, 1, 1, 0, 0, MODE_FWD), M, N, alpha=alpha, z=z, zstrides=(K * M, K * N, M * N))
     a.dY, a.X, a.out = _p(A), _p(Bm), _p(out)
-    a.g = ConvGeom(1, 1, K, N, 1, K, 1, 1, 0, 0, MODE_FWD)
-    a.M, a.N, a.ldy, a.npix, a.nsplit = M, N, M, K, 1
-    a.batch, a.sYb, a.sXb, a.sOb = z, K * M, K * N, M * N
-    a.xf, a.alpha, a.prec = XF_NONE, alpha, PRECISION  # bf16 mode: scores / context / their gradients on the bf16 MFMA too
     _launch_wgrad(a)
     return out
 
