@@ -225,7 +225,10 @@ vae_wgrad_args wgrad_canon(const vae_wgrad_args& a) {
     vae_wgrad_args t = b;
     if (t.X16 != nullptr && t.xf == VAE_XF_NONE) t.X = reinterpret_cast<const float*>(t.X16);
     if (t.dY16 != nullptr && t.dY == nullptr) t.dY = reinterpret_cast<const float*>(t.dY16);
-    if (!wgrad_use_tile_bf16(t)) {
+    // (a tensor the halo-tile kernels cannot take as an image -- rows that are no whole 16-byte pieces -- is a stored tensor too)
+    const bool images = (t.dY16 == nullptr || (aligned16(t.dY16) && t.ldy % 8 == 0 && t.M % 8 == 0)) &&
+                        (t.X16 == nullptr || t.xf != VAE_XF_NONE || (aligned16(t.X16) && t.g.Cs % 8 == 0));
+    if (!wgrad_use_tile_bf16(t) || !images) {
       if (b.X16 != nullptr && b.xf == VAE_XF_NONE) { b.X = reinterpret_cast<const float*>(b.X16); b.X16 = nullptr; b.x_bf16 = 1; }
       if (b.dY16 != nullptr) { b.dY = reinterpret_cast<const float*>(b.dY16); b.dY16 = nullptr; b.y_bf16 = 1; }
     }

@@ -449,9 +449,8 @@ def _upconv_phase_fwd(x, wv, bias, want16: bool):
         # phase convolutions as 2x2 tap blocks.  The image is a bf16 x itself, else a copy made below (a misaligned fp32 x is
         # refused through A: the bf16 halo-tile kernels take 16-byte aligned operands only)
         a.A16, a.out_bf16 = (_p(x) if xb else _UNALLOCATED), int(want16)
+        # (only the wide-tile kernel serves a phase with an image, and it writes either storage: vae_conv_io16_ok is not asked)
         use16 = bool(lib.query("vae_conv_phase_ok", C.byref(a)))
-        if use16 and want16 and not lib.query("vae_conv_io16_ok", C.byref(a)):
-            a.out_bf16, want16 = 0, False
         if not use16:
             a.A16, a.out_bf16 = None, 0
     if not use16:
@@ -571,13 +570,10 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
         # bf16 kernels.)
         x32 = to_f32(a16) if a16 is not None else to_f32(x)
         y = conv_fwd(x32, w, bias, kind, xf=xf, stats=stats, res=None if res is None else to_f32(_like(res, want16)), track=track,
-                     gstat_groups=gstat_groups, out_dtype=torch.float32)
-        if not want16:
-            return y
-        y16 = to_bf16(y)
-        if hasattr(y, "_gstat"):
-            y16._gstat = y._gstat
-        return y16
+                     gstat_groups=None if want16 else gstat_groups, out_dtype=torch.float32)
+        # (epilogue statistics would describe the UNROUNDED result: a re-stored one goes without them, and gn_stats makes its own
+        # pass over the tensor as stored)
+        return to_bf16(y) if want16 else y
     wino = _wino_ok(a)
     if res is not None:
         res = _like(res, want16)
