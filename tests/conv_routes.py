@@ -28,9 +28,12 @@ PURE = {"vae_igemm_kernel_name", "vae_wgrad_kernel_name", "vae_wgrad_plan", "vae
 # the helper entry points a route is made of besides its kernels
 HELPERS = ("vae_gn_apply", "vae_unpack_bf16", "vae_pack_bf16", "vae_sumpool2x2", "vae_reduce_splits", "vae_reduce_splits2",
            "vae_upconv_fold_wgrad", "vae_wgrad_wino_reduce")
-TRACED = ("_upconv_wino_fwd", "_upconv_wino_dgrad", "_upconv_phase_fwd", "_upconv_phase_dgrad", "_upconv_phase_wgrad",
-          "conv_fwd", "conv_dgrad", "conv_wgrad", "_wgrad_wino", "_reduce_splits", "_phase_weights", "_like", "to_f32", "to_bf16",
-          "_grad16", "act_image_ok", "act_image32_ok", "grad_image_ok")
+TRACED = ("_upconv_wino", "_upconv_wino_fwd", "_upconv_wino_dgrad", "_upconv_phase_fwd", "_upconv_phase_dgrad", "_upconv_phase_wgrad",
+          "conv_fwd", "conv_dgrad", "conv_wgrad", "_wgrad_wino", "_reduce_splits", "_phase_weights", "_phases", "_like", "to_f32", "to_bf16",
+          "_grad16", "act_image_ok", "act_image32_ok", "grad_image_ok",
+          # the launch descriptions the conv entry points build their argument blocks from
+          "out_hw", "_fwd_geom", "_rows_args", "_wgrad_form", "fwd_args", "dgrad_args", "up2x_dgrad_args", "phase_args", "wgrad_args",
+          "wgrad_phase_args")
 
 # statements of the traced functions that no case can execute: {source text: why}.  At most 5, each shown unreachable by a
 # library query on the host (tests/test_conv_routes_host.py); everything else runs inside a case whose value is compared.

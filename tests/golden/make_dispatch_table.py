@@ -1,8 +1,9 @@
 """Kernel-selection table of libvaehip: what every pure dispatch query answers over a grid of argument blocks.
 
-For each convolution launch it records the kernel name, the fused-epilogue chunk counts and the capability answers; for each
-weight gradient the kernel name, the split plan and the capability answers; for each forward geometry the two bf16 image
-checks.  The pointers are fake (16-byte-aligned integers): no query dereferences them and none touches the HIP runtime,
+The argument blocks are the ones vaehip.ops launches: every case is built by the launch descriptions of ops.py (fwd_args,
+dgrad_args, ..., gemm_tn_args); only the fake pointers and the per-variant fields are added here.  For each convolution
+launch it records the kernel name, the fused-epilogue chunk counts and the capability answers; for each weight gradient
+the kernel name, the split plan and the capability answers; for each forward geometry the two bf16 image checks.  The pointers are fake (16-byte-aligned integers): no query dereferences them and none touches the HIP runtime,
 so the table is built on any host.  Nothing here calls a launching entry point (vae_igemm_rows, vae_wgrad,
 vae_wino_weights, vae_wgrad_wino): with fake pointers a launch would fault a real device.
 
@@ -21,10 +22,10 @@ SRC = os.path.join(ROOT, "vae-channel-dynamics_amd", "src")
 if SRC not in sys.path:
     sys.path.insert(0, SRC)
 
-from vaehip.lib import ConvGeom, IgemmArgs, WgradArgs, lib  # noqa: E402
+from vaehip import ops  # noqa: E402
+from vaehip.lib import lib  # noqa: E402
 
-FWD, UP2X, DGRAD, DGRAD_S2, UP2X_DGRAD = 0, 1, 2, 3, 4
-F32, BF16 = 0, 1
+F32, BF16 = ops.PREC_F32, ops.PREC_BF16
 OPTIONS = ("flat_conv", "no_wino", "no_wino4", "no_wide", "no_thin_mfma", "no_wgrad_dma")
 
 # the SDXL-VAE's convolutions: (kind, Cin, Cout, divisor of the image size giving the layer's input map)
@@ -48,78 +49,6 @@ def ptr(misaligned=False):
     return _next[0] + (4 if misaligned else 0)
 
 
-def out_hw(kind, H, W):
-    if kind == "c3s2":  # padding (0, 1, 0, 1)
-        return (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
-    if kind == "c3up":
-        return 2 * H, 2 * W
-    return H, W
-
-
-def fwd_geom(kind, B, H, W, Cs):
-    Ho, Wo = out_hw(kind, H, W)
-    if kind == "c3":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 1, 1, 1, FWD)
-    if kind == "c1":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 1, 1, 0, 0, FWD)
-    if kind == "c3s2":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 2, 0, 0, FWD)
-    return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 1, 1, 1, UP2X)
-
-
-# --------------------------------------------------------------------------- convolution (vae_igemm_args) cases
-def conv_args(g, M, N, K, ldc, sn, sk, st, prec, xf=0):
-    a = IgemmArgs()
-    a.A, a.W, a.C = ptr(), ptr(), ptr()
-    a.g = g
-    a.M, a.N, a.K, a.ldc = M, N, K, ldc
-    a.sn, a.sk, a.st = sn, sk, st
-    a.batch, a.alpha, a.prec, a.xf = 1, 1.0, prec, xf
-    if xf:
-        a.scale, a.shift = ptr(), ptr()
-    return a
-
-
-def conv_fwd_args(kind, B, H, W, Ci, Co, prec, xf=0):
-    g = fwd_geom(kind, B, H, W, Ci)
-    taps = 1 if kind == "c1" else 9
-    return conv_args(g, B * g.Ho * g.Wo, Co, Ci, Co, taps * Ci, 1, Ci, prec, xf)
-
-
-def conv_dgrad_args(kind, B, H, W, Ci, Co, prec, s2=True):
-    """the launch conv_dgrad builds: dy [B, Ho, Wo, Co] -> [B, H, W, Ci] (c3up: the virtual-upsample form, rows 2H x 2W)"""
-    Hy, Wy = out_hw(kind, H, W)
-    taps = 1 if kind == "c1" else 9
-    Hr, Wr, stride, pad, mode = H, W, 1, 1 if taps == 9 else 0, DGRAD
-    if kind == "c3up":
-        Hr, Wr = 2 * H, 2 * W
-    if kind == "c3s2":
-        stride, pad = 2, 0
-        if s2 and H % 2 == 0 and W % 2 == 0 and (B * H * W // 4) % 128 == 0:
-            mode = DGRAD_S2
-    g = ConvGeom(B, Hy, Wy, Co, Hr, Wr, taps, stride, pad, pad, mode)
-    return conv_args(g, B * Hr * Wr, Ci, Co, Ci, 1, taps * Ci, Ci, prec)
-
-
-def upwino_dgrad_args(B, H, W, Ci, Co):
-    g = ConvGeom(B, 2 * H, 2 * W, Co, H, W, 9, 1, 1, 1, UP2X_DGRAD)
-    return conv_args(g, B * H * W, Ci, Co, Ci, 1, 9 * Ci, Ci, F32)
-
-
-def phase_args(B, H, W, Ci, Co, dgrad, prec, tapmask, step):
-    """one phase convolution of an upsampler on the low-resolution grid (ops._upconv_phase_fwd / _upconv_phase_dgrad)"""
-    if not dgrad:
-        g = ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, FWD)
-        a = conv_args(g, B * H * W, Co, Ci, Co, 9 * Ci, 1, Ci, prec)
-        a.c_step = step
-    else:
-        g = ConvGeom(B, H, W, Co, H, W, 9, 1, 1, 1, DGRAD)
-        a = conv_args(g, B * H * W, Ci, Co, Ci, 1, 9 * Ci, Ci, prec)
-        a.a_step = step
-    a.tapmask = tapmask
-    return a
-
-
 P, MIS = "ptr", "misaligned"  # in a variant: a fresh fake pointer, a fresh one 4 bytes off 16-byte alignment
 
 
@@ -129,6 +58,12 @@ def _copy(a, **fields):
     for k, v in fields.items():
         setattr(b, k, ptr(v == MIS) if v in (P, MIS) else v)
     return b
+
+
+# --------------------------------------------------------------------------- convolution (vae_igemm_args) cases
+def conv_ptrs(a):
+    """the block of a convolution launch with its operands (and the transform's scale / shift) in place"""
+    return _copy(a, A=P, W=P, C=P, **(dict(scale=P, shift=P) if a.xf else {}))
 
 
 def conv_variants(a, dgrad):
@@ -162,27 +97,8 @@ def conv_result(dll, a):
 
 
 # --------------------------------------------------------------------------- weight-gradient (vae_wgrad_args) cases
-def wgrad_args(kind, B, H, W, Ci, Co, prec, xf=0):
-    g = fwd_geom(kind, B, H, W, Ci)
-    a = WgradArgs()
-    a.dY, a.X = ptr(), ptr()
-    a.g = g
-    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, B * g.Ho * g.Wo, 1
-    a.batch, a.alpha, a.prec, a.xf = 1, 1.0, prec, xf
-    if xf:
-        a.scale, a.shift = ptr(), ptr()
-    return a
-
-
-def wgrad_phase_args(B, H, W, Ci, Co, prec, tapmask, step):
-    g = ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, FWD)
-    a = WgradArgs()
-    a.dY, a.X = ptr(), ptr()
-    a.g = g
-    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, B * H * W, 1
-    a.batch, a.alpha, a.prec = 1, 1.0, prec
-    a.tapmask, a.y_step = tapmask, step
-    return a
+def wgrad_ptrs(a):
+    return _copy(a, dY=P, X=P, **(dict(scale=P, shift=P) if a.xf else {}))
 
 
 def wgrad_variants(a):
@@ -239,35 +155,35 @@ def cases():
                 continue
             for B in BATCHES:
                 base = f"{kind}:{Ci}>{Co}:{H}x{W}:B{B}"
-                yield f"geom|{base}", "geom", (fwd_geom(kind, B, H, W, Ci), Co, Ci)
+                yield f"geom|{base}", "geom", (ops._fwd_geom(kind, B, H, W, Ci), Co, Ci)
                 for prec in (F32, BF16):
                     for xf in (0, 1, 2):
-                        for tag, a in conv_variants(conv_fwd_args(kind, B, H, W, Ci, Co, prec, xf), False):
+                        for tag, a in conv_variants(conv_ptrs(ops.fwd_args(kind, B, H, W, Ci, Co, Ci, xf=xf, prec=prec)), False):
                             yield f"fwd|{base}|p{prec}|xf{xf}|{tag}", "conv", a
-                    for tag, a in conv_variants(conv_dgrad_args(kind, B, H, W, Ci, Co, prec), True):
+                    for tag, a in conv_variants(conv_ptrs(ops.dgrad_args(kind, B, H, W, Co, Ci, prec=prec)), True):
                         yield f"dgrad|{base}|p{prec}|{tag}", "conv", a
                     for xf in (0, 2):
-                        for tag, a in wgrad_variants(wgrad_args(kind, B, H, W, Ci, Co, prec, xf)):
+                        for tag, a in wgrad_variants(wgrad_ptrs(ops.wgrad_args(kind, B, H, W, Ci, Co, Ci, xf=xf, prec=prec))):
                             yield f"wgrad|{base}|p{prec}|xf{xf}|{tag}", "wgrad", a
                 if kind == "c3s2":  # the plain DGRAD form of a stride-2 layer as well
                     for prec in (F32, BF16):
-                        yield f"dgrad|{base}|p{prec}|nos2", "conv", conv_dgrad_args(kind, B, H, W, Ci, Co, prec, s2=False)
+                        yield f"dgrad|{base}|p{prec}|nos2", "conv", conv_ptrs(ops.dgrad_args(kind, B, H, W, Co, Ci, s2=False, prec=prec))
                 if kind == "c3up":
-                    a = upwino_dgrad_args(B, H, W, Ci, Co)
+                    a = conv_ptrs(ops.up2x_dgrad_args(B, H, W, Co, Ci, prec=F32))
                     yield f"updgrad|{base}", "conv", a
                     yield f"updgrad|{base}|Wu", "conv", _copy(a, Wu=P)
                     # the four phase convolutions on the low-resolution grid
                     for prec in (F32, BF16):
                         for tm in (0x1b, 0x36, 0xd8, 0x1b0):
                             for dg in (False, True):
-                                a = phase_args(B, H, W, Ci, Co, dg, prec, tm, 2)
+                                a = _copy(conv_ptrs(ops.phase_args(B, H, W, Co, Ci, dg, prec=prec)), tapmask=tm)
                                 pre = f"phase|{base}|p{prec}|{'dg' if dg else 'fw'}|{tm:x}"
                                 yield pre, "conv", a
                                 v = ([("A16", dict(Wh=P, A16=P)), ("A16,out16", dict(Wh=P, A16=P, out_bf16=1)), ("out16", dict(Wh=P, out_bf16=1))]
                                      if prec == BF16 else [("xf2", dict(xf=2, scale=P, shift=P))])
                                 for tag, kw in v:
                                     yield f"{pre}|{tag}", "conv", _copy(a, **kw)
-                            w = wgrad_phase_args(B, H, W, Ci, Co, prec, tm, 2)
+                            w = _copy(wgrad_ptrs(ops.wgrad_phase_args(B, H, W, Co, Ci, prec=prec)), tapmask=tm)
                             yield f"wphase|{base}|p{prec}|{tm:x}", "wgrad", w
                             if prec == BF16:
                                 for tag, kw in (("X16,dY16", dict(X16=P, dY16=P)), ("dY16", dict(dY16=P)), ("xf2", dict(xf=2, scale=P, shift=P))):
@@ -277,23 +193,12 @@ def cases():
         for z in (1, 2, 16):
             for prec in (F32, BF16):
                 for Cc in (512,):
-                    for nm, M, N, K, sn, sk in (("nt", T, T, Cc, Cc, 1), ("nn", T, Cc, T, 1, Cc), ("nt_c", T, Cc, T, T, 1)):
-                        a = IgemmArgs()
-                        a.A, a.W, a.C = ptr(), ptr(), ptr()
-                        a.g = ConvGeom(1, 1, M, K, 1, M, 1, 1, 0, 0, FWD)
-                        a.M, a.N, a.K, a.ldc = M, N, K, N
-                        a.sn, a.sk, a.st = sn, sk, 0
-                        a.batch, a.sAb, a.sWb, a.sCb = z, M * K, N * K, M * N
-                        a.xf, a.alpha, a.prec = 0, 0.125, prec
+                    for nm, M, N, K, bkm in (("nt", T, T, Cc, False), ("nn", T, Cc, T, True), ("nt_c", T, Cc, T, False)):
+                        a = conv_ptrs(ops.gemm_rows_args(M, N, K, bkm, 0.125, z, prec=prec))
                         yield f"gemm_{nm}|T{T}|z{z}|p{prec}", "conv", a
                         yield f"gemm_{nm}|T{T}|z{z}|p{prec}|misaligned", "conv", _copy(a, A=MIS)
                     for nm, K, M, N in (("tn", T, T, Cc), ("tn_c", T, Cc, Cc), ("tn_s", T, Cc, T)):
-                        a = WgradArgs()
-                        a.dY, a.X, a.out = ptr(), ptr(), ptr()
-                        a.g = ConvGeom(1, 1, K, N, 1, K, 1, 1, 0, 0, FWD)
-                        a.M, a.N, a.ldy, a.npix, a.nsplit = M, N, M, K, 1
-                        a.batch, a.sYb, a.sXb, a.sOb = z, K * M, K * N, M * N
-                        a.xf, a.alpha, a.prec = 0, 1.0, prec
+                        a = _copy(wgrad_ptrs(ops.gemm_tn_args(M, N, K, 1.0, z, prec=prec)), out=P)
                         yield f"gemm_{nm}|T{T}|z{z}|p{prec}", "wgrad", a
                         yield f"gemm_{nm}|T{T}|z{z}|p{prec}|odd_sXb", "wgrad", _copy(a, sXb=K * N + 1)
 

@@ -379,10 +379,8 @@ def test_storage_flags_are_refused_where_no_kernel_honours_them(cuda):
     wd = _to_dev_ohwi(torch.randn(128, 128, 3, 3) / 30)
     y = ops.conv_fwd(x, wd, None, "c3")
     assert y.dtype == torch.float32 and not ops.act16()
-    a = ops.IgemmArgs()
+    a = ops.fwd_args("c3", 1, 8, 32, 128, 128, 128, prec=ops.PREC_F32)
     a.A, a.W, a.C = ops._p(x), ops._p(ops.ohwi(wd)), ops._p(y)
-    a.g = ops._fwd_geom("c3", 1, 8, 32, 128)
-    a.M, a.N, a.K, a.ldc, a.sn, a.sk, a.st, a.batch, a.alpha = 256, 128, 128, 128, 9 * 128, 1, 128, 1, 1.0
     assert lib.query("vae_conv_io16_ok", C.byref(a)) == 1
     a.out_bf16 = 1
     assert lib.query("vae_conv_io16_ok", C.byref(a)) == 0

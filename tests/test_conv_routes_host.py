@@ -138,8 +138,8 @@ def test_a_phase_with_an_operand_image_runs_on_the_wide_kernel_which_writes_eith
                 for pa in (0, 1):
                     for pb in (0, 1):
                         for out16 in (0, 1):
-                            a = mdt._copy(mdt.phase_args(B, H, W, Ci, Co, False, mdt.BF16, ops._phase_tapmask(pa, pb), 2),
-                                          Wh=mdt.P, A16=mdt.P, out_bf16=out16)
+                            a = mdt._copy(mdt.conv_ptrs(ops.phase_args(B, H, W, Co, Ci, False, prec=ops.PREC_BF16)),
+                                          tapmask=ops._phase_tapmask(pa, pb), Wh=mdt.P, A16=mdt.P, out_bf16=out16)
                             if dll.vae_conv_phase_ok(C.byref(a)):
                                 accepted += 1
                                 assert dll.vae_conv_io16_ok(C.byref(a)) == 1, (B, H, W, Ci, Co, out16)

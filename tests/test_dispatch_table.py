@@ -1,6 +1,7 @@
 """Kernel selection pinned on the host: every pure dispatch query of libvaehip (kernel names, epilogue chunk counts, split
 plans, capability answers) over the case grid of tests/golden/make_dispatch_table.py must give what the committed table
 records.  Fake pointers, no launch: runs without a GPU."""
+import ctypes as C
 import json
 import os
 import re
@@ -48,3 +49,30 @@ def test_dispatch_table_matches_golden():
     assert any(k.startswith("wgrad|c3s2") and "dma" in v[0] for k, v in golden.items())
     assert {1} <= {v[0] for k, v in golden.items() if k.startswith("geom|")}
     assert len(golden) > 1000
+
+
+def test_image_queries_answer_for_the_blocks_ops_launches():
+    """vae_bf16_act_image_ok / vae_bf16_grad_image_ok build their forward, dgrad and weight-gradient blocks by hand in
+    csrc/dispatch.cpp; over EVERY geometry of the grid they must say what the dispatcher selects for the blocks ops.py
+    launches there (bf16 arithmetic, the weights' image present)"""
+    from vaehip import ops
+    from vaehip.lib import lib
+    dll = lib.load()
+    n = act_yes = grad_yes = 0
+    for kind, Ci, Co, div in mdt.LAYERS:
+        for R in mdt.SIZES:
+            for B in mdt.BATCHES:
+                H = W = R // div
+                fwd = mdt._copy(mdt.conv_ptrs(ops.fwd_args(kind, B, H, W, Ci, Co, Ci, prec=mdt.BF16)), Wh=mdt.P)
+                dgrad = mdt._copy(mdt.conv_ptrs(ops.dgrad_args(kind, B, H, W, Co, Ci, prec=mdt.BF16)), Wh=mdt.P)
+                wgrad = mdt.wgrad_ptrs(ops.wgrad_args(kind, B, H, W, Ci, Co, Ci, prec=mdt.BF16))
+                tiles = kind == "c3" and Ci % 8 == 0 and ops._kernel_name("vae_wgrad_kernel_name", wgrad).startswith("wgrad3_tile_bf16_kernel")
+                act = tiles and ops._kernel_name("vae_igemm_kernel_name", fwd).startswith("conv3_tile_bf16_kernel")
+                grad = tiles and Co % 8 == 0 and ops._kernel_name("vae_igemm_kernel_name", dgrad).startswith("conv3_tile_bf16_kernel")
+                g = ops._fwd_geom(kind, B, H, W, Ci)
+                case = (kind, Ci, Co, H, W, B)
+                assert bool(dll.vae_bf16_act_image_ok(C.byref(g), Co, Ci)) == act, case
+                assert bool(dll.vae_bf16_grad_image_ok(C.byref(g), Co, Ci)) == grad, case
+                n, act_yes, grad_yes = n + 1, act_yes + act, grad_yes + grad
+    assert n == len(mdt.LAYERS) * len(mdt.SIZES) * len(mdt.BATCHES)
+    assert min(act_yes, n - act_yes, grad_yes, n - grad_yes) >= 100, (n, act_yes, grad_yes)  # both answers occur: no pass by vacuity

@@ -65,12 +65,6 @@ def _fam(name):
     return re.split(r"[ <(]", name)[0].replace("_kernels", "").replace("_kernel", "")
 
 
-def _out_hw(kind, H, W):
-    if kind == "c3s2":
-        return (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
-    return (2 * H, 2 * W) if kind == "c3up" else (H, W)
-
-
 @contextlib.contextmanager
 def _mode(mode, options):
     """f32 | bf16 (bf16 arithmetic, fp32 storage: the bf16_mode fixture's setting) | bf16p (+ packed weight image) |
@@ -161,10 +155,11 @@ def _check(cid, operands, fn, *, outputs=None, mode="f32", options=None, inplace
 
 # ------------------------------------------------------------------------------------------------- convolutions
 def _conv_operands(kind, B, H, W, Ci, Co, seed, *, res=False, gn=False, gstat=False, add=False, store16=False, dy16=False):
+    from vaehip import ops
     gen = torch.Generator().manual_seed(seed)
     k = 1 if kind == "c1" else 3
     cpad = 4 if Ci == 3 else Ci
-    Ho, Wo = _out_hw(kind, H, W)
+    Ho, Wo = ops.out_hw(kind, H, W)
     x = torch.zeros(B, H, W, cpad)
     x[..., :Ci] = torch.randn(B, H, W, Ci, generator=gen) * 1.3 + 0.2
     t = dict(x=x, w=torch.randn(Co, k, k, Ci, generator=gen) / math.sqrt(Ci * k * k), b=torch.randn(Co, generator=gen),
@@ -673,9 +668,8 @@ def test_misaligned_forward(cuda, kind, B, H, W, Ci, Co, xf, which, mode):
     fn = _conv_fn(kind, H, W, Ci, Co, xf=xf, dgrad=False, wgrad=False, stats_x="x_al")
     cid = f"misaligned fwd {which} xf={xf} {kind} {B}x{H}x{W} {Ci}->{Co}"
     offsets = {"x" if which == "activation" else "w": 4}
-    Ho, Wo = _out_hw(kind, H, W)
     geom = ops._fwd_geom(kind, B, H, W, x.shape[-1])
-    if which == "activation" and xf and not lib.query("vae_xf_fusable_rows", ctypes.byref(geom), B * Ho * Wo, Ci):
+    if which == "activation" and xf and not lib.query("vae_xf_fusable_rows", ctypes.byref(geom), B * geom.Ho * geom.Wo, Ci):
         # a transform that cannot be fused at this size goes through vae_gn_apply first, which refuses the misaligned tensor
         # loudly: there is no launch of a conv kernel on it to compare
         with pytest.raises(VaeHipError, match="gn_apply: unaligned"):

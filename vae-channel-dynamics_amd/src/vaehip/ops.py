@@ -194,28 +194,108 @@ class Stats(NamedTuple):
     shift: torch.Tensor  # [B, C]
 
 
-# ------------------------------------------------------------------ conv geometry
+# ------------------------------------------------------------------ launch descriptions
+# Every launch's argument block from integers alone (no tensor, no allocation, no library call); the entry points add the
+# pointers, views, storage flags and epilogue fields.  tests/golden/make_dispatch_table.py and the tests build their blocks
+# here too.  H, W: the layer's forward INPUT map; Cs: channels of its storage (>= Ci); prec: None = PRECISION.
 def out_hw(kind: str, H: int, W: int) -> Tuple[int, int]:
     if kind in ("c3", "c1"):
         return H, W
-    if kind == "c3s2":
+    if kind == "c3s2":  # padding (0, 1, 0, 1)
         return (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
     if kind == "c3up":
         return 2 * H, 2 * W
     raise ValueError(kind)
 
 
+_KIND = {"c3": (9, 1, 1, MODE_FWD), "c1": (1, 1, 0, MODE_FWD), "c3s2": (9, 2, 0, MODE_FWD), "c3up": (9, 1, 1, MODE_UP2X)}  # taps, stride, pad, forward mode
+
+
 def _fwd_geom(kind: str, B: int, H: int, W: int, Cs: int) -> ConvGeom:
-    Ho, Wo = out_hw(kind, H, W)
-    if kind == "c3":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 1, 1, 1, MODE_FWD)
-    if kind == "c1":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 1, 1, 0, 0, MODE_FWD)
-    if kind == "c3s2":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 2, 0, 0, MODE_FWD)
-    if kind == "c3up":
-        return ConvGeom(B, H, W, Cs, Ho, Wo, 9, 1, 1, 1, MODE_UP2X)
-    raise ValueError(kind)
+    taps, stride, pad, mode = _KIND[kind]
+    return ConvGeom(B, H, W, Cs, *out_hw(kind, H, W), taps, stride, pad, pad, mode)
+
+
+def _rows_args(g: ConvGeom, Co: int, Ci: int, dgrad: bool, prec: Optional[int], xf: int = XF_NONE) -> IgemmArgs:
+    """rows form over the row grid of `g`: forward (N = Co, contraction over Ci, OHWI weights read k-contiguous) or dgrad
+    (N = Ci, contraction over Co, the same weights read n-contiguous)"""
+    a = IgemmArgs(g=g)
+    a.M = g.B * g.Ho * g.Wo
+    if dgrad:
+        a.N, a.K, a.ldc = Ci, Co, Ci
+        a.sn, a.sk = 1, g.taps * Ci
+    else:
+        a.N, a.K, a.ldc = Co, Ci, Co
+        a.sn, a.sk = g.taps * Ci, 1
+    a.st, a.batch = Ci, 1
+    a.xf, a.alpha, a.prec = xf, 1.0, PRECISION if prec is None else prec
+    return a
+
+
+def _wgrad_form(g: ConvGeom, Co: int, Ci: int, prec: Optional[int], xf: int = XF_NONE) -> WgradArgs:
+    """wgrad form: [Co, taps, Ci] = dY^T @ patches(X) over the pixels of `g`, one split until a plan says otherwise"""
+    a = WgradArgs(g=g)
+    a.M, a.N, a.ldy, a.npix, a.nsplit, a.batch = Co, Ci, Co, g.B * g.Ho * g.Wo, 1, 1
+    a.xf, a.alpha, a.prec = xf, 1.0, PRECISION if prec is None else prec
+    return a
+
+
+def fwd_args(kind: str, B: int, H: int, W: int, Cs: int, Co: int, Ci: int, *, xf: int = XF_NONE, prec: Optional[int] = None) -> IgemmArgs:
+    """forward of a layer (c3up: MODE_UP2X, the virtual-upsample kernel and the upsampler-Winograd forward alike)"""
+    return _rows_args(_fwd_geom(kind, B, H, W, Cs), Co, Ci, False, prec, xf)
+
+
+def dgrad_args(kind: str, B: int, H: int, W: int, Co: int, Ci: int, *, s2: bool = True, prec: Optional[int] = None) -> IgemmArgs:
+    """dgrad of a layer: dy [B,Ho,Wo,Co] -> rows over the input map (c3up: the virtual-upsample form over 2H x 2W, which the
+    caller sums 2x2).  A stride-2 layer gets the parity-class form where its map allows (s2 = False: the plain form)."""
+    Hy, Wy = out_hw(kind, H, W)
+    Hr, Wr = (Hy, Wy) if kind == "c3up" else (H, W)
+    taps, stride, pad, _ = _KIND[kind]
+    mode = MODE_DGRAD
+    if s2 and kind == "c3s2" and H % 2 == 0 and W % 2 == 0 and (B * H * W // 4) % 128 == 0:
+        mode = MODE_DGRAD_S2  # parity-class-major rows: only the taps a class meets are computed (9/4 instead of 9)
+    return _rows_args(ConvGeom(B, Hy, Wy, Co, Hr, Wr, taps, stride, pad, pad, mode), Co, Ci, True, prec)
+
+
+def up2x_dgrad_args(B: int, H: int, W: int, Co: int, Ci: int, *, prec: Optional[int] = None) -> IgemmArgs:
+    """dgrad of an upsampler in one pass (MODE_UP2X_DGRAD): dy [B,2H,2W,Co] -> rows over the low-resolution map"""
+    return _rows_args(ConvGeom(B, 2 * H, 2 * W, Co, H, W, 9, 1, 1, 1, MODE_UP2X_DGRAD), Co, Ci, True, prec)
+
+
+def phase_args(B: int, H: int, W: int, Co: int, Ci: int, dgrad: bool, *, prec: Optional[int] = None) -> IgemmArgs:
+    """one phase convolution of an upsampler on its low-resolution map, forward or dgrad: the high-resolution side is read
+    (dgrad) or written (forward) at every second pixel; tap mask of phase (0, 0), which the caller replaces per phase"""
+    a = _rows_args(ConvGeom(B, H, W, Co if dgrad else Ci, H, W, 9, 1, 1, 1, MODE_DGRAD if dgrad else MODE_FWD), Co, Ci, dgrad, prec)
+    a.a_step, a.c_step = (2, 0) if dgrad else (0, 2)  # (0 = a plain view)
+    a.tapmask = _phase_tapmask(0, 0)
+    return a
+
+
+def wgrad_args(kind: str, B: int, H: int, W: int, Cs: int, Co: int, Ci: int, *, xf: int = XF_NONE, prec: Optional[int] = None) -> WgradArgs:
+    """weight gradient of a layer, over its forward geometry"""
+    return _wgrad_form(_fwd_geom(kind, B, H, W, Cs), Co, Ci, prec, xf)
+
+
+def wgrad_phase_args(B: int, H: int, W: int, Co: int, Ci: int, *, prec: Optional[int] = None) -> WgradArgs:
+    """weight gradient of one phase of an upsampler (dy read at every second pixel; tap mask of phase (0, 0))"""
+    a = _wgrad_form(ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, MODE_FWD), Co, Ci, prec)
+    a.y_step, a.tapmask = 2, _phase_tapmask(0, 0)
+    return a
+
+
+def gemm_rows_args(M: int, N: int, K: int, bkm: bool, alpha: float, z: int, *, prec: Optional[int] = None) -> IgemmArgs:
+    """z dense GEMMs out = alpha * A @ Bm^T (A [M,K], Bm [N,K]), or A @ Bm (bkm: Bm [K,N]): a one-tap convolution over M pixels
+    in a row, forward or dgrad form.  (In bf16 mode scores / context / their gradients run on the bf16 MFMA too)"""
+    a = _rows_args(ConvGeom(1, 1, M, K, 1, M, 1, 1, 0, 0, MODE_FWD), K if bkm else N, N if bkm else K, bkm, prec)
+    a.st, a.alpha, a.batch, a.sAb, a.sWb, a.sCb = 0, alpha, z, M * K, N * K, M * N
+    return a
+
+
+def gemm_tn_args(M: int, N: int, K: int, alpha: float, z: int, *, prec: Optional[int] = None) -> WgradArgs:
+    """z dense GEMMs out = alpha * A^T @ Bm (A [K,M], Bm [K,N]): a one-tap weight gradient over K pixels in a row"""
+    a = _wgrad_form(ConvGeom(1, 1, K, N, 1, K, 1, 1, 0, 0, MODE_FWD), M, N, prec)
+    a.alpha, a.batch, a.sYb, a.sXb, a.sOb = alpha, z, K * M, K * N, M * N
+    return a
 
 
 # The conv entry points decide (every library query), then allocate, then launch, so a query may concern an output, or a bf16
@@ -224,37 +304,6 @@ def _fwd_geom(kind: str, B: int, H: int, W: int, Cs: int) -> ConvGeom:
 # allocations are at least 256-byte aligned (torch's device allocator; tests/guarded.py ALIGN).  It is never dereferenced,
 # and every site replaces it by the real pointer before it launches.
 _UNALLOCATED = C.c_void_p(256)
-
-
-def _rows_args(g: ConvGeom, Co: int, Ci: int, taps: int, dgrad: bool, *, xf: int = XF_NONE, alpha: float = 1.0, st: Optional[int] = None,
-               z: int = 1, zstrides=(0, 0, 0)) -> IgemmArgs:
-    """rows-form argument block over the row grid of `g` (pointers, views and storage flags are the caller's): forward
-    (N = Co, contraction over Ci, OHWI weights read k-contiguous) or dgrad (N = Ci, contraction over Co, the same weights read
-    n-contiguous).  st: tap stride of the weights (Ci); z, zstrides: the batched GEMMs' count and A / W / C strides."""
-    a = IgemmArgs()
-    a.g = g
-    a.M = g.B * g.Ho * g.Wo
-    if dgrad:
-        a.N, a.K, a.ldc = Ci, Co, Ci
-        a.sn, a.sk = 1, taps * Ci
-    else:
-        a.N, a.K, a.ldc = Co, Ci, Co
-        a.sn, a.sk = taps * Ci, 1
-    a.st = Ci if st is None else st
-    a.batch, (a.sAb, a.sWb, a.sCb) = z, zstrides
-    a.xf, a.alpha, a.prec = xf, alpha, PRECISION
-    return a
-
-
-def _wgrad_args(g: ConvGeom, Co: int, Ci: int, *, xf: int = XF_NONE, alpha: float = 1.0, z: int = 1, zstrides=(0, 0, 0)) -> WgradArgs:
-    """wgrad-form argument block ([Co, taps, Ci] = dY^T @ patches(X) over the pixels of `g`, one split until a plan says
-    otherwise); z, zstrides: the batched GEMMs' count and dY / X / out strides"""
-    a = WgradArgs()
-    a.g = g
-    a.M, a.N, a.ldy, a.npix, a.nsplit = Co, Ci, Co, g.B * g.Ho * g.Wo, 1
-    a.batch, (a.sYb, a.sXb, a.sOb) = z, zstrides
-    a.xf, a.alpha, a.prec = xf, alpha, PRECISION
-    return a
 
 
 def _reduce_splits(partial, bpart, ns: int, n: int, Co: int, wout, bout):
@@ -303,9 +352,7 @@ def act_image_ok(kind: str, x_shape, Co: int, Ci: int) -> bool:
     """bf16 mode: may this layer's forward and wgrad read a bf16 image of the transformed input (gn_apply_bf16)?"""
     if PRECISION != PREC_BF16 or WEIGHTS16 is None or kind != "c3":
         return False
-    B, H, W, Cs = x_shape
-    g = _fwd_geom(kind, B, H, W, Cs)
-    return bool(lib.query("vae_bf16_act_image_ok", C.byref(g), Co, Ci))
+    return bool(lib.query("vae_bf16_act_image_ok", C.byref(_fwd_geom(kind, *x_shape)), Co, Ci))
 
 
 # fp32 mode: a Winograd workgroup covers 64 output channels, so GroupNorm+SiLU fused into its halo staging is recomputed
@@ -330,9 +377,7 @@ def grad_image_ok(kind: str, x_shape, Co: int, Ci: int) -> bool:
     outputs of the halo-tile kernels and the GroupNorm-backward outputs)"""
     if PRECISION != PREC_BF16 or WEIGHTS16 is None or kind != "c3":
         return False
-    B, H, W, Cs = x_shape
-    g = _fwd_geom(kind, B, H, W, Cs)
-    return bool(lib.query("vae_bf16_grad_image_ok", C.byref(g), int(Co), int(Ci)))
+    return bool(lib.query("vae_bf16_grad_image_ok", C.byref(_fwd_geom(kind, *x_shape)), int(Co), int(Ci)))
 
 
 def _grad16(dy: torch.Tensor) -> Optional[torch.Tensor]:
@@ -389,47 +434,45 @@ def upconv_phase_weights(wv: torch.Tensor) -> torch.Tensor:
 def _phase_weights(wv):
     """effective kernels of the four phases, and their bf16 image in bf16 mode"""
     we = upconv_phase_weights(wv)
-    we16 = None
-    if PRECISION == PREC_BF16:
-        we16 = torch.empty(we.shape, device=we.device, dtype=torch.bfloat16)
-        pack_bf16(we, we16)
+    we16 = pack_bf16(we, torch.empty(we.shape, device=we.device, dtype=torch.bfloat16)) if PRECISION == PREC_BF16 else None
     return we, we16
 
 
-def _upconv_wino_fwd(x, wv, bias):
-    """fp32: conv3x3(nearest_upsample_2x(x)) with 9 multiplications per low-resolution pixel and channel pair
-    (csrc/conv3_upwino.hip) -> [B,2H,2W,Co], or None when the kernel does not serve the layer"""
-    if not WINOGRAD or PRECISION != PREC_F32 or x.dtype != torch.float32:
-        return None
-    B, H, W, Cs = x.shape
-    Co, _, _, Ci = wv.shape
-    a = _rows_args(ConvGeom(B, H, W, Cs, 2 * H, 2 * W, 9, 1, 1, 1, MODE_UP2X), Co, Ci, 9, False)
-    a.A, a.W, a.C, a.bias = _p(x), _p(wv), _UNALLOCATED, _p(bias)
+def _phases(wv: Optional[torch.Tensor] = None):
+    """the four phases of an upsampler in launch order -> (index, tap mask, row offset, column offset, W, Wh): W / Wh are the
+    phase's effective kernel and its bf16 image, made here from the layer's OHWI weights `wv` (None: the weight gradient)"""
+    we, we16 = _phase_weights(wv) if wv is not None else (None, None)
+    for ph, (pa, pb) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        yield ph, _phase_tapmask(pa, pb), pa, pb, None if we is None else _p(we[ph]), None if we16 is None else _p(we16[ph])
+
+
+def _upconv_wino(a: IgemmArgs, src, wv, bias):
+    """fp32: the upsampler launch `a` over `src` on csrc/conv3_upwino.hip (9 multiplications per low-resolution pixel and
+    channel pair) -> the tensor of its row grid, or None when the kernel does not serve the layer"""
+    a.A, a.W, a.C, a.bias = _p(src), _p(wv), _UNALLOCATED, _p(bias)
     if not _wino_ok(a):
         return None
-    out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.float32)
+    out = torch.empty((a.g.B, a.g.Ho, a.g.Wo, a.N), device=src.device, dtype=torch.float32)
     a.C = _p(out)
-    wu = _wino_weights(a, x.device)  # (kept alive until the launch is enqueued; the allocator orders its reuse on the stream)
+    wu = _wino_weights(a, src.device)  # (kept alive until the launch is enqueued; the allocator orders its reuse on the stream)
     _launch_igemm(a)
     return out
+
+
+def _upconv_wino_fwd(x, wv, bias):
+    """fp32: conv3x3(nearest_upsample_2x(x)) -> [B,2H,2W,Co], or None"""
+    if not WINOGRAD or PRECISION != PREC_F32 or x.dtype != torch.float32:
+        return None
+    Co, _, _, Ci = wv.shape
+    return _upconv_wino(fwd_args("c3up", *x.shape, Co, Ci), x, wv, bias)
 
 
 def _upconv_wino_dgrad(dy, wv, in_hw):
     """fp32: dy [B,2H,2W,Co] -> gradient wrt the low-resolution input [B,H,W,Ci] (3x3 dgrad + 2x2 sum-pool in one pass), or None"""
     if not WINOGRAD or PRECISION != PREC_F32 or dy is None or dy.dtype != torch.float32:
         return None
-    B, Hy, Wy, Co = dy.shape
-    H, W = in_hw
-    _, _, _, Ci = wv.shape
-    a = _rows_args(ConvGeom(B, Hy, Wy, Co, H, W, 9, 1, 1, 1, MODE_UP2X_DGRAD), Co, Ci, 9, True)
-    a.A, a.W, a.C = _p(dy), _p(wv), _UNALLOCATED
-    if not _wino_ok(a):
-        return None
-    out = torch.empty((B, H, W, Ci), device=dy.device, dtype=torch.float32)
-    a.C = _p(out)
-    wu = _wino_weights(a, dy.device)
-    _launch_igemm(a)
-    return out
+    Co, _, _, Ci = wv.shape
+    return _upconv_wino(up2x_dgrad_args(dy.shape[0], *in_hw, Co, Ci), dy, wv, None)
 
 
 def _upconv_phase_fwd(x, wv, bias, want16: bool):
@@ -439,9 +482,8 @@ def _upconv_phase_fwd(x, wv, bias, want16: bool):
     Co, _, _, Ci = wv.shape
     if Cs != Ci:
         return None
-    a = _rows_args(ConvGeom(B, H, W, Ci, H, W, 9, 1, 1, 1, MODE_FWD), Co, Ci, 9, False)  # one phase, on the low-resolution grid
+    a = phase_args(B, H, W, Co, Ci, False)
     a.A, a.W, a.Wh, a.bias = _p(x), _p(wv), _wh(wv), _p(bias)  # (W / Wh: the layer's own stand for the phase kernels in the queries)
-    a.c_step, a.tapmask = 2, _phase_tapmask(0, 0)
     xb = x.dtype == torch.bfloat16
     use16 = False
     if PRECISION == PREC_BF16 and a.Wh is not None and Cs % 8 == 0:
@@ -462,12 +504,8 @@ def _upconv_phase_fwd(x, wv, bias, want16: bool):
         a.A16 = _p(x._b16)
     out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
     a.C = _p(out)
-    we, we16 = _phase_weights(wv)
-    for pa in (0, 1):
-        for pb in (0, 1):
-            a.W, a.Wh = _p(we[pa * 2 + pb]), None if we16 is None else _p(we16[pa * 2 + pb])
-            a.tapmask, a.c_oy, a.c_ox = _phase_tapmask(pa, pb), pa, pb
-            _launch_igemm(a)
+    for _, a.tapmask, a.c_oy, a.c_ox, a.W, a.Wh in _phases(wv):
+        _launch_igemm(a)
     return out
 
 
@@ -478,9 +516,8 @@ def _upconv_phase_dgrad(dy, wv, in_hw, dy16=None):
     B, Hy, Wy, Co = src.shape
     H, W = in_hw
     _, _, _, Ci = wv.shape
-    a = _rows_args(ConvGeom(B, H, W, Co, H, W, 9, 1, 1, 1, MODE_DGRAD), Co, Ci, 9, True)  # one phase, on the low-resolution grid
+    a = phase_args(B, H, W, Co, Ci, True)
     a.A, a.W, a.Wh = _p(src), _p(wv), _wh(wv)
-    a.a_step, a.tapmask = 2, _phase_tapmask(0, 0)
     use16 = False
     if PRECISION == PREC_BF16 and a.Wh is not None and Co % 8 == 0:
         # the image: dy16, else a copy of dy made below (a misaligned fp32 dy is refused through A, as in _upconv_phase_fwd)
@@ -495,15 +532,9 @@ def _upconv_phase_dgrad(dy, wv, in_hw, dy16=None):
         a.A16 = _p(dy16)
     out = torch.empty((B, H, W, Ci), device=src.device, dtype=torch.float32)
     a.C = _p(out)
-    we, we16 = _phase_weights(wv)
-    first = True
-    for pa in (0, 1):
-        for pb in (0, 1):
-            a.W, a.Wh = _p(we[pa * 2 + pb]), None if we16 is None else _p(we16[pa * 2 + pb])
-            a.tapmask, a.a_oy, a.a_ox = _phase_tapmask(pa, pb), pa, pb
-            a.res = None if first else _p(out)  # the four phases add up
-            _launch_igemm(a)
-            first = False
+    for ph, a.tapmask, a.a_oy, a.a_ox, a.W, a.Wh in _phases(wv):
+        a.res = _p(out) if ph else None  # the four phases add up
+        _launch_igemm(a)
     return out
 
 
@@ -540,12 +571,10 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
         if out is not None:
             return out if (out.dtype == torch.bfloat16) == want16 else _like(out, want16)
     B, H, W, Cs = x.shape
-    taps = kh * kw
-    assert taps == (1 if kind == "c1" else 9) and Ci <= Cs, (kind, wv.shape, x.shape)
-    g = _fwd_geom(kind, B, H, W, Cs)
-    if xf != XF_NONE and not lib.query("vae_xf_fusable_rows", C.byref(g), B * g.Ho * g.Wo, Ci):
-        x, xf = gn_apply(x, stats, xf), XF_NONE  # tiny spatial size: several batch items per tile
-    a = _rows_args(g, Co, Ci, taps, False, xf=xf)
+    assert kh * kw == (1 if kind == "c1" else 9) and Ci <= Cs, (kind, wv.shape, x.shape)
+    a = fwd_args(kind, B, H, W, Cs, Co, Ci, xf=xf)
+    if xf != XF_NONE and not lib.query("vae_xf_fusable_rows", C.byref(a.g), a.M, Ci):
+        x, xf, a.xf = gn_apply(x, stats, xf), XF_NONE, XF_NONE  # tiny spatial size: several batch items per tile
     a.A, a.W, a.Wh, a.C, a.bias, a.track = _p(x), _p(wv), _wh(wv), _UNALLOCATED, _p(bias), _p(track)
     xb = x.dtype == torch.bfloat16
     if a16 is not None:
@@ -557,7 +586,7 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
     a.out_bf16 = int(want16)
     if res is not None:  # the residual is stored like the output: res itself, or a copy made once the storage is settled
         _chk_act(res, "conv_fwd.res")
-        assert res.shape == (B, g.Ho, g.Wo, Co)
+        assert res.shape == (B, a.g.Ho, a.g.Wo, Co)
         a.res, a.res_bf16 = (_p(res) if _b16(res) == a.out_bf16 else _UNALLOCATED), a.out_bf16
     if xf != XF_NONE:
         assert stats is not None and stats.scale.shape == (B, Cs)
@@ -578,7 +607,7 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kin
     if res is not None:
         res = _like(res, want16)
         a.res = _p(res)
-    out = torch.empty((B, g.Ho, g.Wo, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
+    out = torch.empty((B, a.g.Ho, a.g.Wo, Co), device=x.device, dtype=torch.bfloat16 if want16 else torch.float32)
     a.C = _p(out)
     wu = _wino_weights(a, x.device) if wino else None
     if gstat_groups:  # GroupNorm statistics of the output from this launch's epilogue where the serving kernel has one
@@ -621,10 +650,8 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, kind: str, in_hw: Tuple[int, i
     _chk_act(dy, "conv_dgrad.dy")
     wv = ohwi(w)
     Co, kh, kw, Ci = wv.shape
-    taps = kh * kw
-    B, Hy, Wy, Cy = dy.shape
-    assert Cy == Co
-    H, W = in_hw
+    B, (H, W) = dy.shape[0], in_hw
+    assert kh * kw == (1 if kind == "c1" else 9) and dy.shape == (B, *out_hw(kind, H, W), Co), (kind, wv.shape, dy.shape, in_hw)
     forced = out_dtype is not None
     want16 = (out_dtype == torch.bfloat16) if forced else (act16() and Ci >= ACT16_MIN_C)
     use16 = dy16 is not None and (dy32 is None or grad_image_ok(kind, (B, H, W, Ci), Co, Ci))
@@ -636,18 +663,7 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, kind: str, in_hw: Tuple[int, i
         out = _upconv_phase_dgrad(dy32, wv, in_hw, dy16)
         if out is not None:
             return _like(out, want16)
-    if kind == "c3up":
-        Hr, Wr, stride, pad = 2 * H, 2 * W, 1, 1
-    elif kind == "c3s2":
-        Hr, Wr, stride, pad = H, W, 2, 0
-    elif kind == "c3":
-        Hr, Wr, stride, pad = H, W, 1, 1
-    else:
-        Hr, Wr, stride, pad = H, W, 1, 0
-    mode = MODE_DGRAD
-    if kind == "c3s2" and H % 2 == 0 and W % 2 == 0 and (B * H * W // 4) % 128 == 0:
-        mode = MODE_DGRAD_S2  # parity-class-major rows: only the taps a class meets are computed (9/4 instead of 9)
-    a = _rows_args(ConvGeom(B, Hy, Wy, Co, Hr, Wr, taps, stride, pad, pad, mode), Co, Ci, taps, True)
+    a = dgrad_args(kind, B, H, W, Co, Ci)
     dev = dy.device
     a.A, a.W, a.Wh = _p(dy32 if dy32 is not None else dy16), _p(wv), _wh(wv)  # with A16 the kernel reads the image; A only gives the alignment
     a.A16 = _p(dy16) if use16 else None
@@ -659,7 +675,7 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, kind: str, in_hw: Tuple[int, i
     if a.A16 and not lib.query("vae_conv_io16_ok", C.byref(a)):  # an fp32-only kernel: hand it an fp32 copy of the gradient
         return _like(conv_dgrad(to_f32(dy16), w, kind, in_hw, out_dtype=torch.float32), want16)
     wino = _wino_ok(a)
-    out = torch.empty((B, Hr, Wr, Ci), device=dev, dtype=torch.bfloat16 if a.out_bf16 else torch.float32)
+    out = torch.empty((B, a.g.Ho, a.g.Wo, Ci), device=dev, dtype=torch.bfloat16 if a.out_bf16 else torch.float32)
     a.C = _p(out)
     wu = _wino_weights(a, dev) if wino else None
     # GroupNorm-backward partial sums from this launch's epilogue where the serving kernel has one (a result that is re-stored as
@@ -696,9 +712,8 @@ def _upconv_phase_wgrad(dy, x, gv, bgrad_out, dy16=None) -> bool:
     if Cs != Ci:
         return False
     xb = x.dtype == torch.bfloat16
-    a = _wgrad_args(ConvGeom(B, H, W, Cs, H, W, 9, 1, 1, 1, MODE_FWD), Co, Ci)  # one phase, on the low-resolution grid
+    a = wgrad_phase_args(B, H, W, Co, Ci)
     a.dY, a.X = _p(dy if dy is not None else dy16), _p(x)
-    a.y_step, a.tapmask = 2, _phase_tapmask(0, 0)
     if not lib.query("vae_wgrad_phase_ok", C.byref(a)):
         return False
     images = PRECISION == PREC_BF16 and Cs % 8 == 0 and Co % 8 == 0
@@ -725,17 +740,11 @@ def _upconv_phase_wgrad(dy, x, gv, bgrad_out, dy16=None) -> bool:
     dbe = torch.empty((4, Co), device=x.device, dtype=torch.float32) if bgrad_out is not None else None
     partial = torch.empty((ns, n), device=x.device, dtype=torch.float32) if ns > 1 else None
     bpart = torch.empty((ns, Co), device=x.device, dtype=torch.float32) if bgrad_out is not None else None
-    for pa in (0, 1):
-        for pb in (0, 1):
-            ph = pa * 2 + pb
-            a.tapmask, a.y_oy, a.y_ox = _phase_tapmask(pa, pb), pa, pb
-            if ns == 1:
-                a.out = _p(dwe[ph])
-            else:
-                a.partial = _p(partial)
-            a.bias_partial = _p(bpart)
-            _launch_wgrad(a)
-            _reduce_splits(partial, bpart, ns, n, Co, dwe[ph], None if dbe is None else dbe[ph])
+    a.partial, a.bias_partial = _p(partial), _p(bpart)
+    for ph, a.tapmask, a.y_oy, a.y_ox, _, _ in _phases():
+        a.out = _p(dwe[ph]) if ns == 1 else None  # (one split: the kernel writes the phase's gradient itself)
+        _launch_wgrad(a)
+        _reduce_splits(partial, bpart, ns, n, Co, dwe[ph], None if dbe is None else dbe[ph])
     lib.call("vae_upconv_fold_wgrad", _p(dwe), _p(dbe), Co, Ci, _p(gv), _p(bgrad_out), _stream())
     return True
 
@@ -778,14 +787,12 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
         assert x16.shape == x.shape and x16.dtype == torch.bfloat16 and x16.is_contiguous()
         xf = XF_NONE
     gv = ohwi(wgrad_out)
-    Co, kh, kw, Ci = gv.shape
-    taps = kh * kw
+    Co, _, _, Ci = gv.shape
     B, H, W, Cs = x.shape
-    g = _fwd_geom(kind, B, H, W, Cs)
-    assert dy.shape == (B, g.Ho, g.Wo, Co), (dy.shape, (B, g.Ho, g.Wo, Co))
+    assert dy.shape == (B, *out_hw(kind, H, W), Co), (dy.shape, kind, x.shape, Co)
     if (kind == "c3up" and PRECISION == PREC_F32 and WINOGRAD and xf == XF_NONE and x16 is None and dy32 is not None
             and x.dtype == torch.float32):
-        a = _wgrad_args(g, Co, Ci)  # the 9-position scheme of csrc/wgrad3_upwino.hip (fp32)
+        a = wgrad_args(kind, B, H, W, Cs, Co, Ci)  # the 9-position scheme of csrc/wgrad3_upwino.hip (fp32)
         a.dY, a.X = _p(dy32), _p(x)
         if _wgrad_wino(a, gv, bgrad_out, x.device):
             return
@@ -793,7 +800,7 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
         return
     xb = x.dtype == torch.bfloat16
     use16 = dy16 is not None and (dy32 is None or grad_image_ok(kind, x.shape, Co, Ci))
-    a = _wgrad_args(g, Co, Ci, xf=xf)
+    a = wgrad_args(kind, B, H, W, Cs, Co, Ci, xf=xf)
     a.dY, a.X = _p(dy32 if dy32 is not None else dy16), _p(x)
     a.dY16 = _p(dy16) if use16 else None
     if x16 is not None:
@@ -823,14 +830,14 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, kind: str, wgrad_out: torch.Te
     if ns == 1:
         a.out = _p(gv)
     else:
-        partial = torch.empty((ns, Co * taps * Ci), device=x.device, dtype=torch.float32)
+        partial = torch.empty((ns, gv.numel()), device=x.device, dtype=torch.float32)
         a.partial = _p(partial)
     bpart = None
     if bgrad_out is not None:  # bias gradient = column sums of dY, folded into the wgrad kernel
         bpart = torch.empty((ns, Co), device=x.device, dtype=torch.float32)
         a.bias_partial = _p(bpart)
     _launch_wgrad(a)
-    _reduce_splits(partial, bpart, ns, Co * taps * Ci, Co, gv, bgrad_out)
+    _reduce_splits(partial, bpart, ns, gv.numel(), Co, gv, bgrad_out)
 
 
 # ------------------------------------------------------------------ GroupNorm
@@ -971,31 +978,23 @@ def gn_bwd(x: torch.Tensor, g: torch.Tensor, st: Stats, gamma: torch.Tensor, bet
 
 
 # ------------------------------------------------------------------ batched GEMMs (attention)
-def _gemm_rows(A, Bm, out, M, N, K, bkm: bool, alpha, z, sAb, sWb, sCb):
-    """out[z] = alpha * A[z] @ Bm[z]^T (Bm [z,N,K]), or A[z] @ Bm[z] (bkm: Bm [z,K,N]): a one-tap convolution over M pixels in a
-    row, forward or dgrad form.  (PRECISION applies: in bf16 mode scores / context / their gradients run on the bf16 MFMA too)"""
-    a = _rows_args(ConvGeom(1, 1, M, K, 1, M, 1, 1, 0, 0, MODE_FWD), K if bkm else N, N if bkm else K, 1, bkm, alpha=alpha, st=0, z=z,
-                   zstrides=(sAb, sWb, sCb))
+def _gemm_rows(A: torch.Tensor, Bm: torch.Tensor, N: int, bkm: bool, alpha: float) -> torch.Tensor:
+    z, M, K = A.shape
+    out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
+    a = gemm_rows_args(M, N, K, bkm, alpha, z)
     a.A, a.W, a.C = _p(A), _p(Bm), _p(out)
     _launch_igemm(a)
+    return out
 
 
 def gemm_nt(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
     """out[z] = alpha * A[z] @ Bm[z]^T ; A [z,M,K], Bm [z,N,K]."""
-    z, M, K = A.shape
-    N = Bm.shape[1]
-    out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    _gemm_rows(A, Bm, out, M, N, K, False, alpha, z, M * K, N * K, M * N)
-    return out
+    return _gemm_rows(A, Bm, Bm.shape[1], False, alpha)
 
 
 def gemm_nn(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
     """out[z] = alpha * A[z] @ Bm[z] ; A [z,M,K], Bm [z,K,N]."""
-    z, M, K = A.shape
-    N = Bm.shape[2]
-    out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    _gemm_rows(A, Bm, out, M, N, K, True, alpha, z, M * K, K * N, M * N)
-    return out
+    return _gemm_rows(A, Bm, Bm.shape[2], True, alpha)
 
 
 def gemm_tn(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
@@ -1003,7 +1002,7 @@ def gemm_tn(A: torch.Tensor, Bm: torch.Tensor, alpha: float = 1.0) -> torch.Tens
     z, K, M = A.shape
     N = Bm.shape[2]
     out = torch.empty((z, M, N), device=A.device, dtype=torch.float32)
-    a = _wgrad_args(ConvGeom(1, 1, K, N, 1, K, 1, 1, 0, 0, MODE_FWD), M, N, alpha=alpha, z=z, zstrides=(K * M, K * N, M * N))
+    a = gemm_tn_args(M, N, K, alpha, z)
     a.dY, a.X, a.out = _p(A), _p(Bm), _p(out)
     _launch_wgrad(a)
     return out
