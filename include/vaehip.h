@@ -279,6 +279,24 @@ int vae_moments_partial(const void* x, int32_t x_bf16, const float* scale, const
  * all B*HW*C elements, their unbiased (N - 1) std                                   */
 int vae_moments_final(const float* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* chan, float* out,
                       void* stream);
+/* ---- image-quality metrics of a reconstruction (evaluate.py: Average MSE, PSNR, SSIM; reference src/evaluate.py:172-183,
+ * torchmetrics PeakSignalNoiseRatio / StructuralSimilarityIndexMeasure), csrc/image_metrics.hip ----
+ * pred, target: fp32 images of logical shape (B, C, H, W), values nominally in [-1, 1], each with its own four ELEMENT strides
+ * (batch, channel, row, column): contiguous NCHW, a channels-last view and a batch slice are all read in place; base pointers
+ * need 4-byte alignment only; every offset is formed in 64 bits.  u(x) = clamp((x + 1) / 2, 0, 1) in fp32.
+ * Per image three float64 values, out [B][3]:
+ *   [0] sum over C*H*W of (pred - target)^2 of the values as given          (Average MSE = sum / (C*H*W), averaged over images)
+ *   [1] sum over C*H*W of (u(pred) - u(target))^2                           (PSNR = 10 log10(1 / (sum of [1] / sum of C*H*W)))
+ *   [2] mean SSIM index of u(pred) against u(target) over the C*(H-10)*(W-10) positions whose 11 x 11 gaussian window (sigma 1.5,
+ *       c1 = 0.01^2, c2 = 0.03^2, data range 1) lies inside the image: what torchmetrics keeps after its border crop
+ * Window statistics and all sums are float64.  H < 11 or W < 11 is VAE_EINVAL (nothing is launched).
+ * vae_image_metrics_workspace: *ndoubles = size of ws for this shape (exactly what the partial pass writes); needs no GPU.
+ * partial: ws = per-workgroup sums; final: ws -> out, fixed order.  No atomics: repeated launches are bitwise identical. */
+int vae_image_metrics_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int64_t* ndoubles);
+int vae_image_metrics_partial(const float* pred, int64_t psb, int64_t psc, int64_t psh, int64_t psw, const float* target,
+                              int64_t tsb, int64_t tsc, int64_t tsh, int64_t tsw, int32_t B, int32_t C, int32_t H, int32_t W,
+                              double* ws, void* stream);
+int vae_image_metrics_final(const double* ws, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* stream);
 /* GroupNorm(+SiLU) backward.  g = dL/d(XF(gn(x))): fp32, or bf16 when g_bf16 != 0 (bf16 mode stores the dgrad outputs of
  * the halo-tile kernels as bf16, vae_igemm_args.out_bf16).
  * stage 1: ws [B][nchunk][C][2] partial sums of du and du*xhat                     */

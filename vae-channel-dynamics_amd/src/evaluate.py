@@ -2,9 +2,12 @@
 `<checkpoint_path>/vae`, deterministic reconstruction (latent mode), Average MSE / KL / PSNR / SSIM,
 sample PNGs and `eval_metrics.txt` in the reference's format.
 
-The forward runs on the HIP engine.  PSNR (data_range 1.0 on [0,1]-clamped images) and SSIM (11x11
-gaussian, sigma 1.5) are computed here directly (the reference needs torchmetrics); they are
-evaluation-only torch ops, not part of the train-step hot path.  Logit-lens visualisation is out of
+The forward runs on the HIP engine, and so do the metrics: MSE, PSNR (data_range 1.0 on [0,1]-clamped
+images) and SSIM (11x11 gaussian, sigma 1.5; the reference needs torchmetrics) come from one fused device
+kernel per batch (vaehip.ops.image_metrics, accumulated by vaehip.metrics.ImageMetrics), read straight from
+the engine's channels-last reconstruction; KL is summed on the device too, so the loop synchronises the host
+only to save the sample PNGs.  `to_unit`, `psnr_sums` and `ssim_per_image` below are the CPU definition the
+kernel is held to (tests/test_eval_metrics.py, tests/test_image_metrics_gpu.py).  Logit-lens visualisation is out of
 scope; `--enable_logit_lens` is accepted and captures the requested layers' activations through the
 hook protocol (as evaluate.py:207-211 does) so downstream tooling can use them.
 """
@@ -21,6 +24,7 @@ from utils.config_utils import load_config
 from utils.logging_utils import setup_logging
 from data_utils import load_and_preprocess_dataset, create_dataloader
 from models.sdxl_vae_wrapper import SDXLVAEWrapper
+from vaehip.metrics import ImageMetrics
 
 setup_logging()
 logger = logging.getLogger(__name__)
@@ -107,11 +111,9 @@ def main():
         max_samples=data_cfg.get("validation_max_samples", None), split=args.eval_split)
     dl = create_dataloader(ds, batch_size=bs, num_workers=data_cfg.get("num_workers", 0), shuffle=False)
 
-    total_mse = total_kl = 0.0
+    metrics = ImageMetrics()
+    kl_sum = torch.zeros((), dtype=torch.float64, device=device)
     n = saved = 0
-    sse = torch.zeros((), dtype=torch.float64, device=device)
-    sse_count = 0
-    ssim_sum = torch.zeros((), dtype=torch.float64, device=device)
     with torch.no_grad():
         for step, batch in enumerate(dl):
             if step == 0 and args.enable_logit_lens:
@@ -124,14 +126,9 @@ def main():
             rec = out["reconstruction"]
             kl = out["latent_dist"].kl()
             b = pv.shape[0]
-            total_mse += F.mse_loss(rec.float(), pv.float(), reduction="mean").item() * b
-            total_kl += kl.mean().item() * b
+            metrics.update(rec.float(), pv)
+            kl_sum += kl.double().sum()
             n += b
-            r01, o01 = to_unit(rec).contiguous(), to_unit(pv)
-            s, c = psnr_sums(r01, o01)
-            sse += s
-            sse_count += c
-            ssim_sum += ssim_per_image(r01, o01).double().sum()
             while saved < args.num_samples_to_save and saved - (n - b) < b:
                 i = saved - (n - b)
                 save_png(pv[i], os.path.join(args.output_dir, f"sample_{saved}_orig.png"))
@@ -141,10 +138,9 @@ def main():
                 acts = w.get_captured_activations()
                 torch.save({k: v for k, v in acts.items()}, os.path.join(args.output_dir, "first_batch_activations.pt"))
                 w.remove_hooks()
-    avg_mse = total_mse / n if n else 0
-    avg_kl = total_kl / n if n else 0
-    psnr = float(10.0 * torch.log10(1.0 / (sse / max(sse_count, 1)))) if n else float("nan")
-    ssim = float(ssim_sum / n) if n else float("nan")
+    m = metrics.compute()
+    avg_mse, psnr, ssim = m["avg_mse"], m["psnr"], m["ssim"]
+    avg_kl = float(kl_sum) / n if n else 0
     logger.info("***** Evaluation Results *****")
     logger.info(f"  Dataset split: {args.eval_split}; samples: {n}")
     logger.info(f"  Average MSE Loss: {avg_mse:.6f}  Average KL Divergence: {avg_kl:.6f}  PSNR: {psnr:.4f} dB  SSIM: {ssim:.4f}")

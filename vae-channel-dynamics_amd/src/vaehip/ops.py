@@ -922,6 +922,29 @@ def moments(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE) -
     return out
 
 
+def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """per-image quality metrics of `pred` against `target` (evaluate.py's Average MSE / PSNR / SSIM) in one read of both: a
+    float64 device tensor [B, 3] = [sum (pred - target)^2, sum (u(pred) - u(target))^2 with u(x) = clamp((x + 1) / 2, 0, 1),
+    mean SSIM of u(pred) against u(target) (11 x 11 gaussian, sigma 1.5, border-cropped)].  Both are fp32 (B, C, H, W) tensors
+    with any strides (NCHW, a channels-last view, a batch slice: read in place, no copy); nothing synchronises the host."""
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"image_metrics: expected two (B, C, H, W) tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"image_metrics: expected float32 tensors, got {pred.dtype} and {target.dtype}")
+    if not (pred.is_cuda and target.is_cuda and pred.device == target.device):
+        raise ValueError(f"image_metrics: expected two tensors on one GPU, got {pred.device} and {target.device}")
+    B, Cc, H, W = pred.shape
+    if B < 1 or Cc < 1 or H < 11 or W < 11:
+        raise ValueError(f"image_metrics: {tuple(pred.shape)}: needs B >= 1, C >= 1 and images of at least 11 x 11 (the SSIM window)")
+    n = C.c_int64(0)
+    lib.call("vae_image_metrics_workspace", B, Cc, H, W, C.byref(n))
+    ws = torch.empty((n.value,), device=pred.device, dtype=torch.float64)
+    out = torch.empty((B, 3), device=pred.device, dtype=torch.float64)
+    lib.call("vae_image_metrics_partial", _p(pred), *pred.stride(), _p(target), *target.stride(), B, Cc, H, W, _p(ws), _stream())
+    lib.call("vae_image_metrics_final", _p(ws), B, Cc, H, W, _p(out), _stream())
+    return out
+
+
 def map_snapshot(t: torch.Tensor) -> torch.Tensor:
     """fp32 NHWC device copy of an activation (full_activation_map): bf16 storage widened by vae_unpack_bf16"""
     if t.dtype == torch.bfloat16:
