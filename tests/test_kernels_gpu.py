@@ -399,7 +399,7 @@ def test_bf16_conv_fused_gn_silu(cuda, bf16_mode, packed_weights, B, C, H, W, Co
     assert _rel(_nchw(y), y_ref) < 5e-4
 
 
-# shapes the bf16 FLAT kernels serve (igemm_bf16.hip): 1x1, stride 2 (gather dgrad and parity-class dgrad), ragged and
+# shapes the bf16 FLAT kernels serve (igemm.hip, bf16 policy): 1x1, stride 2 (gather dgrad and parity-class dgrad), ragged and
 # tiny 3x3, skinny N / skinny M, K tails that are not a multiple of the 64-channel step
 BF16_FLAT_CASES = [
     ("c1", 2, 8, 8, 128, 256), ("c1", 2, 4, 4, 8, 8), ("c1", 1, 6, 10, 320, 96),

@@ -1,6 +1,6 @@
 // 1x1 convolutions (the resnet shortcuts) and their dgrads in bf16 mode as a STREAMING GEMM with the weights resident in LDS:
 //     out[m][n] = sum_k A[m][k] * W(n, k) (+ bias[n])        A, out: bf16 tensors [M][K], [M][N]; W: the bf16 image of the weights
-// M = B*H*W runs to 2M rows while K, N are 128 .. 512: 0.3 ms of HBM traffic per launch.  The flat kernel (igemm_bf16.hip) cuts
+// M = B*H*W runs to 2M rows while K, N are 128 .. 512: 0.3 ms of HBM traffic per launch.  The flat kernel (igemm.hip, bf16 policy) cuts
 // such a product into 128 x 128 tiles of 2 .. 8 k-steps: workgroups that live for two memory round trips, 0.5 - 0.7 ms
 // (190 - 330 TFLOP/s).  Here
 //   * a workgroup (4 waves) keeps a 128-column slice of W in LDS for its whole life (k-contiguous rows for the forward, [k][n]

@@ -1,66 +1,255 @@
-// Implicit-GEMM convolution / GEMM family on the fp32-input MFMA
-// (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate).
+// Flat implicit-GEMM convolution / GEMM family: the kernels behind every geometry no specialised kernel serves (stride-2
+// convolutions and their parity-class dgrad, 1x1, tiny and ragged maps, attention linears and batched GEMMs, skinny layers).
 //
 // Three operand forms cover every contraction of the SDXL-VAE train step:
-//   rows   (A rows = pixels gathered through the conv geometry)
-//     - weight tile k-contiguous : conv/linear forward, Q.K^T, dO.V^T
-//     - weight tile n-contiguous : conv/linear dgrad, P.V, dS.K
-//   wgrad  (contraction over pixels; both tiles k-major) : conv/linear wgrad, P^T.dO, dS^T.Q
+//   rows   (A rows = pixels gathered through the conv geometry; A tile [BM rows][BK k], k-contiguous)
+//     - weight tile k-contiguous ([BN][BK])              : conv/linear forward, Q.K^T, dO.V^T
+//     - weight tile n-contiguous ([BK][BN], BKM = true)  : conv/linear dgrad, P.V, dS.K
+//   wgrad  (contraction over pixels; both tiles pixel-major, [BK px][BM] and [BK px][BN]) : conv/linear wgrad, P^T.dO, dS^T.Q
 //
-// Tiling: 64*WM*WN threads (8 waves for the 128x128 tile, 4 for the skinny ones), BK = 32, wave tile =
-// (BM/WM) x (BN/WN) built from 32x32 MFMA tiles.  LDS tiles are padded so every ds_read_b128 fragment read is
-// bank-conflict free (row stride 36 dwords: 36*i mod 64 hits 16 distinct 16-B slots
-// for the 16 rows of a b128 lane group).  Global loads of step s+1 are issued before
-// the MFMA block of step s and written to LDS after it (register-staged prefetch);
-// GroupNorm+SiLU is applied to the A operand in that write pass, so the normalised
-// activation never exists in HBM.
-#include "common.h"
+// There is ONE rows body and ONE wgrad body.  Each is instantiated under two arithmetic policies:
+//   F32  (VAE_PREC_F32) : exact fp32 products, fp32 accumulate, on v_mfma_f32_32x32x2_f32.  Serves any shape: the
+//         unvectorised instantiations (VEC = false) load element by element.
+//   BF16 (VAE_PREC_BF16): operands rounded to bf16 while staged in LDS, products on v_mfma_f32_32x32x16_bf16, fp32 accumulate.
+//         Every activation operand is stored as fp32 or as bf16, per tensor (a_bf16 / out_bf16 / res_bf16, x_bf16 / y_bf16:
+//         wave-uniform switches on the load / store instructions; the weights W are always the fp32 master copy).  Only the
+//         vectorised shapes (16-B aligned, channel counts % 4 == 0) exist; the rest stays on the F32 kernels.
+// A policy holds what really differs (LDS element, K step, paddings, staging conversion, fragment reads, the MFMA block, the
+// epilogue's element access); the bodies ask it for a type, a constant or a small function and never which policy it is.
+//
+// Tiling: 64*WM*WN threads (8 waves for the 128x128 tile, 4 for the skinny ones), wave tile = (BM/WM) x (BN/WN) built from
+// 32x32 MFMA tiles.  Global loads of step s+2 are issued, and the registers of step s+1 written to the other LDS stage, in
+// the middle of step s's MFMA block (register-staged prefetch); GroupNorm+SiLU is applied to the activation operand in that
+// write pass, so the normalised activation never exists in HBM.
+#include "bf16_frag.h"
 #include <algorithm>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "launchers.h"
 
 namespace {
 
-constexpr int BK = 32;
-__device__ __forceinline__ int b_lo_of(int m0, int hw) { return m0 / hw; }
+// ---------------------------------------------------------------------------------------
+// arithmetic policies
+// ---------------------------------------------------------------------------------------
+// a lane's coordinates in the fragment reads.  lr / lh: row (or column) and k half of the MFMA operand layout;
+// trq / trp / trh: row, column quad and column half this lane addresses in a 16-lane group's transposing read (bf16_frag.h)
+struct LanePos {
+  int lr, lh, trq, trp, trh;
+};
+__device__ __forceinline__ LanePos lane_pos(int lane) { return LanePos{lane & 31, lane >> 5, (lane & 15) >> 2, lane & 3, (lane >> 4) & 1}; }
+
+struct F32 {
+  typedef float elem;    // LDS element
+  typedef f32x4 raw4;    // what a 16-byte operand load lands in
+  typedef f32x4 frag;    // this lane half's 4 consecutive k of a k-group: element j feeds MFMA j (k = 2, one per lane half)
+  typedef unsigned off_t;  // epilogue element handle: byte offset, BUF_OOB = outside the matrix
+  static constexpr int BK_ROWS = 32, BK_WGRAD = 32;  // K step (channels / pixels)
+  static constexpr int KG = 8;                       // k per k-group
+  // LDS row paddings (elements).  Row stride 36 dwords: 36*i mod 64 hits 16 distinct 16-B slots for the 16 rows of a b128
+  // lane group, so every ds_read_b128 fragment read is bank-conflict free; the transposing (dword) reads of the [k][col]
+  // tiles take the same 4.
+  static constexpr int PAD_K = 4, PAD_T = 4;
+  static constexpr bool SETPRIO = true;  // s_setprio brackets the MFMA block
+  static constexpr bool PAIR16 = false;
+  static constexpr bool flag(int32_t) { return false; }  // operands and results are fp32: no storage switch exists
+
+  static __device__ __forceinline__ raw4 load4(__amdgpu_buffer_rsrc_t rs, unsigned, bool ok, int row, int ld, int c) {
+    return VAE_BUF_LOAD4(rs, oob_unless(ok, ((unsigned)row * (unsigned)ld + (unsigned)c) * 4u));
+  }
+  static __device__ __forceinline__ f32x4 to_f32(raw4 r, bool) { return r; }
+  static __device__ __forceinline__ void put4(elem* d, f32x4 v) { *reinterpret_cast<f32x4*>(d) = v; }
+  static __device__ __forceinline__ void put4_stored(elem* d, raw4, f32x4 v, bool) { put4(d, v); }
+  // 4 consecutive k at p (one ds_read_b128)
+  static __device__ __forceinline__ frag frag_k(const elem* p) { return *reinterpret_cast<const f32x4*>(p); }
+  // the same 4 k of k-group kg from a [k][col] tile: this lane's column of the 32 from col0
+  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0) {
+    frag v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = tile[(kg * 8 + l.lh * 4 + j) * ld + col0 + l.lr];
+    return v;
+  }
+  // both operands from [k][col] tiles (wgrad), MI / NI fragments from columns colA / colB on.  The a and b reads alternate
+  // per k row: the compiler's pairing of the dword reads, and with it the register count, follows the source order.
+  template <int MI, int NI>
+  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = kg * 8 + l.lh * 4 + j;
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) a[mi][j] = sA[k * ldA + colA + mi * 32 + l.lr];
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) b[ni][j] = sB[k * ldB + colB + ni * 32 + l.lr];
+    }
+  }
+  template <int MI, int NI>
+  static __device__ __forceinline__ void mma(f32x16 (&acc)[MI][NI], const frag* a, const frag* b) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi][j], b[ni][j], acc[mi][ni], 0, 0, 0);
+  }
+  static __device__ __forceinline__ off_t out_off(bool ok, int orow, int ldc, int col) {
+    return ok ? ((unsigned)orow * (unsigned)ldc + (unsigned)col) * 4u : BUF_OOB;
+  }
+  static __device__ __forceinline__ bool inside(off_t o) { return o != BUF_OOB; }
+  static __device__ __forceinline__ float load1(__amdgpu_buffer_rsrc_t rs, bool, off_t o) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
+  }
+  static __device__ __forceinline__ void store1(__amdgpu_buffer_rsrc_t rs, bool, off_t o, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, o, 0, 0);
+  }
+};
+
+struct BF16 {
+  typedef u16 elem;
+  typedef uint4 raw4;    // as loaded (fp32 quad, or 4 bf16 in the low half): converted at the LDS write
+  typedef bf16x8 frag;   // 8 k per lane half: one MFMA of k = 16 per k-group
+  typedef int off_t;     // epilogue element handle: element offset (C and res may differ in storage), -1 = outside the matrix
+  static constexpr int BK_ROWS = 64, BK_WGRAD = 32;
+  static constexpr int KG = 16;
+  // k-contiguous rows: 144 B row stride, conflict-free ds_read_b128.  [k][col] rows: 64 B mod 256 B row strides put the four
+  // rows of a transposing read's block in different bank ranges (bf16_frag.h).
+  static constexpr int PAD_K = 8, PAD_T = 32;
+  static constexpr bool SETPRIO = false;
+  static constexpr bool PAIR16 = true;  // the rows epilogue has the paired 4-byte bf16 store
+  static __device__ __forceinline__ bool flag(int32_t v) { return v != 0; }  // storage of an operand / result (uniform)
+
+  static __device__ __forceinline__ raw4 load4(__amdgpu_buffer_rsrc_t rs, unsigned esize, bool ok, int row, int ld, int c) {
+    return buf_load4_raw(rs, esize, neg_unless(ok, row * ld + c));
+  }
+  static __device__ __forceinline__ f32x4 to_f32(raw4 r, bool bf) { return raw4_to_f32(r, bf); }
+  static __device__ __forceinline__ void put4(elem* d, f32x4 v) { *reinterpret_cast<uint2*>(d) = pack4(v); }
+  // an operand that is staged untransformed and already stored as bf16 goes to LDS as loaded
+  static __device__ __forceinline__ void put4_stored(elem* d, raw4 r, f32x4 v, bool bf) {
+    *reinterpret_cast<uint2*>(d) = bf ? uint2{r.x, r.y} : pack4(v);
+  }
+  static __device__ __forceinline__ frag frag_k(const elem* p) { return frag_direct(p); }
+  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0) {
+    return frag_tr(tile + (kg * 16 + l.lh * 8 + l.trq) * ld + col0 + l.trh * 16 + l.trp * 4, ld);
+  }
+  template <int MI, int NI>
+  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) a[mi] = frag_t(sA, ldA, kg, l, colA + mi * 32);
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) b[ni] = frag_t(sB, ldB, kg, l, colB + ni * 32);
+  }
+  template <int MI, int NI>
+  static __device__ __forceinline__ void mma(f32x16 (&acc)[MI][NI], const frag* a, const frag* b) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+  }
+  static __device__ __forceinline__ off_t out_off(bool ok, int orow, int ldc, int col) { return ok ? orow * ldc + col : -1; }
+  static __device__ __forceinline__ bool inside(off_t o) { return o >= 0; }
+  static __device__ __forceinline__ float load1(__amdgpu_buffer_rsrc_t rs, bool bf, off_t o) { return buf_load1_elem(rs, bf, o); }
+  static __device__ __forceinline__ void store1(__amdgpu_buffer_rsrc_t rs, bool bf, off_t o, float v) { buf_store1_elem(rs, bf, o, v); }
+
+  // bf16 output with an even column count (and a bf16 residual or none): adjacent lanes hold adjacent columns of the same 16
+  // rows; they swap every other register, so a lane stores BOTH columns of its pair for 8 rows -- 4-byte stores and 4-byte
+  // residual loads instead of 2-byte ones (the 2-byte form cost the flat kernels 20 % when bf16 storage came in)
+  static __device__ __forceinline__ bool pair16(const vae_igemm_args& p, bool cbf, bool rbf, const char* C) {
+    return cbf && (p.N % 2 == 0) && (p.ldc % 2 == 0) && (p.res == nullptr || rbf) && p.track == nullptr && ((reinterpret_cast<uintptr_t>(C) & 3u) == 0);
+  }
+  // one 32-column block of a wave tile whose rows start at trow0 (lane half lh); row_pixel: the stride-2 dgrad's (s2c) row mapping
+  template <int MI, int NI, class RowPixel>
+  static __device__ __forceinline__ void store_pairs(const vae_igemm_args& p, const f32x16 (&acc)[MI][NI], int ni, __amdgpu_buffer_rsrc_t rsC,
+                                                     __amdgpu_buffer_rsrc_t rsR, int col, bool colok, int m0, int trow0, int lh, bool s2c,
+                                                     RowPixel row_pixel) {
+    const bool odd = col & 1;
+    const float b0 = (p.bias && colok) ? p.bias[col & ~1] : 0.f, b1 = (p.bias && colok) ? p.bias[col | 1] : 0.f;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      unsigned o16[8], rr[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int r = 2 * j + (odd ? 1 : 0);
+        const int row = trow0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        int orow = row;
+        if (s2c) {
+          int b, y, x;
+          row_pixel(row < p.M ? row : m0, b, y, x);
+          orow = (b * p.g.Ho + y) * p.g.Wo + x;
+        }
+        o16[j] = (colok && row < p.M) ? (unsigned)(orow * p.ldc + (col & ~1)) * 2u : BUF_OOB;
+        rr[j] = 0u;
+      }
+      if (p.res) {  // uniform
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rr[j] = __builtin_amdgcn_raw_buffer_load_b32(rsR, o16[j], 0, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float a0 = p.alpha * acc[mi][ni][2 * j], a1 = p.alpha * acc[mi][ni][2 * j + 1];
+        const float recv = lane_xor1(odd ? a0 : a1);
+        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+        bf16x2_t h;
+        h[0] = (__bf16)((odd ? recv : a0) + b0 + __builtin_bit_cast(float, rr[j] << 16));
+        h[1] = (__bf16)((odd ? a1 : recv) + b1 + __builtin_bit_cast(float, rr[j] & 0xffff0000u));
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h), rsC, o16[j], 0, 0);
+      }
+    }
+  }
+};
+
+template <int MI, int NI>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NI]) {
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+}
 
 // ---------------------------------------------------------------------------------------
-// rows kernel.  Pipeline: LDS is double buffered; the global loads of K-step s+2 are issued and
-// the registers of step s+1 are transformed + written to the other LDS stage in the MIDDLE of
-// step s's MFMA block, so one workgroup barrier per K-step suffices and the VALU/LDS-write work
-// sits in the shadow of MFMAs already issued.  The GroupNorm scale/shift rows the tile needs are
-// staged in LDS once per workgroup (they used to be 8 dependent global loads per thread per step).
+// rows body.  Pipeline: LDS is double buffered; the global loads of K-step s+2 are issued and the registers of step s+1 are
+// transformed + written to the other LDS stage in the MIDDLE of step s's MFMA block, so one workgroup barrier per K-step
+// suffices and the VALU/LDS-write work sits in the shadow of MFMAs already issued.  A step is NKG = 2 or 4 k-groups.  The
+// GroupNorm scale/shift rows the tile needs are staged in LDS once per workgroup (they used to be 8 dependent global loads
+// per thread per step).
+// (The pipeline driver -- compute and the step loop -- is written out in both bodies: behind a shared function hipcc's
+// register allocation moved by 2..5 VGPRs in most instantiations and one bf16 rows kernel lost a wave of occupancy.)
 // ---------------------------------------------------------------------------------------
-
-template <int BM, int BN, int WM, int WN, bool BKM, bool VEC, int XF>
-__global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args p) {
+template <class P, int BM, int BN, int WM, int WN, bool BKM, bool VEC, int XF>
+__device__ __forceinline__ void rows_body(const vae_igemm_args& p) {
+  typedef typename P::elem elem;
+  constexpr int BK = P::BK_ROWS;
   constexpr int NT = 64 * WM * WN;  // 4 waves (skinny tiles) or 8 waves (128x128: 4 waves/SIMD at 2 workgroups/CU)
-  constexpr int NL = NT;
-  constexpr int RP = NT / 8;        // tile rows covered by one pass of the float4 loaders
-  constexpr int LDA = BK + 4;
-  constexpr int LDB = BKM ? (BN + 4) : (BK + 4);
+  constexpr int KQ = BK / 4;        // float4 per k-contiguous tile row
+  constexpr int RP = NT / KQ;       // tile rows covered by one pass of the float4 loaders
+  constexpr int LDA = BK + P::PAD_K;
+  constexpr int LDB = BKM ? (BN + P::PAD_T) : (BK + P::PAD_K);
   constexpr int SA = BM * LDA;
   constexpr int SB = BKM ? BK * LDB : BN * LDB;
-  constexpr int STAGE = SA + SB;
-  constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF : 0;
+  constexpr int STAGE = SA + SB;  // elements
+  constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(elem)) : 0;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
-  constexpr int AR = BM / RP;                       // A rows per thread
-  constexpr int BR = BKM ? (BK / (NL / (BN / 4))) : (BN / RP);
-  static_assert(AR >= 1 && BR >= 1 && TM % 32 == 0 && TN % 32 == 0, "tile/wave layout");
-  __shared__ __attribute__((aligned(16))) float smem[2 * STAGE + SS];
-  float* sS = smem + 2 * STAGE;
+  constexpr int AR = BM / RP;  // A rows per thread
+  constexpr int NQ = BN / 4, KR = NT / NQ;  // n-contiguous weight tile: NQ float4 per k row, KR k rows per pass
+  constexpr int BR = BKM ? (BK / KR) : (BN / RP);
+  static_assert(AR >= 1 && BR >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
+  __shared__ __attribute__((aligned(16))) elem smem[2 * STAGE + SS];
+  float* sS = reinterpret_cast<float*>(smem + 2 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lt = tid;
   const int wm = wave / WN, wn = wave % WN;
+  const LanePos lp = lane_pos(lane);
+  const int lr = lp.lr, lh = lp.lh;
   const int tilesN = (p.N + BN - 1) / BN;
   const int tm = blockIdx.x / tilesN, tn = blockIdx.x % tilesN;
   const int m0 = tm * BM, n0 = tn * BN;
   const int z = blockIdx.z;
   const vae_conv_geom g = p.g;
   const SrcMap smap = make_srcmap(g);
-  const float* __restrict__ A = p.A + (int64_t)z * p.sAb;
+  const bool abf = P::flag(p.a_bf16), cbf = P::flag(p.out_bf16), rbf = P::flag(p.res_bf16);  // storage of A / C / res
+  const unsigned esA = abf ? 2u : 4u;
+  const char* __restrict__ A = reinterpret_cast<const char*>(p.A) + (int64_t)z * p.sAb * esA;
   const float* __restrict__ W = p.W + (int64_t)z * p.sWb;
   const int hw = g.Ho * g.Wo;
 
@@ -91,18 +280,19 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args
   // vectorised instantiations read both operands through buffer descriptors (common.h): out-of-range offsets read
   // zeros, so no select sits on a loaded value.  The activation descriptor starts at the first image this tile's
   // rows touch (the host checked that the images one tile can span fit 32-bit offsets).
-  const int b_base = s2c ? (m0 - cls * cls_rows) / (hh * wh) : b_lo_of(m0, hw);
+  const int b_base = s2c ? (m0 - cls * cls_rows) / (hh * wh) : m0 / hw;
   const size_t img = (size_t)g.Hs * g.Ws * g.Cs;
-  const size_t abytes = (size_t)(g.B - b_base) * img * 4u, wbytes = (size_t)(BKM ? (int64_t)p.K * p.sk : (int64_t)p.N * p.sn) * 4u;
-  const auto rsA = VAE_BUF_RSRC(A + (int64_t)b_base * img, abytes < BUF_MAX ? abytes : BUF_MAX);
+  const size_t abytes = (size_t)(g.B - b_base) * img * esA, wbytes = (size_t)(BKM ? (int64_t)p.K * p.sk : (int64_t)p.N * p.sn) * 4u;
+  const auto rsA = VAE_BUF_RSRC(A + (int64_t)b_base * img * esA, abytes < BUF_MAX ? abytes : BUF_MAX);
   const auto rsW = VAE_BUF_RSRC(W, wbytes < BUF_MAX ? wbytes : BUF_MAX);
 
   // per-thread A rows
-  const int k4 = lt & 7, r0 = lt >> 3;
+  const int k4 = tid % KQ, r0 = tid / KQ;
+  const int n4 = tid % NQ, kq = tid / NQ;  // n-contiguous weight tile
   int rb[AR], ry[AR], rx[AR];
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
-    int m = m0 + r0 + RP * i;
+    const int m = m0 + r0 + RP * i;
     if (m < p.M) {
       row_pixel(m, rb[i], ry[i], rx[i]);
     } else {
@@ -124,17 +314,13 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args
   }
 
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  zero_acc(acc);
 
   const int kchunks = (p.K + BK - 1) / BK;
   const int steps = ntaps * kchunks;
 
-  f32x4 ra[AR], rbw[BR];
+  typename P::raw4 ra[AR];
+  f32x4 rw[BR];
   int a_b[AR];  // batch index of the loaded row (for scale/shift), -1 = padding
   int reg_c0 = 0;
 
@@ -157,157 +343,142 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args
     for (int i = 0; i < AR; ++i) {
       int sy = 0, sx = 0;
       const bool ok = src_pixel(smap, ry[i], rx[i], kh, kw, sy, sx) && (rb[i] >= 0);
-      if (VEC) {
-        ra[i] = VAE_BUF_LOAD4(rsA, oob_unless(ok && c < p.K, ((unsigned)(((rb[i] - b_base) * g.Hs + sy) * g.Ws + sx) * (unsigned)g.Cs + (unsigned)c) * 4u));
-      } else {
-        ra[i] = load4s(A + (((int64_t)rb[i] * g.Hs + sy) * g.Ws + sx) * g.Cs + c, ok, c, p.K);
-      }
+      if constexpr (VEC) ra[i] = P::load4(rsA, esA, ok && c < p.K, ((rb[i] - b_base) * g.Hs + sy) * g.Ws + sx, g.Cs, c);
+      else ra[i] = load4s(p.A + (int64_t)z * p.sAb + (((int64_t)rb[i] * g.Hs + sy) * g.Ws + sx) * g.Cs + c, ok, c, p.K);
       a_b[i] = ok ? rb[i] : -1;
     }
     if (!BKM) {
 #pragma unroll
       for (int i = 0; i < BR; ++i) {
         const int n = n0 + r0 + RP * i;
-        if (VEC) rbw[i] = VAE_BUF_LOAD4(rsW, oob_unless(n < p.N && c < p.K, ((unsigned)n * (unsigned)p.sn + (unsigned)tap * (unsigned)p.st + (unsigned)c) * 4u));
-        else rbw[i] = load4s(W + (int64_t)n * p.sn + (int64_t)tap * p.st + c, n < p.N, c, p.K);
+        if constexpr (VEC) rw[i] = VAE_BUF_LOAD4(rsW, oob_unless(n < p.N && c < p.K, ((unsigned)n * (unsigned)p.sn + (unsigned)tap * (unsigned)p.st + (unsigned)c) * 4u));
+        else rw[i] = load4s(W + (int64_t)n * p.sn + (int64_t)tap * p.st + c, n < p.N, c, p.K);
       }
     } else {
-      constexpr int NQ = BN / 4, KR = NL / NQ;
-      const int n4 = lt % NQ, kq = lt / NQ;
 #pragma unroll
       for (int i = 0; i < BR; ++i) {
         const int k = c0 + kq + KR * i;
         const int n = n0 + n4 * 4;
-        if (VEC) rbw[i] = VAE_BUF_LOAD4(rsW, oob_unless(k < p.K && n < p.N, ((unsigned)k * (unsigned)p.sk + (unsigned)tap * (unsigned)p.st + (unsigned)n) * 4u));
-        else rbw[i] = load4s(W + (int64_t)k * p.sk + (int64_t)tap * p.st + n, k < p.K, n, p.N);
+        if constexpr (VEC) rw[i] = VAE_BUF_LOAD4(rsW, oob_unless(k < p.K && n < p.N, ((unsigned)k * (unsigned)p.sk + (unsigned)tap * (unsigned)p.st + (unsigned)n) * 4u));
+        else rw[i] = load4s(W + (int64_t)k * p.sk + (int64_t)tap * p.st + n, k < p.K, n, p.N);
       }
     }
   };
-
-  auto store_lds = [&](float* sA, float* sB) {
+  auto store_lds = [&](elem* sA, elem* sB) {
     const int c = reg_c0 + k4 * 4;
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
-      f32x4 v = ra[i];
+      f32x4 v = P::to_f32(ra[i], abf);
       if (XF != VAE_XF_NONE) {
         const bool ok = (a_b[i] >= 0) && (c < p.K);
         const int o = ok ? (a_b[i] - b_lo) * p.K + c : 0;
         v = xform4_tab<XF>(v, sS + o, sS + SS_HALF + o, ok);
       }
-      *reinterpret_cast<f32x4*>(&sA[(r0 + RP * i) * LDA + k4 * 4]) = v;
+      P::put4(&sA[(r0 + RP * i) * LDA + k4 * 4], v);
     }
-    if (!BKM) {
 #pragma unroll
-      for (int i = 0; i < BR; ++i) *reinterpret_cast<f32x4*>(&sB[(r0 + RP * i) * LDB + k4 * 4]) = rbw[i];
-    } else {
-      constexpr int NQ = BN / 4, KR = NL / NQ;
-      const int n4 = lt % NQ, kq = lt / NQ;
-#pragma unroll
-      for (int i = 0; i < BR; ++i) *reinterpret_cast<f32x4*>(&sB[(kq + KR * i) * LDB + n4 * 4]) = rbw[i];
+    for (int i = 0; i < BR; ++i) {
+      if (!BKM) P::put4(&sB[(r0 + RP * i) * LDB + k4 * 4], rw[i]);
+      else P::put4(&sB[(kq + KR * i) * LDB + n4 * 4], rw[i]);
     }
   };
-
-  const int lr = lane & 31, lh = lane >> 5;
-  // fragments of k-group kk+1 are requested before the MFMAs of kk are issued (pinned with sched_barrier)
-  f32x4 fa[2][MI], fb[2][NI];
-  auto fetch = [&](const float* sA, const float* sB, int kk, f32x4* a, f32x4* b) {
+  // fragments of k-group kg+1 are requested before the MFMAs of kg are issued (pinned with sched_barrier)
+  typename P::frag fa[2][MI], fb[2][NI];
+  auto fetch = [&](const elem* sA, const elem* sB, int kg, typename P::frag* a, typename P::frag* b) {
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-      a[mi] = *reinterpret_cast<const f32x4*>(&sA[(wm * TM + mi * 32 + lr) * LDA + kk * 8 + lh * 4]);
+    for (int mi = 0; mi < MI; ++mi) a[mi] = P::frag_k(&sA[(wm * TM + mi * 32 + lr) * LDA + kg * P::KG + lh * (P::KG / 2)]);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      if (!BKM) {
-        b[ni] = *reinterpret_cast<const f32x4*>(&sB[(wn * TN + ni * 32 + lr) * LDB + kk * 8 + lh * 4]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[ni][j] = sB[(kk * 8 + lh * 4 + j) * LDB + wn * TN + ni * 32 + lr];
-      }
+      if (!BKM) b[ni] = P::frag_k(&sB[(wn * TN + ni * 32 + lr) * LDB + kg * P::KG + lh * (P::KG / 2)]);
+      else b[ni] = P::frag_t(sB, LDB, kg, lp, wn * TN + ni * 32);
     }
   };
-  auto compute = [&](const float* sA, const float* sB, int kk) {  // fragments of kk already requested
-    if (kk + 1 < BK / 8) fetch(sA, sB, kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1]);
+  constexpr int NKG = BK / P::KG;
+  auto compute = [&](const elem* sA, const elem* sB, int kg) {  // fragments of kg already requested
+    if (kg + 1 < NKG) fetch(sA, sB, kg + 1, fa[(kg + 1) & 1], fb[(kg + 1) & 1]);
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk & 1][mi][j], fb[kk & 1][ni][j], acc[mi][ni], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
+    if (P::SETPRIO) __builtin_amdgcn_s_setprio(1);
+    P::mma(acc, fa[kg & 1], fb[kg & 1]);
+    if (P::SETPRIO) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
-
   load_regs(0);
   __syncthreads();  // scale/shift table visible
   store_lds(smem, smem + SA);
   if (steps > 1) load_regs(1);
   __syncthreads();
   for (int s = 0; s < steps; ++s) {
-    const float* cA = smem + (s & 1) * STAGE;
-    const float* cB = cA + SA;
+    const elem* cA = smem + (s & 1) * STAGE;
+    const elem* cB = cA + SA;
     fetch(cA, cB, 0, fa[0], fb[0]);
     compute(cA, cB, 0);
-    compute(cA, cB, 1);
+    if (NKG == 4) compute(cA, cB, 1);
     if (s + 1 < steps) {  // staged in the shadow of the MFMAs already issued
-      float* nA = smem + ((s + 1) & 1) * STAGE;
+      elem* nA = smem + ((s + 1) & 1) * STAGE;
       store_lds(nA, nA + SA);
       if (s + 2 < steps) load_regs(s + 2);
     }
-    compute(cA, cB, 2);
-    compute(cA, cB, 3);
+    compute(cA, cB, NKG / 2);
+    if (NKG == 4) compute(cA, cB, 3);
     __syncthreads();
   }
 
   // ---------------- epilogue ----------------
   // outputs and the residual through buffer descriptors (common.h): a row / column outside the matrix is an
   // out-of-range offset (load reads 0, store is dropped): no branch per element, residual loads issued back to back
-  float* __restrict__ C = p.C + (int64_t)z * p.sCb;
-  const size_t obytes = (size_t)p.M * p.ldc * 4u;
-  const auto rsC = VAE_BUF_RSRC(C, obytes);
-  const auto rsR = VAE_BUF_RSRC(p.res ? p.res + (int64_t)z * p.sCb : C, obytes);
+  const unsigned esC = cbf ? 2u : 4u, esR = rbf ? 2u : 4u;
+  char* __restrict__ C = reinterpret_cast<char*>(p.C) + (int64_t)z * p.sCb * esC;
+  const auto rsC = VAE_BUF_RSRC(C, (size_t)p.M * p.ldc * esC);
+  const auto rsR = VAE_BUF_RSRC(p.res ? reinterpret_cast<const char*>(p.res) + (int64_t)z * p.sCb * esR : C, (size_t)p.M * p.ldc * (p.res ? esR : esC));
   float tsum[NI];
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) tsum[ni] = 0.f;
+  bool pair16 = false;
+  if constexpr (P::PAIR16) pair16 = P::pair16(p, cbf, rbf, C);
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int col = n0 + wn * TN + ni * 32 + lr;
     const bool colok = col < p.N;
     const float bv = (p.bias && colok) ? p.bias[col] : 0.f;
+    if constexpr (P::PAIR16) {
+      if (pair16) {  // uniform
+        P::store_pairs(p, acc, ni, rsC, rsR, col, colok, m0, m0 + wm * TM, lh, s2c, row_pixel);
+        continue;
+      }
+    }
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      unsigned off[16];
+      typename P::off_t off[16];
       float rv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * TM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        unsigned orow = (unsigned)row;
+        int orow = row;
         if (s2c) {  // class-major row -> pixel-major output row
           int b, y, x;
           row_pixel(row < p.M ? row : m0, b, y, x);
-          orow = (unsigned)((b * g.Ho + y) * g.Wo + x);
+          orow = (b * g.Ho + y) * g.Wo + x;
         }
-        off[r] = (colok && row < p.M) ? (orow * (unsigned)p.ldc + (unsigned)col) * 4u : BUF_OOB;
+        off[r] = P::out_off(colok && row < p.M, orow, p.ldc, col);
         rv[r] = 0.f;
       }
       if (p.res) {  // uniform
 #pragma unroll
-        for (int r = 0; r < 16; ++r) rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, off[r], 0, 0));
+        for (int r = 0; r < 16; ++r) rv[r] = P::load1(rsR, rbf, off[r]);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = p.alpha * acc[mi][ni][r] + bv + rv[r];
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, off[r], 0, 0);
-        tsum[ni] += (off[r] != BUF_OOB) ? fabsf(v) : 0.f;
+        P::store1(rsC, cbf, off[r], v);
+        tsum[ni] += P::inside(off[r]) ? fabsf(v) : 0.f;
       }
     }
   }
   if (p.track && z == 0) {
-    float* red = smem;  // [WM][BN]; the last loop barrier already separated it from the MFMA reads
+    float* red = reinterpret_cast<float*>(smem);  // [WM][BN]; the last loop barrier already separated it from the MFMA reads
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      float s2 = tsum[ni] + __shfl_xor(tsum[ni], 32, 64);
+      const float s2 = tsum[ni] + __shfl_xor(tsum[ni], 32, 64);
       if (lh == 0) red[wm * BN + wn * TN + ni * 32 + lr] = s2;
     }
     __syncthreads();
@@ -321,28 +492,30 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args
 }
 
 // ---------------------------------------------------------------------------------------
-// wgrad kernel: out[m][tap][n] = sum_pix dY[pix][m] * XF(X[src(pix,tap)][n])
-// Same double-buffered one-barrier pipeline.  The bias gradient (column sums of dY) is folded in:
+// wgrad body: out[m][tap][n] = sum_pix dY[pix][m] * XF(X[src(pix,tap)][n]).  Both tiles pixel-major, both fragments through
+// the transposing read; the same double-buffered one-barrier pipeline.  The bias gradient (column sums of dY) is folded in:
 // workgroups with tn == 0 and tap == 0 add up the dY tiles they stage anyway.
 // ---------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, bool VEC, int XF>
-__global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
+template <class P, int BM, int BN, int WM, int WN, bool VEC, int XF>
+__device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
+  typedef typename P::elem elem;
+  constexpr int BK = P::BK_WGRAD;  // pixels per step
   constexpr int NT = 64 * WM * WN;
-  constexpr int NL = NT;
-  constexpr int LDA = BM + 4, LDB = BN + 4;
+  constexpr int LDA = BM + P::PAD_T, LDB = BN + P::PAD_T;
   constexpr int SA = BK * LDA, SB = BK * LDB;
   constexpr int STAGE = SA + SB;
-  constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF : 0;
+  constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(elem)) : 0;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
-  constexpr int AQ = BM / 4, AKR = NL / AQ, AI = BK / AKR;  // dY tile: AQ float4 per row
-  constexpr int BQ = BN / 4, BKR = NL / BQ, BI = BK / BKR;
-  static_assert(AI >= 1 && BI >= 1 && TM % 32 == 0 && TN % 32 == 0, "tile/wave layout");
-  __shared__ __attribute__((aligned(16))) float smem[2 * STAGE + SS];
-  float* sS = smem + 2 * STAGE;
+  constexpr int AQ = BM / 4, AKR = NT / AQ, AI = BK / AKR;  // dY tile: AQ float4 per row
+  constexpr int BQ = BN / 4, BKR = NT / BQ, BI = BK / BKR;
+  static_assert(AI >= 1 && BI >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
+  __shared__ __attribute__((aligned(16))) elem smem[2 * STAGE + SS];
+  float* sS = reinterpret_cast<float*>(smem + 2 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lt = tid;
   const int wm = wave / WN, wn = wave % WN;
+  const LanePos lp = lane_pos(lane);
+  const int lr = lp.lr, lh = lp.lh;
   const int tilesN = (p.N + BN - 1) / BN;
   const int tm = blockIdx.x / tilesN, tn = blockIdx.x % tilesN;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -351,11 +524,13 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
   const vae_conv_geom g = p.g;
   const SrcMap smap = make_srcmap(g);
   const int kh = (g.taps == 9) ? tap / 3 : 0, kw = (g.taps == 9) ? tap - kh * 3 : 0;
-  const float* __restrict__ dY = p.dY + (int64_t)z * p.sYb;
-  const float* __restrict__ X = p.X + (int64_t)z * p.sXb;
+  const bool ybf = P::flag(p.y_bf16), xbf = P::flag(p.x_bf16);  // storage of dY / X
+  const unsigned esY = ybf ? 2u : 4u, esX = xbf ? 2u : 4u;
+  const char* __restrict__ dY = reinterpret_cast<const char*>(p.dY) + (int64_t)z * p.sYb * esY;
+  const char* __restrict__ X = reinterpret_cast<const char*>(p.X) + (int64_t)z * p.sXb * esX;
 
   int chunk = (p.npix + p.nsplit - 1) / p.nsplit;
-  chunk = ((chunk + BK - 1) / BK) * BK;
+  chunk = ((chunk + 31) / 32) * 32;  // to 32 pixels under every policy: the host's table-fit check (vae_xf_fusable_wgrad) assumes it
   const int pbeg = split * chunk;
   const int pend = min(p.npix, pbeg + chunk);
   const int steps = (pend > pbeg) ? (pend - pbeg + BK - 1) / BK : 0;
@@ -377,22 +552,17 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
   }
 
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  zero_acc(acc);
 
   // buffer descriptors (vectorised instantiations): dY from this split's first pixel, X from its first image
   const size_t img = (size_t)g.Hs * g.Ws * g.Cs;
-  const size_t ybytes = (size_t)(steps > 0 ? pend - pbeg : 0) * p.ldy * 4u, xbytes = (size_t)(g.B - b_lo) * img * 4u;
-  const auto rsY = VAE_BUF_RSRC(dY + (int64_t)pbeg * p.ldy, ybytes < BUF_MAX ? ybytes : BUF_MAX);
-  const auto rsX = VAE_BUF_RSRC(X + (int64_t)b_lo * img, xbytes < BUF_MAX ? xbytes : BUF_MAX);
+  const size_t ybytes = (size_t)(steps > 0 ? pend - pbeg : 0) * p.ldy * esY, xbytes = (size_t)(g.B - b_lo) * img * esX;
+  const auto rsY = VAE_BUF_RSRC(dY + (int64_t)pbeg * p.ldy * esY, ybytes < BUF_MAX ? ybytes : BUF_MAX);
+  const auto rsX = VAE_BUF_RSRC(X + (int64_t)b_lo * img * esX, xbytes < BUF_MAX ? xbytes : BUF_MAX);
 
-  const int a4 = lt % AQ, akq = lt / AQ;
-  const int b4 = lt % BQ, bkq = lt / BQ;
-  f32x4 ra[AI], rx[BI];
+  const int a4 = tid % AQ, akq = tid / AQ;
+  const int b4 = tid % BQ, bkq = tid / BQ;
+  typename P::raw4 ra[AI], rx[BI];
   int xb[BI];
   f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
 
@@ -402,8 +572,8 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
     for (int i = 0; i < AI; ++i) {
       const int pix = pb + akq + AKR * i;
       const int c = m0 + a4 * 4;
-      if (VEC) ra[i] = VAE_BUF_LOAD4(rsY, oob_unless(pix < pend && c < p.M, ((unsigned)(pix - pbeg) * (unsigned)p.ldy + (unsigned)c) * 4u));
-      else ra[i] = load4s(dY + (int64_t)pix * p.ldy + c, pix < pend, c, p.M);
+      if constexpr (VEC) ra[i] = P::load4(rsY, esY, pix < pend && c < p.M, pix - pbeg, p.ldy, c);
+      else ra[i] = load4s(p.dY + (int64_t)z * p.sYb + (int64_t)pix * p.ldy + c, pix < pend, c, p.M);
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
@@ -413,56 +583,42 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
       const int y = rem / g.Wo, x = rem - y * g.Wo;
       int sy = 0, sx = 0;
       const bool ok = src_pixel(smap, y, x, kh, kw, sy, sx) && (pix < pend);
-      if (VEC) rx[i] = VAE_BUF_LOAD4(rsX, oob_unless(ok && c < p.N, ((unsigned)(((b - b_lo) * g.Hs + sy) * g.Ws + sx) * (unsigned)g.Cs + (unsigned)c) * 4u));
-      else rx[i] = load4s(X + (((int64_t)b * g.Hs + sy) * g.Ws + sx) * g.Cs + c, ok, c, p.N);
+      if constexpr (VEC) rx[i] = P::load4(rsX, esX, ok && c < p.N, ((b - b_lo) * g.Hs + sy) * g.Ws + sx, g.Cs, c);
+      else rx[i] = load4s(p.X + (int64_t)z * p.sXb + (((int64_t)b * g.Hs + sy) * g.Ws + sx) * g.Cs + c, ok, c, p.N);
       xb[i] = ok ? b : -1;
     }
   };
-  auto store_lds = [&](float* sA, float* sB) {
+  auto store_lds = [&](elem* sA, elem* sB) {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-      *reinterpret_cast<f32x4*>(&sA[(akq + AKR * i) * LDA + a4 * 4]) = ra[i];
-      if (do_bias) bsum += ra[i];
+      const f32x4 v = P::to_f32(ra[i], ybf);
+      P::put4_stored(&sA[(akq + AKR * i) * LDA + a4 * 4], ra[i], v, ybf);
+      if (do_bias) bsum += v;
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
-      f32x4 v = rx[i];
+      f32x4 v = P::to_f32(rx[i], xbf);
       if (XF != VAE_XF_NONE) {
         const bool ok = xb[i] >= 0;
         const int o = ok ? (xb[i] - b_lo) * BN + b4 * 4 : 0;
         v = xform4_tab<XF>(v, sS + o, sS + SS_HALF + o, ok);
       }
-      *reinterpret_cast<f32x4*>(&sB[(bkq + BKR * i) * LDB + b4 * 4]) = v;
+      P::put4(&sB[(bkq + BKR * i) * LDB + b4 * 4], v);
     }
   };
-
-  const int lr = lane & 31, lh = lane >> 5;
-  f32x4 fa[2][MI], fb[2][NI];
-  auto fetch = [&](const float* sA, const float* sB, int kk, f32x4* a, f32x4* b) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = kk * 8 + lh * 4 + j;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) a[mi][j] = sA[k * LDA + wm * TM + mi * 32 + lr];
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) b[ni][j] = sB[k * LDB + wn * TN + ni * 32 + lr];
-    }
+  typename P::frag fa[2][MI], fb[2][NI];
+  auto fetch = [&](const elem* sA, const elem* sB, int kg, typename P::frag* a, typename P::frag* b) {
+    P::template frags_tt<MI, NI>(a, b, sA, LDA, wm * TM, sB, LDB, wn * TN, kg, lp);
   };
-  auto compute = [&](const float* sA, const float* sB, int kk) {  // fragments of kk already requested
-    if (kk + 1 < BK / 8) fetch(sA, sB, kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1]);
+  constexpr int NKG = BK / P::KG;
+  auto compute = [&](const elem* sA, const elem* sB, int kg) {  // fragments of kg already requested
+    if (kg + 1 < NKG) fetch(sA, sB, kg + 1, fa[(kg + 1) & 1], fb[(kg + 1) & 1]);
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk & 1][mi][j], fb[kk & 1][ni][j], acc[mi][ni], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
+    if (P::SETPRIO) __builtin_amdgcn_s_setprio(1);
+    P::mma(acc, fa[kg & 1], fb[kg & 1]);
+    if (P::SETPRIO) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
-
   if (steps > 0) {
     load_regs(0);
     __syncthreads();  // scale/shift table visible
@@ -470,18 +626,18 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
     if (steps > 1) load_regs(1);
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
-      const float* cA = smem + (s & 1) * STAGE;
-      const float* cB = cA + SA;
+      const elem* cA = smem + (s & 1) * STAGE;
+      const elem* cB = cA + SA;
       fetch(cA, cB, 0, fa[0], fb[0]);
       compute(cA, cB, 0);
-      compute(cA, cB, 1);
-      if (s + 1 < steps) {
-        float* nA = smem + ((s + 1) & 1) * STAGE;
+      if (NKG == 4) compute(cA, cB, 1);
+      if (s + 1 < steps) {  // staged in the shadow of the MFMAs already issued
+        elem* nA = smem + ((s + 1) & 1) * STAGE;
         store_lds(nA, nA + SA);
         if (s + 2 < steps) load_regs(s + 2);
       }
-      compute(cA, cB, 2);
-      compute(cA, cB, 3);
+      compute(cA, cB, NKG / 2);
+      if (NKG == 4) compute(cA, cB, 3);
       __syncthreads();
     }
   }
@@ -515,6 +671,16 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) {
     }
   }
 }
+
+// entry points: a body under its policy
+template <int BM, int BN, int WM, int WN, bool BKM, bool VEC, int XF>
+__global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args p) { rows_body<F32, BM, BN, WM, WN, BKM, VEC, XF>(p); }
+template <int BM, int BN, int WM, int WN, bool VEC, int XF>
+__global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) { wgrad_body<F32, BM, BN, WM, WN, VEC, XF>(p); }
+template <int BM, int BN, int WM, int WN, bool BKM, int XF>
+__global__ __launch_bounds__(64 * WM * WN) void igemm_rows_bf16_kernel(vae_igemm_args p) { rows_body<BF16, BM, BN, WM, WN, BKM, true, XF>(p); }
+template <int BM, int BN, int WM, int WN, int XF>
+__global__ __launch_bounds__(64 * WM * WN) void wgrad_bf16_kernel(vae_wgrad_args p) { wgrad_body<BF16, BM, BN, WM, WN, true, XF>(p); }
 
 // out[i] = sum_k partial[k][i], fixed association (reproducible).  16-byte loads, 8 independent loads in flight per
 // thread; KP threads share a column quad and split the k range (a 128-channel layer has 128 splits of only 147 K elements:
@@ -576,55 +742,82 @@ __global__ void reduce_splits_scalar_kernel(const float* __restrict__ partial, i
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool BKM, bool VEC>
-int launch_rows_xf(const vae_igemm_args& a, dim3 grid, hipStream_t st) {
-  if (BKM) {
-    if (a.xf != VAE_XF_NONE) { vae_set_error("igemm_rows: xf unsupported with n-contiguous weights"); return VAE_EINVAL; }
-    hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, VAE_XF_NONE>), grid, dim3(64 * WM * WN), 0, st, a);
+// ---------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------
+template <int V>
+using int_c = std::integral_constant<int, V>;
+using std::false_type;
+using std::true_type;
+
+// THE xf switch: launch(int_c<xf>) for a valid xf, false for any other value
+template <class Launch>
+bool dispatch_xf(int xf, Launch launch) {
+  switch (xf) {
+    case VAE_XF_NONE: launch(int_c<VAE_XF_NONE>{}); return true;
+    case VAE_XF_AFFINE: launch(int_c<VAE_XF_AFFINE>{}); return true;
+    case VAE_XF_AFFINE_SILU: launch(int_c<VAE_XF_AFFINE_SILU>{}); return true;
+    default: return false;
+  }
+}
+
+// BF: the bf16 policy (vectorised shapes only: the caller checked, `vec` is not read)
+template <bool BF, int BM, int BN, int WM, int WN>
+int launch_rows_tile(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), 1, (unsigned)a.batch), block(64 * WM * WN);
+  auto go = [&](auto bkm_c, auto vec_c) {
+    constexpr bool BKM = decltype(bkm_c)::value, VEC = decltype(vec_c)::value;
+    auto launch = [&](auto xf) {
+      if constexpr (BF) hipLaunchKernelGGL((igemm_rows_bf16_kernel<BM, BN, WM, WN, BKM, decltype(xf)::value>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, decltype(xf)::value>), grid, block, 0, st, a);
+    };
+    if constexpr (BKM) {  // the n-contiguous weight tile exists untransformed only
+      if (a.xf != VAE_XF_NONE) { vae_set_error("igemm_rows: xf unsupported with n-contiguous weights"); return VAE_EINVAL; }
+      launch(int_c<VAE_XF_NONE>{});
+    } else if (!dispatch_xf(a.xf, launch)) {
+      vae_set_error("igemm_rows: bad xf %d", a.xf);
+      return VAE_EINVAL;
+    }
     return 0;
-  }
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, false, VEC, VAE_XF_NONE>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, false, VEC, VAE_XF_AFFINE>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    case VAE_XF_AFFINE_SILU: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, false, VEC, VAE_XF_AFFINE_SILU>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    default: vae_set_error("igemm_rows: bad xf %d", a.xf); return VAE_EINVAL;
-  }
+  };
+  if (BF || vec) return bkm ? go(true_type{}, true_type{}) : go(false_type{}, true_type{});
+  if constexpr (!BF) return bkm ? go(true_type{}, false_type{}) : go(false_type{}, false_type{});
   return 0;
 }
-
-template <int BM, int BN, int WM, int WN>
+template <bool BF>
 int launch_rows(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st) {
-  dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), 1, (unsigned)a.batch);
-  if (bkm) return vec ? launch_rows_xf<BM, BN, WM, WN, true, true>(a, grid, st) : launch_rows_xf<BM, BN, WM, WN, true, false>(a, grid, st);
-  return vec ? launch_rows_xf<BM, BN, WM, WN, false, true>(a, grid, st) : launch_rows_xf<BM, BN, WM, WN, false, false>(a, grid, st);
+  return (a.N <= 32) ? launch_rows_tile<BF, 128, 32, 4, 1>(a, bkm, vec, st) : launch_rows_tile<BF, 128, 128, 4, 2>(a, bkm, vec, st);
 }
 
-template <int BM, int BN, int WM, int WN, bool VEC>
-int launch_wgrad_xf(const vae_wgrad_args& a, dim3 grid, hipStream_t st) {
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, VEC, VAE_XF_NONE>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, VEC, VAE_XF_AFFINE>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    case VAE_XF_AFFINE_SILU: hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, VEC, VAE_XF_AFFINE_SILU>), grid, dim3(64 * WM * WN), 0, st, a); break;
-    default: vae_set_error("wgrad: bad xf %d", a.xf); return VAE_EINVAL;
-  }
+template <bool BF, int BM, int BN, int WM, int WN>
+int launch_wgrad_tile(const vae_wgrad_args& a, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), (unsigned)(a.g.taps * a.nsplit), (unsigned)a.batch), block(64 * WM * WN);
+  auto go = [&](auto vec_c) {
+    auto launch = [&](auto xf) {
+      if constexpr (BF) hipLaunchKernelGGL((wgrad_bf16_kernel<BM, BN, WM, WN, decltype(xf)::value>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, decltype(vec_c)::value, decltype(xf)::value>), grid, block, 0, st, a);
+    };
+    if (dispatch_xf(a.xf, launch)) return 0;
+    vae_set_error("wgrad: bad xf %d", a.xf);
+    return VAE_EINVAL;
+  };
+  if (BF || vec) return go(true_type{});
+  if constexpr (!BF) return go(false_type{});
   return 0;
 }
-template <int BM, int BN, int WM, int WN>
+template <bool BF>
 int launch_wgrad(const vae_wgrad_args& a, bool vec, hipStream_t st) {
-  dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), (unsigned)(a.g.taps * a.nsplit), (unsigned)a.batch);
-  return vec ? launch_wgrad_xf<BM, BN, WM, WN, true>(a, grid, st) : launch_wgrad_xf<BM, BN, WM, WN, false>(a, grid, st);
+  if (a.M <= 32) return launch_wgrad_tile<BF, 32, 128, 1, 4>(a, vec, st);
+  if (a.N <= 32) return launch_wgrad_tile<BF, 128, 32, 4, 1>(a, vec, st);
+  return launch_wgrad_tile<BF, 128, 128, 4, 2>(a, vec, st);
 }
 
 }  // namespace
 
-int launch_rows_f32(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st) {
-  return (a.N <= 32) ? launch_rows<128, 32, 4, 1>(a, bkm, vec, st) : launch_rows<128, 128, 4, 2>(a, bkm, vec, st);
-}
-int launch_wgrad_f32(const vae_wgrad_args& a, bool vec, hipStream_t st) {
-  if (a.M <= 32) return launch_wgrad<32, 128, 1, 4>(a, vec, st);
-  if (a.N <= 32) return launch_wgrad<128, 32, 4, 1>(a, vec, st);
-  return launch_wgrad<128, 128, 4, 2>(a, vec, st);
-}
+int launch_rows_f32(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st) { return launch_rows<false>(a, bkm, vec, st); }
+int launch_rows_bf16(const vae_igemm_args& a, bool bkm, hipStream_t st) { return launch_rows<true>(a, bkm, true, st); }
+int launch_wgrad_f32(const vae_wgrad_args& a, bool vec, hipStream_t st) { return launch_wgrad<false>(a, vec, st); }
+int launch_wgrad_bf16(const vae_wgrad_args& a, hipStream_t st) { return launch_wgrad<true>(a, true, st); }
 
 static int reduce_splits_impl(const float* partial, int32_t nsplit, int64_t n, float* out, const float* partial2, int32_t n2, float* out2,
                               hipStream_t st) {

@@ -4,10 +4,10 @@
 #pragma once
 #include "common_host.h"
 
-// igemm.hip: the flat fp32 implicit-GEMM kernels (any geometry) and the split reduction
+// igemm.hip: the flat implicit-GEMM kernels (any geometry) under the fp32 policy and under the bf16-compute policy
+// (vectorised shapes only), and the split reduction
 int launch_rows_f32(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st);
 int launch_wgrad_f32(const vae_wgrad_args& a, bool vec, hipStream_t st);
-// igemm_bf16.hip: their bf16-compute variants (vectorised shapes only)
 int launch_rows_bf16(const vae_igemm_args& a, bool bkm, hipStream_t st);
 int launch_wgrad_bf16(const vae_wgrad_args& a, hipStream_t st);
 
