@@ -682,22 +682,38 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_bf16_kernel(vae_igemm
 template <int BM, int BN, int WM, int WN, int XF>
 __global__ __launch_bounds__(64 * WM * WN) void wgrad_bf16_kernel(vae_wgrad_args p) { wgrad_body<BF16, BM, BN, WM, WN, true, XF>(p); }
 
+// out2[i] = sum_k partial2[k][i] for the 256 columns of workgroup `blk` (the bias gradient: few columns, up to 1024 splits), added
+// one after the other in ascending k.  Sixteen loads go out before the first of them is added: a loop of one load and one add per
+// split waits a full memory latency per split, 1024 times for the <= 4-channel weight gradients.
+__device__ __forceinline__ void small_column_sums(const float* __restrict__ partial2, int nsplit, int n2, float* __restrict__ out2, int blk) {
+  const int i = blk * 256 + (int)threadIdx.x;
+  if (i >= n2) return;
+  const float* p = partial2 + i;
+  float s = 0.f;
+  int k = 0;
+  for (; k + 16 <= nsplit; k += 16) {
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = p[(int64_t)(k + j) * n2];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += v[j];
+  }
+  for (; k < nsplit; ++k) s += p[(int64_t)k * n2];
+  out2[i] = s;
+}
+
 // out[i] = sum_k partial[k][i], fixed association (reproducible).  16-byte loads, 8 independent loads in flight per
 // thread; KP threads share a column quad and split the k range (a 128-channel layer has 128 splits of only 147 K elements:
 // one thread per element leaves too few bytes in flight to fill HBM), combined through LDS in k order.
-// A second, small reduction (the bias gradient: [nsplit][n2]) rides in the same launch: workgroups main_blocks.. do it.
+// A second, small reduction (the bias gradient: [nsplit][n2]) rides in the same launch: workgroups main_blocks.. do it
+// (small_column_sums).
 template <int KP>
 __global__ __launch_bounds__(256) void reduce_splits_kernel(const float* __restrict__ partial, int nsplit, int64_t n, float* __restrict__ out,
                                                             int main_blocks, const float* __restrict__ partial2, int n2, float* __restrict__ out2) {
   constexpr int COLS = 256 / KP;
   __shared__ f32x4 red[KP > 1 ? 256 : 1];
   if ((int)blockIdx.x >= main_blocks) {  // uniform per workgroup
-    const int i = ((int)blockIdx.x - main_blocks) * 256 + threadIdx.x;
-    if (i < n2) {
-      float s2 = 0.f;
-      for (int k = 0; k < nsplit; ++k) s2 += partial2[(int64_t)k * n2 + i];
-      out2[i] = s2;
-    }
+    small_column_sums(partial2, nsplit, n2, out2, (int)blockIdx.x - main_blocks);
     return;
   }
   const int col = threadIdx.x % COLS, kp = threadIdx.x / COLS;
@@ -739,6 +755,148 @@ __global__ void reduce_splits_scalar_kernel(const float* __restrict__ partial, i
     float s = 0.f;
     for (int k = 0; k < nsplit; ++k) s += partial[(int64_t)k * n + i];
     out[i] = s;
+  }
+}
+
+// Reduction of a Winograd weight-gradient slab [nsplit][NPOS][Cin][Cout] (wgrad3_wino.hip: NPOS = 16, wgrad3_upwino.hip: 9) into
+// dW [Cout][3][3][Cin] (OHWI) in one launch: the slab is read once, nothing is staged in global memory.
+//     S_p[ci][co] = sum_k slab[k][p][ci][co]
+//     NPOS 16:  dW[co][a][b][ci] = sum_{i,j} At[a][i] At[b][j] c_i c_j S_{4i+j}[ci][co]   At = [1 1 1 0; 0 1 -1 0; 0 1 1 -1], c = (1, .5, .5, 1)
+//     NPOS  9:  dW[co][a][b][ci] = sum_{i,j} At[a][i] At[b][j]         S_{3i+j}[ci][co]   At = [1 1 0; 0 1 0; 0 1 -1]
+// S_p is added in the association of reduce_splits_kernel (which used to form it in a buffer of its own, so dW keeps its bits):
+//     nsplit >= 32:  ((g0 + g1) + g2) + g3, g_j = the splits [j per, (j + 1) per), per = ceil(nsplit / 4);   nsplit < 32: one range;
+//     a range = rounds of 8 splits, each added to the sum as ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)), then the rest one by one.
+// Workgroup = a tile of TCI ci x 32 co = Q column quads (16-byte loads, lanes along co: 128-byte rows) and KP = 256 / Q thread
+// groups that share the POSITIONS (group g: positions g, g + KP, ..), so that no sum is split over threads and the parallelism
+// costs no change of association: a thread has 8 or 16 loads of one position in flight (rounds), or one load of each of its
+// positions (the rest).  The sums meet in LDS, thread group 0 applies the transform to its quad and the tile goes out through an
+// LDS transpose with lanes along ci.  The launcher picks the largest tile that still gives 256 workgroups: a 128-channel layer
+// (64 splits of 1 MB) runs as 256 workgroups of 2 x 32 with one position per thread, a 512-channel layer (4 splits of 16 MB) as
+// 256 workgroups of 32 x 32 with all 16 positions in a thread.
+// Workgroups beyond the tiles sum the bias-gradient slab [nsplit][Cout] (small_column_sums).
+template <int NPOS, int TCI>
+__global__ __launch_bounds__(256) void wgrad_wino_reduce_kernel(const float* __restrict__ slab, int nsplit, int N, int M, float* __restrict__ dW,
+                                                                int tiles, const float* __restrict__ bpart, float* __restrict__ db) {
+  constexpr int TQ = 8, TCO = 4 * TQ, Q = TCI * TQ, KP = 256 / Q, NP = (NPOS + KP - 1) / KP;
+  constexpr int ST0 = KP > 1 ? NPOS * Q * 4 : 0;  // floats of the sums [NPOS][Q] quads; behind them the transposed tile [9][TCO][TCI + 1]
+  __shared__ __attribute__((aligned(16))) float smem[ST0 + 9 * TCO * (TCI + 1)];
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= tiles) {  // uniform per workgroup
+    small_column_sums(bpart, nsplit, M, db, (int)blockIdx.x - tiles);
+    return;
+  }
+  const int tilesM = M / TCO;
+  const int c0 = ((int)blockIdx.x / tilesM) * TCI, m0 = ((int)blockIdx.x % tilesM) * TCO;
+  const int q = tid % Q, kp = tid / Q;
+  const int cq = q % TQ, cl = q / TQ;
+  const int64_t pstride4 = ((int64_t)N * M) >> 2, sstride4 = NPOS * pstride4;  // one position / one split, in quads
+  const f32x4* src = reinterpret_cast<const f32x4*>(slab + (int64_t)(c0 + cl) * M + m0 + 4 * cq);
+  const f32x4* sp[NP];  // this thread's positions kp + j KP (one past the last: position 0 again, read and dropped)
+#pragma unroll
+  for (int j = 0; j < NP; ++j) sp[j] = src + (kp + j * KP < NPOS ? kp + j * KP : 0) * pstride4;
+  auto tree8 = [](const f32x4* v) { return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])); };
+  auto range = [&](int k0, int k1, f32x4(&g)[NP]) {  // the splits [k0, k1) of every position of this thread
+#pragma unroll
+    for (int j = 0; j < NP; ++j) g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int k = k0;
+    if constexpr (NP == 1) {  // two rounds' loads at once
+      for (; k + 16 <= k1; k += 16) {
+        f32x4 v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = sp[0][(int64_t)(k + i) * sstride4];
+        g[0] += tree8(v);
+        g[0] += tree8(v + 8);
+      }
+    }
+    for (; k + 8 <= k1; k += 8) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        f32x4 v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = sp[j][(int64_t)(k + i) * sstride4];
+        g[j] += tree8(v);
+      }
+    }
+    for (; k < k1; ++k) {
+      f32x4 v[NP];
+#pragma unroll
+      for (int j = 0; j < NP; ++j) v[j] = sp[j][(int64_t)k * sstride4];
+#pragma unroll
+      for (int j = 0; j < NP; ++j) g[j] += v[j];
+    }
+  };
+  f32x4 mine[NP];
+  if (nsplit >= 32) {
+    const int per = (nsplit + 3) / 4;
+    range(0, min(nsplit, per), mine);
+    for (int r = 1; r < 4; ++r) {
+      f32x4 g[NP];
+      range(r * per, min(nsplit, (r + 1) * per), g);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) mine[j] += g[j];
+    }
+  } else {
+    range(0, nsplit, mine);
+  }
+  f32x4 acc[NPOS];
+  if constexpr (KP > 1) {
+    f32x4* red = reinterpret_cast<f32x4*>(smem);  // [NPOS][Q]
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+      if (kp + j * KP < NPOS) red[(kp + j * KP) * Q + q] = mine[j];
+    __syncthreads();
+    if (kp == 0) {
+#pragma unroll
+      for (int p = 0; p < NPOS; ++p) acc[p] = red[p * Q + q];
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < NPOS; ++p) acc[p] = mine[p];
+  }
+  float(*sT)[TCO][TCI + 1] = reinterpret_cast<float(*)[TCO][TCI + 1]>(smem + ST0);
+  if (kp == 0) {
+    f32x4 o[9];
+    if constexpr (NPOS == 16) {
+      f32x4 h[3][4];  // A^T (c c^T (.) S)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float cj = (j == 1 || j == 2) ? 0.5f : 1.f;
+        const f32x4 r0 = acc[0 * 4 + j] * cj, r1 = acc[1 * 4 + j] * (0.5f * cj), r2 = acc[2 * 4 + j] * (0.5f * cj), r3 = acc[3 * 4 + j] * cj;
+        h[0][j] = (r0 + r1) + r2;
+        h[1][j] = r1 - r2;
+        h[2][j] = (r1 + r2) - r3;
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        o[a * 3 + 0] = (h[a][0] + h[a][1]) + h[a][2];
+        o[a * 3 + 1] = h[a][1] - h[a][2];
+        o[a * 3 + 2] = (h[a][1] + h[a][2]) - h[a][3];
+      }
+    } else {
+      f32x4 h[3][3];  // A''^T S
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        h[0][j] = acc[0 * 3 + j] + acc[1 * 3 + j];
+        h[1][j] = acc[1 * 3 + j];
+        h[2][j] = acc[1 * 3 + j] - acc[2 * 3 + j];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        o[a * 3 + 0] = h[a][0] + h[a][1];
+        o[a * 3 + 1] = h[a][1];
+        o[a * 3 + 2] = h[a][1] - h[a][2];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sT[t][4 * cq + e][cl] = o[t][e];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < 9 * TCO * TCI; idx += 256) {  // lanes along ci, then the 9 taps of one co: (9 N)-float rows of dW
+    const int c = idx % TCI, r = idx / TCI;
+    const int t = r % 9, ml = r / 9;
+    dW[((int64_t)(m0 + ml) * 9 + t) * N + c0 + c] = sT[t][ml][c];
   }
 }
 
@@ -858,15 +1016,26 @@ extern "C" int vae_wgrad_wino_reduce(const float* slab, int32_t nsplit, int32_t 
   VAE_CHECK(slab && dW && nsplit > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, "wgrad_wino_reduce: bad args");
   VAE_CHECK(npos == 16 || npos == 9, "wgrad_wino_reduce: npos must be 16 (plain 3x3 layer) or 9 (upsampler convolution)");
   VAE_CHECK((bias_partial == nullptr) == (db == nullptr), "wgrad_wino_reduce: bias_partial and db go together");
-  VAE_CHECK(nsplit == 1 || scratch != nullptr, "wgrad_wino_reduce: nsplit > 1 needs the [16*Cin*Cout] scratch buffer");
+  VAE_CHECK(aligned16(slab), "wgrad_wino_reduce: the slab must be 16-byte aligned");
+  VAE_CHECK((int64_t)Cin * Cout <= (1ll << 30), "wgrad_wino_reduce: too many channel pairs");
+  (void)scratch;  // unused since the reduction reads the slab once (kept in the signature)
   hipStream_t st = (hipStream_t)stream;
-  if (nsplit > 1) {  // wide fixed-order sum over the splits first (the slab of a 128-channel layer is 64 x 1 MB), then the transform
-    if (int rc = reduce_splits_impl(slab, nsplit, (int64_t)npos * Cin * Cout, scratch, bias_partial, bias_partial ? Cout : 0, db, st)) return rc;
-    VAE_LAUNCH_CHECK("reduce_splits");
-    if (int rc = (npos == 9 ? launch_upwino_wgrad_reduce : launch_wino_wgrad_reduce)(scratch, 1, Cin, Cout, dW, nullptr, nullptr, st)) return rc;
-  } else {
-    if (int rc = (npos == 9 ? launch_upwino_wgrad_reduce : launch_wino_wgrad_reduce)(slab, 1, Cin, Cout, dW, bias_partial, db, st)) return rc;
-  }
-  VAE_LAUNCH_CHECK("wino_wgrad_reduce");
+  const int extra = bias_partial ? (Cout + 255) / 256 : 0;
+  auto launch = [&](auto npos_c, auto tci_c) {
+    constexpr int NPOS = decltype(npos_c)::value, TCI = decltype(tci_c)::value;
+    const int tiles = (Cin / TCI) * (Cout / 32);
+    hipLaunchKernelGGL((wgrad_wino_reduce_kernel<NPOS, TCI>), dim3((unsigned)(tiles + extra)), dim3(256), 0, st, slab, nsplit, Cin, Cout, dW, tiles,
+                       bias_partial, db);
+  };
+  // the largest tile (32, 8 or 2 ci x 32 co: 1, 4 or 16 thread groups over the positions) that leaves 256 workgroups
+  const int64_t t32 = (int64_t)(Cin / 32) * (Cout / 32);
+  auto pick = [&](auto npos_c) {
+    if (t32 >= 256) launch(npos_c, int_c<32>{});
+    else if (4 * t32 >= 256) launch(npos_c, int_c<8>{});
+    else launch(npos_c, int_c<2>{});
+  };
+  if (npos == 9) pick(int_c<9>{});
+  else pick(int_c<16>{});
+  VAE_LAUNCH_CHECK("wgrad_wino_reduce");
   return VAE_OK;
 }

@@ -65,12 +65,11 @@ int64_t wgrad3_tile_bf16_units(const vae_conv_geom& g);
 int wgrad3_tile_bf16_columns(const vae_wgrad_args& a);
 int launch_wgrad3_tile_bf16(const vae_wgrad_args& a, hipStream_t st);
 int launch_wgrad3_dma_bf16(const vae_wgrad_args& a, hipStream_t st);
-// wgrad3_wino.hip / wgrad3_upwino.hip: fp32 Winograd weight gradients (16 / 9 positions) and their reductions
+// wgrad3_wino.hip / wgrad3_upwino.hip: fp32 Winograd weight gradients (16 / 9 positions); their slabs are reduced by
+// vae_wgrad_wino_reduce (igemm.hip)
 bool wgrad3_wino_eligible(const vae_wgrad_args& a);
 int64_t wgrad3_wino_units(const vae_conv_geom& g);
 int launch_wgrad3_wino(const vae_wgrad_args& a, hipStream_t st);
-int launch_wino_wgrad_reduce(const float* slab, int nsplit, int N, int M, float* dW, const float* bpart, float* db, hipStream_t st);
 bool wgrad3_upwino_eligible(const vae_wgrad_args& a);
 int64_t wgrad3_upwino_units(const vae_conv_geom& g);
 int launch_wgrad3_upwino(const vae_wgrad_args& a, hipStream_t st);
-int launch_upwino_wgrad_reduce(const float* slab, int nsplit, int N, int M, float* dW, const float* bpart, float* db, hipStream_t st);

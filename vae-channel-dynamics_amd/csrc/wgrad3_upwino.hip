@@ -12,8 +12,8 @@
 //
 // Kernel: as wgrad3_wino.hip -- a unit = 8 low-resolution pixels of one row (a 2 x 16 strip of dY); per unit the 3 x 10-pixel halo
 // of x and the strip of dY go to LDS untransformed, transposed to [row][channel][x]; a wave builds its MFMA operands while
-// reading them; split-K slabs [split][9][Cin][Cout]; a reduction kernel sums the slabs in fixed order, applies A''^T . A'' and
-// writes OHWI.  Workgroup = 8 waves = 32 ci x 128 co x 9 positions: wave w owns position w (all four 32-channel blocks of co), and
+// reading them; split-K slabs [split][9][Cin][Cout]; wgrad_wino_reduce_kernel<9> (igemm.hip, one body for both schemes) sums the
+// slabs in fixed order, applies A''^T . A'' and writes OHWI.  Workgroup = 8 waves = 32 ci x 128 co x 9 positions: wave w owns position w (all four 32-channel blocks of co), and
 // the NINTH position is split by channel block over waves 0..3 -- one per SIMD (wave k of a workgroup runs on SIMD k % 4), so every
 // SIMD carries 36 MFMAs per step.  (A first version with one position per wave and 9 waves put three waves of every workgroup
 // on SIMD 0: 0.51 of the matrix peak.)  One workgroup per CU at 158 registers (a 128-register build spilled 27, with scratch reloads
@@ -250,59 +250,6 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
   }
 }
 
-// dW[co][a][b][ci] = sum_{p,q} At[a][p] At[b][q] sum_split slab[split][p*3+q][ci][co], At = A''^T = [1 1 0; 0 1 0; 0 1 -1]; 32 x 32
-// (ci, co) tile per workgroup, read with lanes along co, written with lanes along ci.  Workgroups beyond the tiles reduce the
-// bias-gradient slab.
-__global__ __launch_bounds__(256) void upwino_wgrad_reduce_kernel(const float* __restrict__ slab, int nsplit, int N, int M, float* __restrict__ dW,
-                                                                  int tiles, const float* __restrict__ bpart, float* __restrict__ db) {
-  __shared__ float sT[9][32][33];
-  const int tid = threadIdx.x;
-  if ((int)blockIdx.x >= tiles) {
-    const int m = ((int)blockIdx.x - tiles) * 256 + tid;
-    if (m < M) {
-      float s = 0.f;
-      for (int k = 0; k < nsplit; ++k) s += bpart[(int64_t)k * M + m];
-      db[m] = s;
-    }
-    return;
-  }
-  const int tilesM = M / 32;
-  const int c0 = ((int)blockIdx.x / tilesM) * 32, m0 = ((int)blockIdx.x % tilesM) * 32;
-  const int64_t pstride = (int64_t)N * M, sstride = NPOS * pstride;
-#pragma unroll 1
-  for (int r = 0; r < 4; ++r) {
-    const int cl = (tid >> 5) + 8 * r, ml = tid & 31;
-    const float* src = slab + (int64_t)(c0 + cl) * M + m0 + ml;
-    float mm[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-      float s = 0.f;
-      for (int k = 0; k < nsplit; ++k) s += src[(int64_t)k * sstride + q * pstride];
-      mm[q] = s;
-    }
-    float h[3][3];  // A''^T M
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      h[0][j] = mm[0 * 3 + j] + mm[1 * 3 + j];
-      h[1][j] = mm[1 * 3 + j];
-      h[2][j] = mm[1 * 3 + j] - mm[2 * 3 + j];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      sT[a * 3 + 0][ml][cl] = h[a][0] + h[a][1];
-      sT[a * 3 + 1][ml][cl] = h[a][1];
-      sT[a * 3 + 2][ml][cl] = h[a][1] - h[a][2];
-    }
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int r = 0; r < 4; ++r) {
-    const int ml = (tid >> 5) + 8 * r, cl = tid & 31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) dW[((int64_t)(m0 + ml) * 9 + t) * N + c0 + cl] = sT[t][ml][cl];
-  }
-}
-
 }  // namespace
 
 // conv3x3(nearest_upsample_2x(x)) in fp32: geometry mode UP2X (source = the low-resolution x, row grid = dY at twice the size),
@@ -326,12 +273,5 @@ int launch_wgrad3_upwino(const vae_wgrad_args& a, hipStream_t st) {
   const int64_t nunits = wgrad3_upwino_units(g);
   dim3 grid((unsigned)((a.M / GCO) * (a.N / GCI) * a.nsplit), 1, 1);
   hipLaunchKernelGGL(wgrad3_upwino_kernel, grid, dim3(GNT), 0, st, a, g.Ws / 8, nunits);
-  return 0;
-}
-
-int launch_upwino_wgrad_reduce(const float* slab, int nsplit, int N, int M, float* dW, const float* bpart, float* db, hipStream_t st) {
-  const int tiles = (N / 32) * (M / 32);
-  const int extra = bpart ? (M + 255) / 256 : 0;
-  hipLaunchKernelGGL(upwino_wgrad_reduce_kernel, dim3((unsigned)(tiles + extra)), dim3(256), 0, st, slab, nsplit, N, M, dW, tiles, bpart, db);
   return 0;
 }

@@ -14,8 +14,9 @@
 //     The halves of G are left out (D' = G' dy G'^T with G' = [1 0; 1 1; 1 -1; 0 1]) and applied as exact power-of-two
 //     factors c_i c_j, c = (1, .5, .5, 1), by the reduction.
 //   * Split-K over unit ranges: a workgroup writes its 16 x 32 x 128 accumulators into a slab [split][16][Cin][Cout];
-//     wino_wgrad_reduce_kernel sums the slabs in fixed order (deterministic), applies A^T . A and writes OHWI through an LDS
-//     transpose; the bias gradient (column sums of dY) rides along as in the direct kernel.
+//     wgrad_wino_reduce_kernel<16> (igemm.hip, shared with the upsampler scheme) reads the slab once: it sums the splits in
+//     fixed order (deterministic), applies the factors and A^T . A and writes OHWI through an LDS transpose; the bias gradient
+//     (column sums of dY) rides along as in the direct kernel.
 // Numerics: measured against the direct kernel in tests/test_kernels_gpu.py (the transform-domain sums cancel in the output
 // transform, so the error is a few 1e-6 of the gradient scale instead of 1e-7; the parity bar is 1e-4).
 #include "common.h"
@@ -322,59 +323,6 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
   }
 }
 
-// dW[co][a][b][ci] = sum_{i,j} At[a][i] At[b][j] c_i c_j sum_split slab[split][i*4+j][ci][co]; 32 x 32 (ci, co) tile per workgroup,
-// read with lanes along co, written with lanes along ci.  Workgroups beyond the tiles reduce the bias-gradient slab.
-__global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const float* __restrict__ slab, int nsplit, int N, int M, float* __restrict__ dW,
-                                                                int tiles, const float* __restrict__ bpart, float* __restrict__ db) {
-  __shared__ float sT[9][32][33];
-  const int tid = threadIdx.x;
-  if ((int)blockIdx.x >= tiles) {
-    const int m = ((int)blockIdx.x - tiles) * 256 + tid;
-    if (m < M) {
-      float s = 0.f;
-      for (int k = 0; k < nsplit; ++k) s += bpart[(int64_t)k * M + m];
-      db[m] = s;
-    }
-    return;
-  }
-  const int tilesM = M / 32;
-  const int c0 = ((int)blockIdx.x / tilesM) * 32, m0 = ((int)blockIdx.x % tilesM) * 32;
-  const int64_t pstride = (int64_t)N * M, sstride = 16 * pstride;
-#pragma unroll 1
-  for (int r = 0; r < 4; ++r) {
-    const int cl = (tid >> 5) + 8 * r, ml = tid & 31;
-    const float* src = slab + (int64_t)(c0 + cl) * M + m0 + ml;
-    float mm[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      float s = 0.f;
-      for (int k = 0; k < nsplit; ++k) s += src[(int64_t)k * sstride + q * pstride];
-      const float ci = ((q >> 2) == 1 || (q >> 2) == 2) ? 0.5f : 1.f, cj = ((q & 3) == 1 || (q & 3) == 2) ? 0.5f : 1.f;
-      mm[q] = s * (ci * cj);
-    }
-    float h[3][4];  // A^T M
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      h[0][j] = (mm[0 * 4 + j] + mm[1 * 4 + j]) + mm[2 * 4 + j];
-      h[1][j] = mm[1 * 4 + j] - mm[2 * 4 + j];
-      h[2][j] = (mm[1 * 4 + j] + mm[2 * 4 + j]) - mm[3 * 4 + j];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      sT[a * 3 + 0][ml][cl] = (h[a][0] + h[a][1]) + h[a][2];
-      sT[a * 3 + 1][ml][cl] = h[a][1] - h[a][2];
-      sT[a * 3 + 2][ml][cl] = (h[a][1] + h[a][2]) - h[a][3];
-    }
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int r = 0; r < 4; ++r) {
-    const int ml = (tid >> 5) + 8 * r, cl = tid & 31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) dW[((int64_t)(m0 + ml) * 9 + t) * N + c0 + cl] = sT[t][ml][cl];
-  }
-}
-
 }  // namespace
 
 // plain 3x3 stride-1 pad-1 layer in fp32 with 16-pixel strips, 32 | Cin, 128 | Cout
@@ -399,12 +347,5 @@ int launch_wgrad3_wino(const vae_wgrad_args& a, hipStream_t st) {
   if (a.xf == VAE_XF_NONE) hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_NONE>, grid, dim3(GNT), 0, st, a, strips, nunits);
   else if (a.xf == VAE_XF_AFFINE) hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_AFFINE>, grid, dim3(GNT), 0, st, a, strips, nunits);
   else hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_AFFINE_SILU>, grid, dim3(GNT), 0, st, a, strips, nunits);
-  return 0;
-}
-
-int launch_wino_wgrad_reduce(const float* slab, int nsplit, int N, int M, float* dW, const float* bpart, float* db, hipStream_t st) {
-  const int tiles = (N / 32) * (M / 32);
-  const int extra = bpart ? (M + 255) / 256 : 0;
-  hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3((unsigned)(tiles + extra)), dim3(256), 0, st, slab, nsplit, N, M, dW, tiles, bpart, db);
   return 0;
 }

@@ -768,9 +768,8 @@ def _wgrad_wino(a: WgradArgs, gv: torch.Tensor, bgrad_out: Optional[torch.Tensor
         _timed("wgrad3_upwino_kernel", fl, fl * 0.25, "vae_wgrad_wino", C.byref(a), _stream())
     else:
         _timed(f"wgrad3_wino_kernel<{a.xf}>", fl, fl * WINO_EXECUTED, "vae_wgrad_wino", C.byref(a), _stream())
-    scratch = torch.empty((npos * a.N * a.M,), device=dev, dtype=torch.float32) if ns > 1 else None
     _timed("wgrad_wino_reduce (split sum + output transform)", 0.0, 0.0, "vae_wgrad_wino_reduce", _p(slab), ns, npos, a.N, a.M,
-           _p(scratch), _p(gv), _p(bpart), _p(bgrad_out), _stream())
+           None, _p(gv), _p(bpart), _p(bgrad_out), _stream())  # (no scratch buffer: the reduction reads the slab once)
     return True
 
 
