@@ -23,6 +23,9 @@
 #ifndef VAE_ABLATE
 #define VAE_ABLATE 0  // diagnostic builds (tools/ablation_builds.sh, wrong results): bit 0 no global loads, 1 no LDS stores, 4 no barrier
 #endif
+#ifndef VAE_WGRAD_DEFER
+#define VAE_WGRAD_DEFER 2  // channel blocks (of 4) whose MFMAs waves 4..7 issue one step late; 0: all eight waves run one program
+#endif
 #include <algorithm>
 #include <type_traits>
 
@@ -67,6 +70,20 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
   const int nu = (int)max((int64_t)0, uend - ubeg);
   const int upi = (g.Ho / 2) * strips;  // units per image
   const bool do_bias = (p.bias_partial != nullptr) && tn == 0;
+#ifdef VAE_WGRAD_TIMING  // debug build (tools/wgrad_timing.py): shader-clock stamps of waves 0 and 4 (the two waves of SIMD 0) of workgroups 0..7 -> p.out,
+  // which this kernel otherwise never touches: [workgroup][wave / 4][4 + TSN * 5] uint64 = entry, loop exit, 100 MHz clock at both; per step TS0.. :
+  // begin (barrier released), deferred MFMAs issued, operands built (first own MFMA), last MFMA issued, barrier reached
+  constexpr int TS0 = 2, TSN = 8;
+  const bool tw = (tid & 255) == 0 && blockIdx.x < 8 && p.out != nullptr;
+  unsigned long long* const tout = reinterpret_cast<unsigned long long*>(p.out) + (blockIdx.x * 2 + (tid >> 8)) * (4 + TSN * 5);
+  unsigned long long tst[5];
+  const unsigned long long te0 = __builtin_amdgcn_s_memtime(), tr0 = __builtin_amdgcn_s_memrealtime();
+#define GSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); tst[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define GSTAMPS_OUT(k) do { if (tw && (k) >= TS0 && (k) < TS0 + TSN) { _Pragma("unroll") for (int i_ = 0; i_ < 5; ++i_) tout[4 + ((k) - TS0) * 5 + i_] = tst[i_]; } } while (0)
+#else
+#define GSTAMP(i) do { } while (0)
+#define GSTAMPS_OUT(k) do { } while (0)
+#endif
 
   // ---- staging roles.  X halo: thread -> (row xr, channel quad xq, column xx) of the 4 x 16 main block, threads with
   // (tid & 8) == 0 && tid < 128 also one element of the two extra columns (same channel quad: shared GroupNorm rows).
@@ -184,10 +201,37 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
     constexpr int wic = decltype(WI)::value, jhc = decltype(JH)::value;
     constexpr bool two = wic == 1 || wic == 2;  // D' row i combines both dY rows
     constexpr bool vplus = wic == 1;            // sign of the second row in the combinations (V: B^T row i, D': G' row i)
+    // The two waves of a SIMD (w and w + 4) run the same program between the same barriers and would build their operands at
+    // the same time, the matrix pipe idle in both.  Waves 4..7 (wic >= 2) therefore hold the MFMAs of a step's last `ndef`
+    // channel blocks back: the operands (a4 and the bb the step ends with) stay in registers across the barrier and the
+    // MFMAs open the NEXT step, in front of its LDS reads, while the partner builds.  Every accumulator still receives the
+    // same products in the same order (units ascending, e = 0..3): the sums do not change by a bit.
+    constexpr int ndef = wic >= 2 ? VAE_WGRAD_DEFER : 0;
+    static_assert(ndef >= 0 && ndef <= 2, "bb holds the operands of two channel blocks");
+    f32x4 a4[2], bb[2][2];  // V fragments of the two positions; D' operands of channel blocks nb (bb[nb & 1])
+    if (ndef > 0) {  // (the first step's held-back MFMAs add 0 * 0 to accumulators that are +0)
+      a4[0] = a4[1] = z4;
+      bb[0][0] = bb[0][1] = bb[1][0] = bb[1][1] = z4;
+    }
+    auto held_back = [&]() {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int nb = 4 - ndef; nb < 4; ++nb)
+#pragma unroll
+          for (int pi = 0; pi < 2; ++pi) acc[pi][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[pi][e], bb[nb & 1][pi][e], acc[pi][nb], 0, 0, 0);
+    };
     auto step = [&](int k, const Stg& cur, Stg& nxt) {  // cur: unit k+1 (requested during step k-1); nxt receives unit k+2
       const float* cx = smem + (k & 1) * GSTAGE;
       const float* cy = cx + SXF;
       float* nst = smem + ((k + 1) & 1) * GSTAGE;
+      GSTAMP(0);
+      if (ndef > 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        held_back();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      GSTAMP(1);
       // D' operands: raw dY rows of channel block nb -> b4 of the two positions.  The operands of block nb+1 are formed and
       // the rows of block nb+2 requested WHILE the MFMAs of block nb issue (interleaved below): the two waves of a SIMD
       // take turns on the matrix pipe and so drift into the same phase -- operand building in a phase of its own would leave
@@ -219,7 +263,6 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
         }
       };
       // V fragments of the two positions: 12 x values of the two rows, combined
-      f32x4 a4[2], bb[2][2];
       {
         f32x4 u1[3], u2[3];
 #pragma unroll
@@ -248,6 +291,7 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
         read_d(1, rd);
       }
       if (!(VAE_ABLATE & 2) && wave < 4) store_unit(nst, cur);  // the two waves of a SIMD store at opposite ends of the step
+      GSTAMP(2);
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
         __builtin_amdgcn_sched_barrier(0);
@@ -262,19 +306,24 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
         }
         if (nb < 3) build_b(rd, bb[(nb + 1) & 1]);  // block nb+1's operands, during the first half of this block's MFMAs
         if (nb < 2) read_d(nb + 2, rd);             // block nb+2's rows into the same registers, during the second half
+        if (nb < 4 - ndef) {  // (a held-back block: its operands are built here, its MFMAs open the next step)
 #pragma unroll
-        for (int pi = 0; pi < 2; ++pi)
+          for (int pi = 0; pi < 2; ++pi)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[pi][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[pi][e], bb[nb & 1][pi][e], acc[pi][nb], 0, 0, 0);
+            for (int e = 0; e < 4; ++e) acc[pi][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[pi][e], bb[nb & 1][pi][e], acc[pi][nb], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
+          for (int i = 0; i < 4; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
+          }
+          __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // DS read
+          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // DS read
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         __builtin_amdgcn_sched_barrier(0);
+        if (nb == 3 - ndef) GSTAMP(3);
       }
+      GSTAMP(4);
+      GSTAMPS_OUT(k);
       if (!(VAE_ABLATE & 16)) __syncthreads();
     };
     int k = 0;
@@ -283,6 +332,7 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
       step(k + 1, s0, s1);
     }
     if (k < nu) step(k, s1, s0);
+    if (ndef > 0 && nu > 0) held_back();  // the last step's (a split without units has none and writes its zero slab)
   };
   {
     using J0 = std::integral_constant<int, 0>;
@@ -299,6 +349,14 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
     }
   }
 
+#ifdef VAE_WGRAD_TIMING
+  if (tw) {
+    tout[0] = te0;
+    tout[1] = __builtin_amdgcn_s_memtime();
+    tout[2] = tr0;
+    tout[3] = __builtin_amdgcn_s_memrealtime();
+  }
+#endif
   // ---- epilogue: slab [split][16 positions][Cin][Cout]; lanes along co (128-byte rows) ----
   float* __restrict__ O = p.partial + (int64_t)split * 16 * p.N * p.M;
 #pragma unroll
