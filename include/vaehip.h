@@ -382,8 +382,9 @@ int vae_preprocess_u8(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32
 int vae_sqnorm(const float* g, int64_t n, float* ws, int32_t nblk, float* out, void* stream);
 /* clip coefficient min(1, max_norm/(sqrt(*sqnorm)+1e-6)) is read from device memory
  * (max_norm <= 0 disables clipping) then torch.optim.AdamW math, one pass over p,g,m,v */
+/* the hyper-parameters are doubles, as torch holds them: 1 - beta2 and the bias corrections of the float 0.999f are 1.3e-5 off */
 int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm,
-              float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+              float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
               int32_t step, void* stream);
 /* dead-weight scan (deadneuron.py:78-115): per segment, the count of |w| < thr and the sum of |w|.
  * seg_off [nseg][2] = {begin,end} element offsets into w (segments need not be adjacent).  The segments are scanned in

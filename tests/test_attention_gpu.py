@@ -3,9 +3,15 @@ width 512, no T x T tensor.  Parity: fp32 against a float64 restatement of oracl
 softmax / context arithmetic (1e-4 relative, north_star's fp32 bar) at T = 1024 and 4096, and against the oracle MODULE
 itself (GroupNorm + linears + residual, forward and every gradient); bf16 against the same arithmetic on bf16-rounded
 operands (P and dS are rounded to bf16 for the second product: 2^-9 relative per element); and the engine's two
-attention paths (materialised scores vs blockwise) against each other."""
+attention paths (materialised scores vs blockwise) against each other.  The same bars at the edges of the online softmax
+(tests/streaming_refs.py:attn_inputs): the row maximum in the first or the last streamed block, one-hot rows, scores past
+fp32 exp overflow, exactly uniform rows, at 1, 3 and 9 row blocks in both precisions."""
+import math
+
 import pytest
 import torch
+
+import streaming_refs as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +67,7 @@ def test_attention_bf16_matches_reference_on_rounded_operands(cuda, B, T):
     ro, rl, rq, rk, rv = _ref(rb(q), rb(k), rb(v), rb(do), scale)
     assert _rel(saved[3], rl) < 1e-5          # scores: exact products of the rounded operands, fp32 sums
     assert _rel(o, ro) < 4e-3                  # P rounded to bf16 for P.V
-    # D = rowsum(dO * O) uses the fp32 dO and the kernel's O, the reference the rounded dO: 1e-2 covers both roundings
+    # P and dS are rounded to bf16 for the second products, D = rowsum(bf16(dO) * O) takes the kernel's O: 1e-2 covers them
     assert _rel(dv, rv) < 1e-2 and _rel(dq, rq) < 1e-2 and _rel(dk, rk) < 1e-2
 
 
@@ -149,3 +155,43 @@ def test_engine_blockwise_path_equals_materialised_path(cuda, mode, tol):
     assert float((s1 - s0).abs().max() / s0.abs().max()) < tol
     assert float((g1.double() - g0.double()).norm() / g0.double().norm()) < 10 * tol
     assert not torch.equal(g0, g1)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("T", sr.ATTN_T)
+@pytest.mark.parametrize("case", sr.ATTN_CASES)
+def test_attention_online_softmax_edges(cuda, case, T, mode):
+    """B = 2, T = 64 x {1, 3, 9}; the bars of the tests above (fp32 1e-4, log-sum-exp 1e-5; bf16 on rounded operands 4e-3 / 1e-2).
+    plain: bf16 at T = 64 and 192 had no test.  Planted maximum: in the first streamed block alpha == 1 ever after, in the last
+    one everything accumulated before is rescaled by about e^-g; g = 40 makes P one-hot, so dq and dk are about 0 and their
+    error is measured against max |dq|, max |dk| of the plain case at the same T.  shift: log-sum-exp 87 .. 120, where only the
+    max subtraction and the saved log-sum-exp keep forward and backward finite.  uniform: a zero query's log-sum-exp is log T
+    (1e-6: two ulp of the fp32 result at T = 576) and its output the mean of v."""
+    from vaehip import ops
+    bf = mode == "bf16"
+    (q, k, v, do), (ro, rl, rq, rk, rv, _) = sr.attn_case(case, T, bf)
+    with ops.precision(ops.PREC_BF16 if bf else ops.PREC_F32):
+        o, saved = ops.attn_fwd(q.cuda(), k.cuda(), v.cuda(), sr.ATTN_SCALE)
+        dq, dk, dv = ops.attn_bwd(saved, o, do.cuda(), sr.ATTN_SCALE)
+    torch.cuda.synchronize()
+    assert saved[0].dtype == (torch.bfloat16 if bf else torch.float32)
+    for t in (o, saved[3], dq, dk, dv):
+        assert bool(torch.isfinite(t).all())
+    key = f"{case},T={T},{mode}"
+    tol_o, tol_g = (4e-3, 1e-2) if bf else (1e-4, 1e-4)
+    sr.check("attention_edges", f"{key},lse", _rel(saved[3], rl), 1e-5)
+    sr.check("attention_edges", f"{key},o", _rel(o, ro), tol_o)
+    sr.check("attention_edges", f"{key},dv", _rel(dv, rv), tol_g)
+    if case.endswith("_g40"):
+        base = sr.attn_case("plain", T, bf)[1]
+        sr.check("attention_edges", f"{key},dq_vs_plain_max", sr.rel_to(dq, rq, float(base[2].abs().max())), tol_g)
+        sr.check("attention_edges", f"{key},dk_vs_plain_max", sr.rel_to(dk, rk, float(base[3].abs().max())), tol_g)
+    else:
+        sr.check("attention_edges", f"{key},dq", _rel(dq, rq), tol_g)
+        sr.check("attention_edges", f"{key},dk", _rel(dk, rk), tol_g)
+    if case == "uniform":
+        lse0 = saved[3][:, ::7].double().cpu()
+        sr.check("attention_edges", f"{key},lse_of_zero_query_minus_logT", float((lse0 - math.log(T)).abs().max()), 1e-6, strict=False)
+        vm = (sr.r16(v) if bf else v).double().mean(1, keepdim=True)
+        sr.check("attention_edges", f"{key},o_of_zero_query_vs_mean_v",
+                 float((o[:, ::7].double().cpu() - vm).abs().max() / vm.abs().max()), tol_o)

@@ -243,12 +243,15 @@ def test_standalone_submodule_calls(pair):
         assert _rel(g, o.vae.encoder.down_blocks[0].resnets[0].norm1(t)) < 1e-5
 
 
-def test_bf16_compute_mode_tracks_fp32(pair):
+# (40,1) and (48,3): ragged maps on the flat kernels, attention over 25 / 36 tokens -- in bf16 mode T = 25 puts the two GEMM
+# forms that contract over T on the unvectorised fp32 kernel, T = 36 runs the bf16 kernel with a K tail of 4
+@pytest.mark.parametrize("R,B", [(64, 2), (40, 1), (48, 3)])
+def test_bf16_compute_mode_tracks_fp32(pair, R, B):
     """training.mixed_precision: bf16 -- bf16 MFMA products with fp32 accumulation, fp32 tensors and statistics.
     Tolerance is the arithmetic's (bf16 has 8 significant bits): losses 2e-2, gradient direction cosine > 0.99."""
     import vae_oracle as vo
     o, w = pair
-    R, B, klw = 64, 2, 1e-4
+    klw = 1e-4
     x, eps = vo.synthetic_pixels(B, R, 42, 5).cuda(), vo.synthetic_eps(B, R, 42, 5).cuda()
     eng = w.vae.engine
     names = ["encoder.down_blocks.0.resnets.0.norm1", "decoder.up_blocks.1.resnets.0.norm1"]
@@ -266,8 +269,10 @@ def test_bf16_compute_mode_tracks_fp32(pair):
     assert float((res["bf16"] - res["no"]).abs().max() / res["no"].abs().max()) < 2e-2
     assert not torch.equal(res["bf16"], res["no"])  # the bf16 kernels really ran
     cos = torch.nn.functional.cosine_similarity(grads["bf16"].double(), grads["no"].double(), dim=0)
-    assert float(cos) > 0.99, float(cos)
     gn = grads["bf16"].norm() / grads["no"].norm()
+    _record("bf16_tracks_fp32", f"R={R},B={B}", {"scalars_rel": float((res["bf16"] - res["no"]).abs().max() / res["no"].abs().max()),
+                                                "grad_cosine": float(cos), "grad_norm_ratio": float(gn)})
+    assert float(cos) > 0.99, float(cos)
     assert 0.97 < float(gn) < 1.03
     for n in names:
         assert float(((stats["bf16"][n] - stats["no"][n]).abs() / stats["no"][n]).max()) < 2e-2

@@ -303,7 +303,10 @@ __global__ __launch_bounds__(AttnShape<BF>::NT, 1) void attn_kernel(AttnArgs p) 
   if (ROLE == ROLE_FWD && dw == 0 && lh == 0) p.lse_out[(int64_t)b * T + r0 + lr] = st_m + __logf(st_l);
 }
 
-// D[b][t] = sum_d dO[b][t][d] * O[b][t][d]  (one wave per row)
+// D[b][t] = sum_d dO[b][t][d] * O[b][t][d]  (one wave per row).  BF: dO rounded to bf16 as the dP products read it -- with the fp32
+// dO, dP - D keeps (dO - bf16(dO)) . O, the rows of dS no longer sum to zero and a component common to all keys (or a
+// one-hot row's large query) carries that residue into dQ / dK
+template <bool BF>
 __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float* __restrict__ a, const float* __restrict__ bb, int64_t rows,
                                                           float* __restrict__ out) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -314,7 +317,12 @@ __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float* __restric
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const f32x4 x = pa[lane + 64 * i], y = pb[lane + 64 * i];
+    f32x4 x = pa[lane + 64 * i];
+    const f32x4 y = pb[lane + 64 * i];
+    if constexpr (BF) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = (float)(__bf16)x[e];
+    }
     s += (x[0] * y[0] + x[1] * y[1]) + (x[2] * y[2] + x[3] * y[3]);
   }
   s = wave_sum(s);
@@ -364,8 +372,9 @@ extern "C" int vae_attn_bwd(const void* q, const void* k, const void* v, const v
   VAE_CHECK((size_t)T * HD * 4u < BUF_MAX, "vae_attn_bwd: one image exceeds a buffer descriptor");
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * T;
-  hipLaunchKernelGGL(attn_rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, do32, o32, rows, dsum);
   const bool bf = prec == VAE_PREC_BF16;
+  if (bf) hipLaunchKernelGGL(attn_rowdot_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, do32, o32, rows, dsum);
+  else hipLaunchKernelGGL(attn_rowdot_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, do32, o32, rows, dsum);
   AttnArgs a{};
   a.T = T; a.scale = scale; a.lse = lse; a.dsum = dsum;
   int rc;

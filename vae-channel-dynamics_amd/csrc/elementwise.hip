@@ -559,23 +559,23 @@ extern "C" int vae_sqnorm(const float* g, int64_t n, float* ws, int32_t nblk, fl
   return VAE_OK;
 }
 
-extern "C" int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm, float max_norm, float lr,
-                         float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream) {
+extern "C" int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm, float max_norm, double lr,
+                         double beta1, double beta2, double eps, double weight_decay, int32_t step, void* stream) {
   VAE_CHECK(p && g && m && v && n > 0 && step >= 1, "adamw: bad args");
   VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "adamw: clipping needs sqnorm");
   VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: unaligned");
   // scalar prep exactly as torch.optim.adamw._single_tensor_adamw (python doubles)
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   AdamArgs a;
   a.max_norm = max_norm;
-  a.decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  a.omb1 = (float)(1.0 - (double)beta1);
-  a.beta2 = beta2;
-  a.omb2 = (float)(1.0 - (double)beta2);
-  a.step_size = (float)((double)lr / bc1);
+  a.decay = (float)(1.0 - lr * weight_decay);
+  a.omb1 = (float)(1.0 - beta1);
+  a.beta2 = (float)beta2;
+  a.omb2 = (float)(1.0 - beta2);
+  a.step_size = (float)(lr / bc1);
   a.bc2_sqrt = (float)sqrt(bc2);
-  a.eps = eps;
+  a.eps = (float)eps;
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a);
   VAE_LAUNCH_CHECK("adamw");
   return VAE_OK;
