@@ -27,6 +27,13 @@
 #include <type_traits>
 #include <algorithm>
 
+// VAE_UPW_PRIO 1 (default): in the dgrad instantiation waves 4..7 (the second-dispatched wave of every SIMD, which multiplies first
+// and stages behind it) run the loop at s_setprio 1.  Measured per instantiation and wave half (tools/wino_seat_ab.py,
+// profiles/wino4_seat_measured.json): the dgrad 1.4-1.8 % faster, the forward 0.5-1.0 % slower with it, waves 0..3 no difference.
+#ifndef VAE_UPW_PRIO
+#define VAE_UPW_PRIO 1
+#endif
+
 namespace {
 
 constexpr int UTH = 4, UTW = 8;            // low-resolution pixels (= Winograd tiles) per workgroup tile
@@ -254,8 +261,14 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
     }
     if (s < nsteps) step(s, 0, first_c);
   };
+#if VAE_UPW_PRIO  // one static s_setprio around the loop; a scalar condition: the instruction ignores EXEC
+  if (DG && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
+#endif
   if (wave < 4) run(std::true_type{});  // uniform per wave
   else run(std::false_type{});
+#if VAE_UPW_PRIO
+  if (DG) __builtin_amdgcn_s_setprio(0);
+#endif
 
   // ---- epilogue: per 32-channel block, M through LDS, then the output transform ----
   float* const sM = wsm;  // [9][32 tiles][UMLD], over the V / halo buffers (the last step's barrier has passed)

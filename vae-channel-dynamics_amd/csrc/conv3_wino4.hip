@@ -28,7 +28,9 @@
 //     behind the following group.  One barrier per step; one copy of the step loop per row pair (uniform per wave).
 //   * What a step still costs (tools/wino4_timing.py, profiles/r04_pmc_wino4.txt): 6300 cycles.  An fp32 MFMA runs at the fp32
 //     vector rate and vector instructions cost matrix-pipe time one for one: 64 x 72 MFMAs + 4 x 3 x 63 vector instructions per
-//     SIMD = 5364, barrier and first-fragment latency the rest.  Prologue + epilogue (one workgroup per CU: nothing beside them)
+//     SIMD = 5364, barrier and first-fragment latency the rest.  The pole is the youngest wave group (waves 8-11, row pair {0,5}:
+//     36 patch values per step against 24); seating that pair on the oldest waves, a static s_setprio for it and the halo DMA
+//     behind the first MFMA group were all measured and lost (profiles/wino4_seat_measured.json).  Prologue + epilogue (one workgroup per CU: nothing beside them)
 //     are 43k cycles per tile: 30 % of a 128-channel layer's workgroup, 9 % of a 512-channel one.
 //   * Epilogue per 32-channel block: accumulators through LDS ([36][32 tiles][32 channels]), each thread takes A^T M A of its (tile,
 //     channel) pairs, adds bias / residual, writes the 4x4 outputs (lanes along channels: 128-byte rows) and leaves the
@@ -36,6 +38,14 @@
 #include "common.h"
 #include <type_traits>
 #include <algorithm>
+
+// VAE_W4_SWAVE 1 (default): the wave index behind the DMA destination and the U-fragment offsets is taken through readfirstlane,
+// so hipcc keeps them in scalar registers: per step a 64-bit multiply-add, a multiply and a readfirstlane leave the vector pipe, where
+// they cost matrix-pipe time and sat in front of the step's first fragment re-request.  0 = the index from threadIdx.x as it is
+// (same bits; tools/wino_seat_ab.py: the kernel 1.5-2.9 % slower on the step's layers, profiles/wino4_seat_measured.json).
+#ifndef VAE_W4_SWAVE
+#define VAE_W4_SWAVE 1
+#endif
 
 namespace {
 
@@ -126,12 +136,19 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   float* const sH = wsm;            // [2][FSH]: the chunk's input halo (first: the LDS-DMA base stays below 64 KB)
   float* const sV = wsm + 2 * FSH;  // [2][FSV]
 #ifdef VAE_WINO4_TIMING  // debug build (tools/wino4_timing.py): shader-clock stamps of waves 0, 4, 8 (the three waves of SIMD 0) of workgroups 0..7 -> p.track
-  unsigned long long tE[10];  // entry, loop entry, loop exit, block 0: accumulators in LDS / outputs stored, block 1: the same, end; [8], [9]: 100 MHz clock
-  unsigned long long tS[8][4];  // steps 2..9: begin, after the first phase, after the second, after the barrier
-  const bool tw = (threadIdx.x & 255) == 0;
-#define WEDGE(k) do { if (tw) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tE[k] = __builtin_amdgcn_s_memtime(); } } while (0)
-#define WSTAMP(s, k) do { if (tw && (s) >= 2 && (s) < 10) { tS[(s) - 2][k] = __builtin_amdgcn_s_memtime(); } } while (0)
-  if (tw) tE[8] = __builtin_amdgcn_s_memrealtime();
+  // The kernel has no register to spare: stamps kept in vector registers spilled 860 of them, and an array indexed by the step (a
+  // run-time value) goes to scratch memory, whose stores count in vmcnt beside the loop's counted waits -- that build ran 17-19k
+  // cycles per step instead of 6.3k.  So the loop's stamps are SCALAR: every wave sums the four phases of steps 2..9 in scalar
+  // registers (32-bit clock differences) and the edges go to 240 B of LDS beside the kernel's image.
+  __shared__ unsigned long long tE[3][10];  // entry, loop entry, loop exit, block 0: accumulators in LDS / outputs stored, block 1: the same, end; [8], [9]: 100 MHz clock
+  unsigned sP[4] = {0u, 0u, 0u, 0u};  // sums over steps 2..9: begin -> first phase -> second phase -> arrival at the barrier -> behind the barrier
+  unsigned sT = 0u, sFirst = 0u, sLast = 0u, sN = 0u;
+#define W4_TW ((threadIdx.x & 255) == 0)
+#define WEDGE(k) do { if (W4_TW) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tE[threadIdx.x >> 8][k] = __builtin_amdgcn_s_memtime(); } } while (0)
+#define WSTAMP(s, k) do { if ((s) >= 2 && (s) < 10) { const unsigned t_ = (unsigned)__builtin_amdgcn_s_memtime(); \
+    if ((k) == 0) { if (sN == 0u) sFirst = t_; } else sP[(k) == 4 ? 2 : (k) == 3 ? 3 : (k) - 1] += t_ - sT; \
+    if ((k) == 3) { sLast = t_; ++sN; } sT = t_; } } while (0)
+  if (W4_TW) tE[threadIdx.x >> 8][8] = __builtin_amdgcn_s_memrealtime();
 #else
 #define WEDGE(k) do { } while (0)
 #define WSTAMP(s, k) do { } while (0)
@@ -139,6 +156,8 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   WEDGE(0);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (XF == NONE only: the register-staged instantiations compile as they did)
+  const int uwave = (VAE_W4_SWAVE && XF == VAE_XF_NONE) ? __builtin_amdgcn_readfirstlane(tid) >> 6 : wave;
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = p.N / FBN;
@@ -202,7 +221,7 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   // LDS-DMA in flight it waits vmcnt(0) at the next use of ANY load, which would serialise the U-fragment pipeline below.  They
   // are the OLDEST vector-memory operations of a step (6 fragment re-requests follow), so `s_waitcnt vmcnt(6)` in front of the
   // step's barrier retires them; beyond the last chunk the last one is requested again (never read) so the count stays fixed.
-  const unsigned lds_h = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)sH) + (unsigned)wave * 2048u;
+  const unsigned lds_h = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)sH) + (unsigned)uwave * 2048u;
   auto dma_halo = [&](int step, int par) {
     const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(min(step, nsteps - 1) * FBK * 4));
 #pragma unroll
@@ -306,7 +325,7 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   const unsigned bpos = (unsigned)p.N * 32u;  // bytes per position of the U image
   f32x4 bq[6];
   auto load_b1 = [&](int step, int i) {
-    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(min(step, nsteps - 1) * FPOS + 3 * wave) * bpos);
+    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(min(step, nsteps - 1) * FPOS + 3 * uwave) * bpos);
     bq[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsU, bvo + (i & 1) * 1024u, so + (i >> 1) * bpos, 0));
   };
 
@@ -412,6 +431,7 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
       }
       group(a2, s, std::integral_constant<int, 5>{});
       if (XF == VAE_XF_NONE) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // this step's DMA (older than the 6 re-requests) has landed
+      WSTAMP(s, 4);
       __syncthreads();
       WSTAMP(s, 3);
     };
@@ -570,15 +590,17 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   }
 #ifdef VAE_WINO4_TIMING
   WEDGE(7);
-  if (tw) {
+  if (W4_TW) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    tE[9] = __builtin_amdgcn_s_memrealtime();
-    if (p.track && blockIdx.x < 8) {  // [workgroup][wave group][10 + 32] uint64
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.track) + (blockIdx.x * 3 + (threadIdx.x >> 8)) * 42;
+    tE[threadIdx.x >> 8][9] = __builtin_amdgcn_s_memrealtime();
+    if (p.track && blockIdx.x < 8) {  // [workgroup][wave group][10 edges + 4 phase sums + span + steps] uint64
+      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.track) + (blockIdx.x * 3 + (threadIdx.x >> 8)) * 16;
 #pragma unroll
-      for (int i = 0; i < 10; ++i) o[i] = tE[i];
+      for (int i = 0; i < 10; ++i) o[i] = tE[threadIdx.x >> 8][i];
 #pragma unroll
-      for (int i = 0; i < 32; ++i) o[10 + i] = tS[i >> 2][i & 3];
+      for (int i = 0; i < 4; ++i) o[10 + i] = sP[i];
+      o[14] = sLast - sFirst;
+      o[15] = sN;
     }
   }
 #endif

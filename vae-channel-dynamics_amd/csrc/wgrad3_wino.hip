@@ -26,6 +26,9 @@
 #ifndef VAE_WGRAD_DEFER
 #define VAE_WGRAD_DEFER 2  // channel blocks (of 4) whose MFMAs waves 4..7 issue one step late; 0: all eight waves run one program
 #endif
+#ifndef VAE_WGRAD_PRIO
+#define VAE_WGRAD_PRIO 1  // 1: waves 4..7 (the second-dispatched wave of every SIMD, which loses the issue arbitration to its partner) run the loop at s_setprio 1; 0: no priority
+#endif
 #include <algorithm>
 #include <type_traits>
 
@@ -334,6 +337,9 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
     if (k < nu) step(k, s1, s0);
     if (ndef > 0 && nu > 0) held_back();  // the last step's (a split without units has none and writes its zero slab)
   };
+#if VAE_WGRAD_PRIO  // one static s_setprio around the loop, no flips inside; a scalar condition: the instruction ignores EXEC
+  if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
+#endif
   {
     using J0 = std::integral_constant<int, 0>;
     using J1 = std::integral_constant<int, 1>;
@@ -348,6 +354,9 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
       default: run(std::integral_constant<int, 3>{}, J1{}); break;
     }
   }
+#if VAE_WGRAD_PRIO
+  __builtin_amdgcn_s_setprio(0);
+#endif
 
 #ifdef VAE_WGRAD_TIMING
   if (tw) {
