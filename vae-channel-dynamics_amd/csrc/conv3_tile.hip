@@ -9,7 +9,7 @@
 // shifted offset.  Wave (wm, wn) owns output row wm of the tile (32 consecutive pixels = one conflict-free
 // ds_read_b128 fragment per k-group) and 64 channels.  Compared with the flat implicit GEMM
 // (igemm.hip) this removes 8/9 of the activation loads, address arithmetic and transforms.
-#include "common.h"
+#include "wino_common.h"  // (gstat_merge: the fixed-order merge of the epilogue's moments, shared with the Winograd kernels)
 #include <algorithm>
 
 namespace {
@@ -258,9 +258,7 @@ __global__ __launch_bounds__(NT) void conv3_tile_kernel(vae_igemm_args p, int ti
     __syncthreads();
     if (tid < gpt) {  // the 4 rows of the tile, fixed order; each holds 32 pixels x cpg channels
       const float nrow = 32.f * (float)cpg;
-      MeanM2 a{red2[tid * 2], red2[tid * 2 + 1]};
-#pragma unroll
-      for (int rr = 1; rr < 4; ++rr) a = mm2_merge(a, nrow * (float)rr, MeanM2{red2[(rr * gpt + tid) * 2], red2[(rr * gpt + tid) * 2 + 1]}, nrow);
+      const MeanM2 a = wino::gstat_merge<4>(red2, gpt, tid, [&](int) { return nrow; });
       float* o = p.gstat + (((int64_t)b * (tiles_x * tiles_y) + ty * tiles_x + tx) * p.gstat_groups + n0 / cpg + tid) * 2;
       o[0] = a.m;
       o[1] = a.M2;

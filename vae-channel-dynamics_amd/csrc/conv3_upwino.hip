@@ -16,14 +16,16 @@
 //     Bt3 = [1 0 -1 0; 0 1 1 0; 0 1 0 -1]     s = [1 1 -1]
 // Neither the upsampled tensor nor the high-resolution input gradient ever exists.
 //
-// Kernel: as conv3_wino.hip (transformed weights U = G' g G'^T rebuilt from the live weights per launch, layout [K/8][9][N][8];
-// chunk of 8 channels per step; the chunk's halo staged once, the V image [9][32 tiles][8] double buffered in LDS; U fragments
-// from L2 straight into registers one step ahead; accumulators through LDS in the epilogue).  Workgroup = 8 waves = 32
-// low-resolution pixels (4 x 8) x 64 channels: wave w owns position w (both 32-channel blocks) and the NINTH position is split
-// by channel block over two waves on different SIMDs (waves 0, 1 in even workgroups, 2, 3 in odd ones: wave k of a workgroup runs on
-// SIMD k % 4), so a workgroup loads the SIMDs 20 20 16 16 MFMAs per step and two co-resident workgroups 36 each.  (A first
-// version with one position per wave and 9 waves put three waves of every workgroup on SIMD 0: 0.46 of the matrix peak.)
-#include "common.h"
+// Kernel: the scheme of conv3_wino.hip (transformed weights U = G' g G'^T rebuilt from the live weights per launch, layout
+// [K/8][9][N][8]; chunk of 8 channels per step; the chunk's halo staged once, the V image [9][32 tiles][8] double buffered in
+// LDS; U fragments from L2 straight into registers one step ahead; accumulators through LDS in the epilogue), sharing with it
+// by name (wino_common.h) tile_of_workgroup / xcd_spatial, the U layout (u_gather, u_out, u_frag, u_bytes), spill_acc and the
+// eligibility preamble.  Workgroup = 8 waves = 32 low-resolution pixels (4 x 8) x 64 channels: wave w owns position w (both
+// 32-channel blocks) and the NINTH position is split by channel block over two waves on different SIMDs (waves 0, 1 in even
+// workgroups, 2, 3 in odd ones: wave k of a workgroup runs on SIMD k % 4), so a workgroup loads the SIMDs 20 20 16 16 MFMAs per
+// step and two co-resident workgroups 36 each.  (A first version with one position per wave and 9 waves put three waves of
+// every workgroup on SIMD 0: 0.46 of the matrix peak.)
+#include "wino_common.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -38,6 +40,7 @@ namespace {
 
 constexpr int UTH = 4, UTW = 8;            // low-resolution pixels (= Winograd tiles) per workgroup tile
 constexpr int UTL = UTH * UTW;             // 32
+static_assert(UTL == wino::TILES, "spill_acc");
 constexpr int UBK = 8;                     // channels per step
 constexpr int NPOS = 9;
 constexpr int UNT = 512;                   // 8 waves
@@ -58,13 +61,7 @@ __global__ __launch_bounds__(256) void upwino_weights_kernel(const float* __rest
   if (i >= (int64_t)N * K) return;
   const int k = (int)(i % K), n = (int)(i / K);
   float g[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int tap = dgrad ? (2 - a) * 3 + (2 - b) : a * 3 + b;
-      g[a][b] = W[(int64_t)n * sn + (int64_t)k * sk + (int64_t)tap * st];
-    }
+  wino::u_gather(W, n, k, dgrad, sn, sk, st, g);
   float t[3][3];
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
@@ -72,12 +69,12 @@ __global__ __launch_bounds__(256) void upwino_weights_kernel(const float* __rest
     t[1][b] = (g[0][b] + g[2][b]) + g[1][b];
     t[2][b] = g[2][b];
   }
-  float* o = U + ((int64_t)(k >> 3) * NPOS * N + n) * 8 + (k & 7);
+  float* o = wino::u_out<NPOS>(U, N, n, k);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    o[(int64_t)(a * 3 + 0) * N * 8] = t[a][0];
-    o[(int64_t)(a * 3 + 1) * N * 8] = (t[a][0] + t[a][2]) + t[a][1];
-    o[(int64_t)(a * 3 + 2) * N * 8] = t[a][2];
+    wino::u_at(o, N, a * 3 + 0) = t[a][0];
+    wino::u_at(o, N, a * 3 + 1) = (t[a][0] + t[a][2]) + t[a][1];
+    wino::u_at(o, N, a * 3 + 2) = t[a][2];
   }
 }
 
@@ -98,18 +95,9 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = (p.N + WBN - 1) / WBN;
-  int t = blockIdx.x, tn;
-  if (xcd_sp) {  // the channel blocks of a spatial tile on one XCD (see conv3_wino.hip)
-    tn = (t >> 3) % tilesN;
-    t = ((t >> 3) / tilesN) * 8 + (t & 7);
-  } else {
-    tn = t % tilesN;
-    t /= tilesN;
-  }
-  const int tx = t % tiles_x; t /= tiles_x;
-  const int ty = t % tiles_y;
-  const int b = t / tiles_y;
-  const int y0 = ty * UTH, x0 = tx * UTW, n0 = tn * WBN;  // low-resolution origin of the tile
+  const wino::TileId wg = wino::tile_of_workgroup(blockIdx.x, tilesN, tiles_x, tiles_y, xcd_sp);
+  const int b = wg.b;
+  const int y0 = wg.ty * UTH, x0 = wg.tx * UTW, n0 = wg.tn * WBN;  // low-resolution origin of the tile
   const int nsteps = p.K / UBK;
 
   // ---- halo role: pixel hp of the chunk's halo, channel quad hq: loaded once per chunk, stored to sH two steps ahead ----
@@ -175,11 +163,11 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   };
 
   // ---- U fragments of this wave's position: [step][pos][n0 + 32 nb + lr][4 lh .. 4 lh + 3], L2 -> registers one step ahead ----
-  const auto rsU = VAE_BUF_RSRC(U, (size_t)nsteps * NPOS * p.N * 8 * 4u);
+  const auto rsU = VAE_BUF_RSRC(U, wino::u_bytes(nsteps, NPOS, p.N));
   unsigned bvo[UNB];
 #pragma unroll
-  for (int q = 0; q < UNB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? (unsigned)(((n0 + q * 32 + lr) * 8 + lh * 4) * 4) : BUF_OOB;
-  const unsigned bpos = (unsigned)p.N * 32u;  // bytes per position of the U image
+  for (int q = 0; q < UNB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? wino::u_frag(n0 + q * 32 + lr, lh) : BUF_OOB;
+  const unsigned bpos = wino::u_pos_bytes(p.N);
   const unsigned bvx = extra ? bvo[xnb & 1] : BUF_OOB;  // the ninth position's block (waves without one request nothing)
   // ONE register set, refilled behind the MFMAs that consume it (conv3_wino.hip); every step issues the same UNB + 1 requests
   // in code every wave runs (beyond the last chunk the last one again, never used; waves without a ninth-position block request
@@ -277,18 +265,8 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 #pragma unroll
   for (int nb = 0; nb < UNB; ++nb) {
     if (nb > 0) __syncthreads();  // the previous block's reads are done
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int tile = (e & 3) + 8 * (e >> 2) + 4 * lh;
-      sM[(wave * UTL + tile) * UMLD + lr] = acc[nb][e];
-    }
-    if (wave == xw0 + nb) {  // the ninth position's block nb
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int tile = (e & 3) + 8 * (e >> 2) + 4 * lh;
-        sM[(8 * UTL + tile) * UMLD + lr] = accx[e];
-      }
-    }
+    wino::spill_acc(sM, wave, UMLD, acc[nb], lr, lh);
+    if (wave == xw0 + nb) wino::spill_acc(sM, 8, UMLD, accx, lr, lh);  // the ninth position's block nb
     __syncthreads();
     {
 #pragma unroll
@@ -335,10 +313,8 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 // the high-resolution dY, row grid = the low-resolution input gradient) of conv3x3(nearest_upsample_2x(x)) in fp32
 bool conv3_upwino_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.prec != VAE_PREC_F32 || a.A16 != nullptr || a.batch != 1 || a.alpha != 1.0f || a.xf != VAE_XF_NONE) return false;
-  if (g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return false;
-  if (a.tapmask != 0 || a.a_step > 1 || a.c_step > 1 || a.track != nullptr || a.res != nullptr || a.gstat != nullptr) return false;
-  if (a.out_bf16 || a.a_bf16 || a.res_bf16) return false;
+  if (!wino::conv_eligible_common(a, NPOS) || a.xf != VAE_XF_NONE) return false;
+  if (a.track != nullptr || a.res != nullptr || a.gstat != nullptr || a.a_bf16 || a.res_bf16) return false;
   int Hl, Wl;  // low-resolution size
   if (g.mode == VAE_MODE_UP2X) {
     if (g.Ho != 2 * g.Hs || g.Wo != 2 * g.Ws || a.sk != 1) return false;
@@ -350,17 +326,11 @@ bool conv3_upwino_eligible(const vae_igemm_args& a) {
     return false;
   }
   if (Hl % UTH != 0 || Wl % UTW != 0 || a.K % UBK != 0 || a.K < 64 || a.K > 1024 || a.N < 32 || a.N % 4 != 0 || g.Cs < a.K) return false;
-  if (!aligned16(a.A) || !aligned16(a.C)) return false;
-  if ((size_t)g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX || (size_t)g.Ho * g.Wo * a.ldc * 4u >= BUF_MAX) return false;
-  if ((size_t)a.K * NPOS * a.N * 4u >= BUF_MAX) return false;
   return true;
 }
 
 int launch_upwino_weights(const vae_igemm_args& a, float* U, hipStream_t st) {
-  const int64_t n = (int64_t)a.N * a.K;
-  hipLaunchKernelGGL(upwino_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.W, a.N, a.K,
-                     a.g.mode == VAE_MODE_UP2X_DGRAD ? 1 : 0, a.sn, a.sk, a.st, U);
-  return 0;
+  return wino::launch_weights(upwino_weights_kernel, a, a.g.mode == VAE_MODE_UP2X_DGRAD, U, st);
 }
 
 int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st) {
@@ -372,7 +342,7 @@ int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st)
   const int64_t nt = (int64_t)tilesN * tx * ty * g.B;
   if (nt > 0x7fffffffLL) return VAE_EINVAL;
   constexpr size_t xcd_u = (size_t)4 << 20;
-  const int xcd_sp = (tilesN > 1 && (size_t)a.K * NPOS * a.N * 4u <= xcd_u && ((int64_t)tx * ty * g.B) % 8 == 0) ? 1 : 0;
+  const int xcd_sp = wino::xcd_spatial(tilesN, wino::u_bytes(a.K / UBK, NPOS, a.N), xcd_u, (int64_t)tx * ty * g.B);
   if (dg) hipLaunchKernelGGL((conv3_upwino_kernel<true>), dim3((unsigned)nt), dim3(UNT), 0, st, a, U, tx, ty, xcd_sp);
   else hipLaunchKernelGGL((conv3_upwino_kernel<false>), dim3((unsigned)nt), dim3(UNT), 0, st, a, U, tx, ty, xcd_sp);
   return 0;

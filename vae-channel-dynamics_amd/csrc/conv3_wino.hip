@@ -6,7 +6,8 @@
 // so a workgroup runs 16 GEMMs of [32 tiles] x [128 co] over the channel chunks.
 //   * U = G g G^T is built once per launch by vae_wino_weights from the LIVE weights (they change every optimizer step and
 //     the nudger edits parameters in place), laid out [K/8][16][N][8]: a workgroup's slab of one channel chunk is 16
-//     contiguous 4 KB pieces.  For dgrad the kernel is rotated and transposed there (N = Cin, K = Cout).
+//     contiguous 4 KB pieces.  For dgrad the kernel is rotated and transposed there (N = Cin, K = Cout).  (wino_common.h holds
+//     the layout, the workgroup id rule, the accumulator spill and the GroupNorm epilogue pieces for the whole family.)
 //   * Workgroup (8 waves) = 8 x 16 output pixels (32 Winograd tiles) x 64 output channels (NB = 2 channel blocks), channel
 //     chunk of 8 per step; 64 accumulator registers per wave, 128 VGPRs, so TWO workgroups share a CU and fill each other's
 //     barrier / load bubbles (NB = 4: 128 channels, 256 VGPRs, one workgroup per CU, was 4-10 % slower and is not built).
@@ -27,14 +28,14 @@
 // (tests/test_kernels_gpu.py), far inside the 1e-4 bar.  The epilogue also leaves the GroupNorm centred moments of the outputs
 // (one chunk per workgroup tile, as the direct kernels do) and -- dgrad launches with gnb_* set -- the first pass of the GroupNorm
 // backward over the gradient it has just computed; a tracked output stays on the direct kernel.
-#include "common.h"
+#include "wino_common.h"
 #include <type_traits>
 #include <algorithm>
 
 namespace {
 
 constexpr int WTH = 8, WTW = 16;          // output pixels per workgroup tile
-constexpr int NTL = 32;                   // Winograd tiles per workgroup (4 rows x 8 columns of 2x2 outputs)
+constexpr int NTL = wino::TILES;                   // Winograd tiles per workgroup (4 rows x 8 columns of 2x2 outputs)
 constexpr int WBK = 8;                    // channels per step
 constexpr int WNT = 512;
 constexpr int SV = 16 * NTL * WBK;        // floats per V buffer (16384 B): rows of 8 floats, a wave's 16-byte fragment reads
@@ -53,13 +54,7 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restri
   if (i >= (int64_t)N * K) return;
   const int k = (int)(i % K), n = (int)(i / K);
   float g[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int tap = dgrad ? (2 - a) * 3 + (2 - b) : a * 3 + b;
-      g[a][b] = W[(int64_t)n * sn + (int64_t)k * sk + (int64_t)tap * st];
-    }
+  wino::u_gather(W, n, k, dgrad, sn, sk, st, g);
   float t[4][3];
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
@@ -68,16 +63,16 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restri
     t[2][b] = 0.5f * ((g[0][b] + g[2][b]) - g[1][b]);
     t[3][b] = g[2][b];
   }
-  float* o = U + ((int64_t)(k >> 3) * 16 * N + n) * 8 + (k & 7);
+  float* o = wino::u_out<16>(U, N, n, k);
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     const float u0 = t[a][0], u3 = t[a][2];
     const float u1 = 0.5f * ((t[a][0] + t[a][2]) + t[a][1]);
     const float u2 = 0.5f * ((t[a][0] + t[a][2]) - t[a][1]);
-    o[(int64_t)(a * 4 + 0) * N * 8] = u0;
-    o[(int64_t)(a * 4 + 1) * N * 8] = u1;
-    o[(int64_t)(a * 4 + 2) * N * 8] = u2;
-    o[(int64_t)(a * 4 + 3) * N * 8] = u3;
+    wino::u_at(o, N, a * 4 + 0) = u0;
+    wino::u_at(o, N, a * 4 + 1) = u1;
+    wino::u_at(o, N, a * 4 + 2) = u2;
+    wino::u_at(o, N, a * 4 + 3) = u3;
   }
 }
 
@@ -110,24 +105,9 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = (p.N + WBN - 1) / WBN;
-  // Workgroup id -> (spatial tile, channel block).  Consecutive ids go round-robin over the 8 XCDs (one L2 each).  With tn
-  // fastest an XCD sees one channel block's slice of U (what fits its L2) but every XCD pulls the whole input: Cout/64-fold
-  // L2 fills.  When the whole U image is small (<= 4 MB: 128 and 256 channels) the channel
-  // blocks of a spatial tile get ids congruent mod 8 instead, so one L2 fetches that tile's halo once.  Measured (rocprofv3
-  // FETCH_SIZE/WRITE_SIZE, bytes per launch averaged over the step's 96 launches): tn fastest everywhere 1351 MB, this rule
-  // 1142 MB, spatial-major everywhere (512 channels too: the U slices then cycle through L2) 1207 MB; same speed in all three.
-  int t = blockIdx.x, tn;
-  if (xcd_sp) {
-    tn = (t >> 3) % tilesN;
-    t = ((t >> 3) / tilesN) * 8 + (t & 7);
-  } else {
-    tn = t % tilesN;
-    t /= tilesN;
-  }
-  const int tx = t % tiles_x; t /= tiles_x;
-  const int ty = t % tiles_y;
-  const int b = t / tiles_y;
-  const int y0 = ty * WTH, x0 = tx * WTW, n0 = tn * WBN;
+  const wino::TileId wg = wino::tile_of_workgroup(blockIdx.x, tilesN, tiles_x, tiles_y, xcd_sp);
+  const int tx = wg.tx, ty = wg.ty, b = wg.b;
+  const int y0 = ty * WTH, x0 = tx * WTW, n0 = wg.tn * WBN;
   const int nsteps = p.K / WBK;
 
   // ---- halo role (threads 0..359): pixel hp of the 10 x 18 input halo, channel quad hq of the chunk.  The chunk's halo is
@@ -205,13 +185,13 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
   // ---- U fragments: the B operand of position pos, channel block nb is U[step][pos][n0 + 32 nb + lr][4 lh .. 4 lh + 3]: 16
   // contiguous bytes of the transformed-weight image per lane, 1 KB per wave and (pos, nb).  Only the wave that owns the
   // position reads them, so they go from global memory (L2) straight into registers, one step ahead, and never touch LDS ----
-  const auto rsU = VAE_BUF_RSRC(U, (size_t)nsteps * 16 * p.N * 8 * 4u);
+  const auto rsU = VAE_BUF_RSRC(U, wino::u_bytes(nsteps, 16, p.N));
   // address = per-thread constant (one per channel block; out of range for channels beyond N) + a workgroup-uniform part in
   // a scalar register: one instruction per load
   unsigned bvo[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? (unsigned)(((n0 + q * 32 + lr) * 8 + lh * 4) * 4) : BUF_OOB;
-  const unsigned bpos = (unsigned)p.N * 32u;  // bytes per position of the U image
+  for (int q = 0; q < NB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? wino::u_frag(n0 + q * 32 + lr, lh) : BUF_OOB;
+  const unsigned bpos = wino::u_pos_bytes(p.N);
   // ONE register set: the fragment of (position pi, channel block nb) for step s+1 is requested right behind the four MFMAs
   // that consume step s's (two sets -- 32 registers -- did not fit the 128-register budget of two workgroups per CU next to the
   // accumulators and the staging role: 7 registers spilled).  Every step issues the same 2 NB requests; beyond the last chunk
@@ -329,9 +309,7 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
   const auto rsR = VAE_BUF_RSRC((p.res ? p.res : p.C) + (int64_t)b * g.Ho * g.Wo * p.ldc, obytes);
   // GroupNorm-backward epilogue (dgrad launches, vaehip.h gnb_*): x at this thread's output positions, stored fp32 or bf16
   const bool gnb = p.gnb_ws != nullptr;  // uniform
-  const unsigned xes = p.gnb_x_bf16 ? 2u : 4u;
-  const auto rsX = VAE_BUF_RSRC(reinterpret_cast<const char*>(gnb ? p.gnb_x : (const void*)p.C) + (int64_t)b * g.Ho * g.Wo * p.ldc * xes,
-                                (size_t)g.Ho * g.Wo * p.ldc * xes);
+  const auto rsX = wino::gnb_x_rsrc(gnb ? p.gnb_x : (const void*)p.C, p.gnb_x_bf16, (int64_t)b * g.Ho * g.Wo, (int64_t)g.Ho * g.Wo, p.ldc);
   // byte offsets of this thread's 8 outputs per channel block (2 tile slots x 2 x 2 pixels, channel n0 + (tid & 31))
   unsigned offp[8];
 #pragma unroll
@@ -353,34 +331,16 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
     float xin[8];  // the GroupNorm input at the same 8 positions (requested here, used after the LDS round trip)
     if (gnb) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const unsigned eo = off[q] == BUF_OOB ? BUF_OOB : (p.gnb_x_bf16 ? off[q] >> 1 : off[q]);
-        xin[q] = p.gnb_x_bf16 ? __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsX, eo, 0, 0) << 16)
-                              : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, eo, 0, 0));
-      }
+      for (int q = 0; q < 8; ++q) xin[q] = wino::gnb_load_x<true>(rsX, p.gnb_x_bf16, off[q], 0u);
     }
 #pragma unroll
-    for (int pi = 0; pi < 2; ++pi) {
-      const int pos = 2 * wave + pi;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int tile = (e & 3) + 8 * (e >> 2) + 4 * lh;
-        sM[(pos * NTL + tile) * SMLD + lr] = acc[pi][nb][e];
-      }
-    }
+    for (int pi = 0; pi < 2; ++pi) wino::spill_acc(sM, 2 * wave + pi, SMLD, acc[pi][nb], lr, lh);
     __syncthreads();
     WEDGE(3 + 2 * nb);
     float gpv = 0.f, gs1 = 0.f, gs2 = 0.f;  // GroupNorm statistics of this thread's 8 outputs of channel `col`: shifted sums
     float bs1 = 0.f, bs2 = 0.f;             // GroupNorm backward: sum dz, sum dz * xhat over the same 8 outputs
-    float bmu = 0.f, brs = 0.f, bga = 0.f, bbe = 0.f;
-    if (gnb) {
-      const int colb = min(n0 + nb * 32 + (tid & 31), p.N - 1);
-      const int grp = colb / (p.N / p.gnb_groups);
-      bmu = p.gnb_mean[b * p.gnb_groups + grp];
-      brs = p.gnb_rstd[b * p.gnb_groups + grp];
-      bga = p.gnb_gamma[colb];
-      bbe = p.gnb_beta[colb];
-    }
+    wino::GnbCoef bco;
+    if (gnb) bco = wino::gnb_coef(p, b, min(n0 + nb * 32 + (tid & 31), p.N - 1));
 #pragma unroll
     for (int rnd = 0; rnd < 2; ++rnd) {
       const int co = tid & 31, tile = (tid >> 5) + 16 * rnd;
@@ -405,52 +365,28 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
           if (p.res) v += rres[q];
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, off[q], 0, 0);
           if (rnd == 0 && a == 0 && bb == 0) gpv = v;
+          // The shifted sums are this kernel's own arithmetic, on purpose not shared with conv3_wino4.hip: accumulated on every
+          // launch (no `if (p.gstat)`), the square as a multiply and an add -- two roundings where F(4x4)'s fmaf has one.
           const float dv = v - gpv;  // (the statistics epilogue only runs on full tiles)
           gs1 += dv;
           gs2 += dv * dv;
-          if (gnb) {  // uniform; same arithmetic per element as gn_bwd_partial_kernel (norm.hip)
-            const float xh = (xin[q] - bmu) * brs;
-            float du = v;
-            if (p.gnb_silu) du *= silu_grad_f(xh * bga + bbe);
-            bs1 += du;
-            bs2 += du * xh;
-          }
+          if (gnb) wino::gnb_accumulate(bco, p.gnb_silu, xin[q], v, bs1, bs2);  // uniform
         }
       }
     }
     WEDGE(4 + 2 * nb);
     float* const red = sM + 16 * NTL * SMLD;  // [8 waves][groups of the 32-channel block][2]
     float* const redb = red + 8 * 8 * 2;      // [16 tile slots][32 channels][2]
-    if (gnb) {
-      redb[((tid >> 5) * 32 + (tid & 31)) * 2] = bs1;
-      redb[((tid >> 5) * 32 + (tid & 31)) * 2 + 1] = bs2;
-    }
+    if (gnb) wino::gnb_slot_store(redb, tid, bs1, bs2);
     const int cpg = p.gstat ? p.N / p.gstat_groups : 4, ng = 32 / cpg;
-    if (p.gstat) {  // uniform: centred moments of the block's groups; a wave holds 2 tile slots x 32 channels
-      const MeanM2 a = mm2_wave_group(mm2_from_shifted(gpv, gs1, gs2, 8.f), cpg, 8.f);
-      if (lh == 0 && (lr & (cpg - 1)) == 0) {
-        red[(wave * ng + lr / cpg) * 2] = a.m;
-        red[(wave * ng + lr / cpg) * 2 + 1] = a.M2;
-      }
-    }
+    if (p.gstat) wino::gstat_wave_store(red, wave, cpg, lr, lh, gpv, gs1, gs2, 8.f);  // uniform; a wave holds 2 tile slots x 32 channels
     __syncthreads();
-    if (gnb && tid < 32 && n0 + nb * 32 + tid < p.N) {  // the 16 tile slots of a channel, fixed order
-      float a1 = redb[tid * 2], a2 = redb[tid * 2 + 1];
-#pragma unroll
-      for (int w = 1; w < 16; ++w) {
-        a1 += redb[(w * 32 + tid) * 2];
-        a2 += redb[(w * 32 + tid) * 2 + 1];
-      }
-      float* o = p.gnb_ws + (((int64_t)b * (tiles_x * tiles_y) + ty * tiles_x + tx) * p.N + n0 + nb * 32 + tid) * 2;
-      o[0] = a1;
-      o[1] = a2;
-    }
-    if (p.gstat && tid < ng) {  // the 8 waves (16 outputs x cpg channels each), fixed order
-      const float nw = 16.f * (float)cpg;
-      MeanM2 a{red[tid * 2], red[tid * 2 + 1]};
-#pragma unroll
-      for (int w = 1; w < 8; ++w) a = mm2_merge(a, nw * (float)w, MeanM2{red[(w * ng + tid) * 2], red[(w * ng + tid) * 2 + 1]}, nw);
-      float* o = p.gstat + (((int64_t)b * (tiles_x * tiles_y) + ty * tiles_x + tx) * p.gstat_groups + (n0 + nb * 32) / cpg + tid) * 2;
+    const int64_t chunk = wino::chunk_of_tile(b, tiles_x, tiles_y, ty, tx);
+    if (gnb && tid < 32 && n0 + nb * 32 + tid < p.N)  // the 16 tile slots of a channel
+      wino::gnb_reduce<16>(redb, tid, p.gnb_ws + (chunk * p.N + n0 + nb * 32 + tid) * 2);
+    if (p.gstat && tid < ng) {  // the 8 waves (16 outputs x cpg channels each)
+      const MeanM2 a = wino::gstat_merge<8>(red, ng, tid, [&](int) { return 16.f * (float)cpg; });
+      float* o = p.gstat + (chunk * p.gstat_groups + (n0 + nb * 32) / cpg + tid) * 2;
       o[0] = a.m;
       o[1] = a.M2;
     }
@@ -468,49 +404,22 @@ __global__ __launch_bounds__(WNT, (NB == 4 ? 2 : 4)) void conv3_wino_kernel(vae_
 // forward / dgrad of a plain 3x3 stride-1 pad-1 layer in fp32, 8x16-pixel tiles, channel chunks of 8
 bool conv3_wino_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.prec != VAE_PREC_F32 || a.A16 != nullptr || a.batch != 1 || a.alpha != 1.0f) return false;
-  if (g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return false;
-  if (a.tapmask != 0 || a.a_step > 1 || a.c_step > 1 || a.out_bf16) return false;
+  if (!wino::conv_eligible_common(a, 16)) return false;
 #ifndef VAE_WINO_TIMING  // (the instrumented build writes its stamps through `track`)
   if (a.track != nullptr) return false;
 #endif
   if (!(g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_DGRAD) || g.Ho != g.Hs || g.Wo != g.Ws) return false;
   if (g.mode == VAE_MODE_DGRAD && a.xf != VAE_XF_NONE) return false;
   if (g.Ho % WTH != 0 || g.Wo % WTW != 0 || a.K % WBK != 0 || a.K < 64 || a.K > 1024 || a.N < 32 || a.N % 4 != 0 || g.Cs < a.K) return false;
-  if (!aligned16(a.A) || !aligned16(a.C)) return false;
-  if ((size_t)g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX || (size_t)g.Ho * g.Wo * a.ldc * 4u >= BUF_MAX) return false;
-  if ((size_t)a.K * 16 * a.N * 4u >= BUF_MAX) return false;
   return true;
 }
 
-// channel blocks (of 32) per workgroup: 2 = 64 channels, 128 VGPRs per wave, TWO workgroups per CU (the template also
-// instantiates with 4 = 128 channels, one workgroup per CU: measured 4-10 % slower in round 2 and no longer built)
-int conv3_wino_nb() { return 2; }
-
-// chunks per image of the statistics epilogue (0 = not available for these arguments)
-int conv3_wino_gstat_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (a.gstat_groups <= 0 || a.N % (32 * conv3_wino_nb()) != 0 || a.N % a.gstat_groups != 0 || g.mode == VAE_MODE_DGRAD) return 0;
-  const int cpg = a.N / a.gstat_groups;
-  if (cpg != 4 && cpg != 8 && cpg != 16) return 0;
-  return (g.Wo / WTW) * (g.Ho / WTH);
-}
-
-// chunks per image of the GroupNorm-backward epilogue (0 = not available for these arguments): full tiles of a dgrad launch
-// whose output has the GroupNorm input's shape
-int conv3_wino_gnb_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (g.mode != VAE_MODE_DGRAD || a.gnb_x == nullptr || a.gnb_groups <= 0 || a.N % a.gnb_groups != 0 || a.ldc != a.N) return 0;
-  if (a.res != nullptr || a.bias != nullptr || a.out_bf16) return 0;
-  if ((size_t)g.Ho * g.Wo * a.ldc * 4u >= BUF_MAX) return 0;
-  return (g.Wo / WTW) * (g.Ho / WTH);
-}
+// chunks per image of the statistics epilogue (whole 64-channel workgroups only) and of the GroupNorm-backward epilogue
+int conv3_wino_gstat_chunks(const vae_igemm_args& a) { return a.N % (32 * CONV3_WINO_NB) != 0 ? 0 : wino::gstat_chunks(a, WTH, WTW); }
+int conv3_wino_gnb_chunks(const vae_igemm_args& a) { return wino::gnb_chunks(a, WTH, WTW); }
 
 int launch_wino_weights(const vae_igemm_args& a, float* U, hipStream_t st) {
-  const int64_t n = (int64_t)a.N * a.K;
-  hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.W, a.N, a.K, a.g.mode == VAE_MODE_DGRAD ? 1 : 0,
-                     a.sn, a.sk, a.st, U);
-  return 0;
+  return wino::launch_weights(wino_weights_kernel, a, a.g.mode == VAE_MODE_DGRAD, U, st);
 }
 
 template <int XF, int NB>
@@ -520,14 +429,13 @@ static int launch_wino_t(const vae_igemm_args& a, const float* U, hipStream_t st
   const int64_t nt = (int64_t)((a.N + 32 * NB - 1) / (32 * NB)) * tx * ty * g.B;
   if (nt > 0x7fffffffLL) return VAE_EINVAL;
   constexpr size_t xcd_u = (size_t)4 << 20;  // U images up to 4 MB: the channel blocks of a tile share an XCD (lowest measured traffic)
-  const int tilesN = (a.N + 32 * NB - 1) / (32 * NB);
-  const int xcd_sp = (tilesN > 1 && (size_t)a.K * 16 * a.N * 4u <= xcd_u && ((int64_t)tx * ty * g.B) % 8 == 0) ? 1 : 0;
+  const int xcd_sp = wino::xcd_spatial((a.N + 32 * NB - 1) / (32 * NB), wino::u_bytes(a.K / WBK, 16, a.N), xcd_u, (int64_t)tx * ty * g.B);
   hipLaunchKernelGGL((conv3_wino_kernel<XF, NB>), dim3((unsigned)nt), dim3(WNT), 0, st, a, U, tx, ty, xcd_sp);
   return 0;
 }
 
 int launch_conv3_wino(const vae_igemm_args& a, const float* U, hipStream_t st) {
-  if (a.xf == VAE_XF_NONE) return launch_wino_t<VAE_XF_NONE, 2>(a, U, st);
-  if (a.xf == VAE_XF_AFFINE) return launch_wino_t<VAE_XF_AFFINE, 2>(a, U, st);
-  return launch_wino_t<VAE_XF_AFFINE_SILU, 2>(a, U, st);
+  if (a.xf == VAE_XF_NONE) return launch_wino_t<VAE_XF_NONE, CONV3_WINO_NB>(a, U, st);
+  if (a.xf == VAE_XF_AFFINE) return launch_wino_t<VAE_XF_AFFINE, CONV3_WINO_NB>(a, U, st);
+  return launch_wino_t<VAE_XF_AFFINE_SILU, CONV3_WINO_NB>(a, U, st);
 }

@@ -34,8 +34,10 @@
 //     are 43k cycles per tile: 30 % of a 128-channel layer's workgroup, 9 % of a 512-channel one.
 //   * Epilogue per 32-channel block: accumulators through LDS ([36][32 tiles][32 channels]), each thread takes A^T M A of its (tile,
 //     channel) pairs, adds bias / residual, writes the 4x4 outputs (lanes along channels: 128-byte rows) and leaves the
-//     GroupNorm moments of the outputs / -- dgrad launches -- the first pass of the GroupNorm backward, as conv3_wino.hip does.
-#include "common.h"
+//     GroupNorm moments of the outputs / -- dgrad launches -- the first pass of the GroupNorm backward.
+// Shared with the other Winograd kernels (wino_common.h): workgroup id -> tile with its XCD placement, the U layout and its
+// fragment offsets, the accumulator spill, the GroupNorm-backward pieces and the fixed-order reductions of both epilogues.
+#include "wino_common.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -50,7 +52,7 @@
 namespace {
 
 constexpr int FTH = 16, FTW = 32;        // output pixels per workgroup tile
-constexpr int FNTL = 32;                 // tiles per workgroup (4 rows x 8 columns of 4x4 outputs)
+constexpr int FNTL = wino::TILES;                 // tiles per workgroup (4 rows x 8 columns of 4x4 outputs)
 constexpr int FBK = 8;                   // channels per step
 constexpr int FNT = 768;                 // 12 waves
 constexpr int FPOS = 36;
@@ -75,13 +77,7 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* __restr
   // (the image is 36/9 = 4x the bytes of the weights it is made from: the writes decide; (n, k) with k fastest wrote 32-byte pieces)
   const int k = (int)((i / (8 * (int64_t)N)) * 8 + (i & 7)), n = (int)((i >> 3) % N);
   float g[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int tap = dgrad ? (2 - a) * 3 + (2 - b) : a * 3 + b;
-      g[a][b] = W[(int64_t)n * sn + (int64_t)k * sk + (int64_t)tap * st];
-    }
+  wino::u_gather(W, n, k, dgrad, sn, sk, st, g);
   constexpr float c4 = 0.25f, c6 = 1.0f / 6.0f, c12 = 1.0f / 12.0f, c24 = 1.0f / 24.0f;
   float t[6][3];
 #pragma unroll
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* __restr
     t[4][b] = (c24 * g0 + c6 * g2) - c12 * g1;
     t[5][b] = g2;
   }
-  float* o = U + ((int64_t)(k >> 3) * FPOS * N + n) * 8 + (k & 7);
+  float* o = wino::u_out<FPOS>(U, N, n, k);
 #pragma unroll
   for (int a = 0; a < 6; ++a) {  // (G g) G^T
     const float g0 = t[a][0], g1 = t[a][1], g2 = t[a][2];
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* __restr
     u[4] = (c24 * g0 + c6 * g2) - c12 * g1;
     u[5] = g2;
 #pragma unroll
-    for (int b = 0; b < 6; ++b) o[(int64_t)(a * 6 + b) * N * 8] = u[b];
+    for (int b = 0; b < 6; ++b) wino::u_at(o, N, a * 6 + b) = u[b];
   }
 }
 
@@ -161,20 +157,9 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = p.N / FBN;
-  // workgroup id -> (spatial tile, channel block): the rule of conv3_wino.hip (small U images: the channel blocks of a spatial
-  // tile get ids congruent mod 8, one XCD's L2 fetches that tile's halo once)
-  int t = blockIdx.x, tn;
-  if (xcd_sp) {
-    tn = (t >> 3) % tilesN;
-    t = ((t >> 3) / tilesN) * 8 + (t & 7);
-  } else {
-    tn = t % tilesN;
-    t /= tilesN;
-  }
-  const int tx = t % tiles_x; t /= tiles_x;
-  const int ty = t % tiles_y;
-  const int b = t / tiles_y;
-  const int y0 = ty * FTH, x0 = tx * FTW, n0 = tn * FBN;
+  const wino::TileId wg = wino::tile_of_workgroup(blockIdx.x, tilesN, tiles_x, tiles_y, xcd_sp);
+  const int tx = wg.tx, ty = wg.ty, b = wg.b;
+  const int y0 = ty * FTH, x0 = tx * FTW, n0 = wg.tn * FBN;
   const int nsteps = p.K / FBK;
 
   // ---- the chunk's 18 x 34 input halo in LDS: pixel-major, 8 channels (32 B) per pixel, 32 B of padding behind every 4 pixels:
@@ -320,9 +305,9 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   };
 
   // ---- U fragments: B operand of (position, channel block nb) = U[step][pos][n0 + 32 nb + lr][4 lh .. 4 lh + 3] ----
-  const auto rsU = VAE_BUF_RSRC(U, (size_t)nsteps * FPOS * p.N * 8 * 4u);
-  const unsigned bvo = (unsigned)(((n0 + lr) * 8 + lh * 4) * 4);  // (+ 1024 B for the second channel block)
-  const unsigned bpos = (unsigned)p.N * 32u;  // bytes per position of the U image
+  const auto rsU = VAE_BUF_RSRC(U, wino::u_bytes(nsteps, FPOS, p.N));
+  const unsigned bvo = wino::u_frag(n0 + lr, lh);  // (+ 1024 B for the second channel block)
+  const unsigned bpos = wino::u_pos_bytes(p.N);
   f32x4 bq[6];
   auto load_b1 = [&](int step, int i) {
     const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(min(step, nsteps - 1) * FPOS + 3 * uwave) * bpos);
@@ -457,37 +442,22 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
   const auto rsC = VAE_BUF_RSRC(p.C + (int64_t)b * g.Ho * g.Wo * p.ldc, obytes);
   const auto rsR = VAE_BUF_RSRC((p.res ? p.res : p.C) + (int64_t)b * g.Ho * g.Wo * p.ldc, obytes);
   const bool gnb = p.gnb_ws != nullptr;  // uniform
-  const unsigned xes = p.gnb_x_bf16 ? 2u : 4u;
-  const auto rsX = VAE_BUF_RSRC(reinterpret_cast<const char*>(gnb ? p.gnb_x : (const void*)p.C) + (int64_t)b * g.Ho * g.Wo * p.ldc * xes,
-                                (size_t)g.Ho * g.Wo * p.ldc * xes);
+  const auto rsX = wino::gnb_x_rsrc(gnb ? p.gnb_x : (const void*)p.C, p.gnb_x_bf16, (int64_t)b * g.Ho * g.Wo, (int64_t)g.Ho * g.Wo, p.ldc);
   const int nrnd = tid < 1024 - FNT ? 2 : 1;  // (tile, channel) items 0..1023 of a block: thread tid takes tid and tid + 768
   float* const red = sM + FPOS * FNTL * FMLD;  // [12 waves][groups of the 32-channel block][2]
   float* const redb = red + 12 * 8 * 2;        // [24 slots][32 channels][2]
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
 #pragma unroll
-    for (int pi = 0; pi < 3; ++pi) {
-      const int pos = 3 * wave + pi;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int tile = (e & 3) + 8 * (e >> 2) + 4 * lh;
-        sM[(pos * FNTL + tile) * FMLD + lr] = acc[pi][nb][e];
-      }
-    }
+    for (int pi = 0; pi < 3; ++pi) wino::spill_acc(sM, 3 * wave + pi, FMLD, acc[pi][nb], lr, lh);
     __syncthreads();
     WEDGE(3 + 2 * nb);
     const int co = tid & 31, col = n0 + nb * 32 + co;
     const float bv = p.bias ? p.bias[col] : 0.f;
     float gpv = 0.f, gs1 = 0.f, gs2 = 0.f;  // GroupNorm statistics of this thread's outputs of channel `col`: shifted sums
     float bs1 = 0.f, bs2 = 0.f;             // GroupNorm backward: sum dz, sum dz * xhat over the same outputs
-    float bmu = 0.f, brs = 0.f, bga = 0.f, bbe = 0.f;
-    if (gnb) {
-      const int grp = col / (p.N / p.gnb_groups);
-      bmu = p.gnb_mean[b * p.gnb_groups + grp];
-      brs = p.gnb_rstd[b * p.gnb_groups + grp];
-      bga = p.gnb_gamma[col];
-      bbe = p.gnb_beta[col];
-    }
+    wino::GnbCoef bco;
+    if (gnb) bco = wino::gnb_coef(p, b, col);
 #pragma unroll 1
     for (int rnd = 0; rnd < nrnd; ++rnd) {
       const int tile = (tid >> 5) + 24 * rnd;
@@ -505,11 +475,7 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
       float xin[16];
       if (gnb) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const unsigned so = (q >> 2) * rstep + (q & 3) * cstep;
-          xin[q] = p.gnb_x_bf16 ? __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsX, obase >> 1, so >> 1, 0) << 16)
-                                : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, obase, so, 0));
-        }
+        for (int q = 0; q < 16; ++q) xin[q] = wino::gnb_load_x<false>(rsX, p.gnb_x_bf16, obase, (q >> 2) * rstep + (q & 3) * cstep);
       }
       float h[4][6];  // A^T M: per column j of M the 4 output rows
 #pragma unroll
@@ -531,58 +497,29 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
           float v = y[bb] + bv;
           if (p.res) v += rres[q];
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, obase, a * rstep + bb * cstep, 0);
+          // The shifted sums are this kernel's own arithmetic, on purpose not shared with conv3_wino.hip: only under p.gstat, the
+          // square through fmaf -- one rounding where F(2x2)'s multiply and add have two.
           if (p.gstat) {  // uniform (forward launches whose output feeds a GroupNorm)
             if (rnd == 0 && q == 0) gpv = v;
             const float dv = v - gpv;
             gs1 += dv;
             gs2 = fmaf(dv, dv, gs2);
           }
-          if (gnb) {  // uniform; same arithmetic per element as gn_bwd_partial_kernel (norm.hip)
-            const float xh = (xin[q] - bmu) * brs;
-            float du = v;
-            if (p.gnb_silu) du *= silu_grad_f(xh * bga + bbe);
-            bs1 += du;
-            bs2 += du * xh;
-          }
+          if (gnb) wino::gnb_accumulate(bco, p.gnb_silu, xin[q], v, bs1, bs2);  // uniform
         }
       }
     }
     WEDGE(4 + 2 * nb);
-    if (gnb) {
-      redb[((tid >> 5) * 32 + co) * 2] = bs1;
-      redb[((tid >> 5) * 32 + co) * 2 + 1] = bs2;
-    }
+    if (gnb) wino::gnb_slot_store(redb, tid, bs1, bs2);
     const int cpg = p.gstat ? p.N / p.gstat_groups : 4, ng = 32 / cpg;
     const float nlane = 16.f * (float)nrnd;  // outputs per lane (uniform per wave: waves 0..3 take two rounds)
-    if (p.gstat) {  // uniform: centred moments of the block's groups; a wave holds 2 tile slots x 32 channels
-      const MeanM2 a = mm2_wave_group(mm2_from_shifted(gpv, gs1, gs2, nlane), cpg, nlane);
-      if (lh == 0 && (lr & (cpg - 1)) == 0) {
-        red[(wave * ng + lr / cpg) * 2] = a.m;
-        red[(wave * ng + lr / cpg) * 2 + 1] = a.M2;
-      }
-    }
+    if (p.gstat) wino::gstat_wave_store(red, wave, cpg, lr, lh, gpv, gs1, gs2, nlane);  // uniform
     __syncthreads();
-    if (gnb && tid < 32) {  // the 24 slots of a channel, fixed order
-      float a1 = redb[tid * 2], a2 = redb[tid * 2 + 1];
-#pragma unroll
-      for (int w = 1; w < 24; ++w) {
-        a1 += redb[(w * 32 + tid) * 2];
-        a2 += redb[(w * 32 + tid) * 2 + 1];
-      }
-      float* o = p.gnb_ws + (((int64_t)b * (tiles_x * tiles_y) + ty * tiles_x + tx) * p.N + n0 + nb * 32 + tid) * 2;
-      o[0] = a1;
-      o[1] = a2;
-    }
-    if (p.gstat && tid < ng) {  // the 12 waves in fixed order: waves 0..3 hold 64 outputs per channel, the others 32
-      MeanM2 a{red[tid * 2], red[tid * 2 + 1]};
-      float na = 64.f * (float)cpg;
-#pragma unroll
-      for (int w = 1; w < 12; ++w) {
-        const float nw = (w < 4 ? 64.f : 32.f) * (float)cpg;
-        a = mm2_merge(a, na, MeanM2{red[(w * ng + tid) * 2], red[(w * ng + tid) * 2 + 1]}, nw);
-        na += nw;
-      }
-      float* o = p.gstat + (((int64_t)b * (tiles_x * tiles_y) + ty * tiles_x + tx) * p.gstat_groups + (n0 + nb * 32) / cpg + tid) * 2;
+    const int64_t chunk = wino::chunk_of_tile(b, tiles_x, tiles_y, ty, tx);
+    if (gnb && tid < 32) wino::gnb_reduce<24>(redb, tid, p.gnb_ws + (chunk * p.N + n0 + nb * 32 + tid) * 2);  // the 24 slots of a channel
+    if (p.gstat && tid < ng) {  // the 12 waves: waves 0..3 hold 64 outputs per channel, the others 32
+      const MeanM2 a = wino::gstat_merge<12>(red, ng, tid, [&](int w) { return (w < 4 ? 64.f : 32.f) * (float)cpg; });
+      float* o = p.gstat + (chunk * p.gstat_groups + (n0 + nb * 32) / cpg + tid) * 2;
       o[0] = a.m;
       o[1] = a.M2;
     }
@@ -611,44 +548,22 @@ __global__ __launch_bounds__(FNT, 3) void conv3_wino4_kernel(vae_igemm_args p, c
 // forward / dgrad of a plain 3x3 stride-1 pad-1 layer in fp32, 16x32-pixel tiles, channel chunks of 8, 64 output channels per workgroup
 bool conv3_wino4_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.prec != VAE_PREC_F32 || a.A16 != nullptr || a.batch != 1 || a.alpha != 1.0f) return false;
-  if (g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return false;
-  if (a.tapmask != 0 || a.a_step > 1 || a.c_step > 1 || a.out_bf16) return false;
+  if (!wino::conv_eligible_common(a, FPOS)) return false;
 #ifndef VAE_WINO4_TIMING  // (the instrumented build writes its stamps through `track`)
   if (a.track != nullptr) return false;
 #endif
   if (!(g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_DGRAD) || g.Ho != g.Hs || g.Wo != g.Ws) return false;
   if (g.mode == VAE_MODE_DGRAD && a.xf != VAE_XF_NONE) return false;
   if (g.Ho % FTH != 0 || g.Wo % FTW != 0 || a.K % FBK != 0 || a.K < 64 || a.K > 1024 || a.N % FBN != 0 || g.Cs < a.K) return false;
-  if (!aligned16(a.A) || !aligned16(a.C)) return false;
-  if ((size_t)g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX || (size_t)g.Ho * g.Wo * a.ldc * 4u >= BUF_MAX) return false;
-  if ((size_t)a.K * FPOS * a.N * 4u >= BUF_MAX) return false;
   return true;
 }
 
-// chunks per image of the statistics epilogue (0 = not available for these arguments)
-int conv3_wino4_gstat_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (a.gstat_groups <= 0 || a.N % a.gstat_groups != 0 || g.mode == VAE_MODE_DGRAD) return 0;
-  const int cpg = a.N / a.gstat_groups;
-  if (cpg != 4 && cpg != 8 && cpg != 16) return 0;
-  return (g.Wo / FTW) * (g.Ho / FTH);
-}
-
-// chunks per image of the GroupNorm-backward epilogue (0 = not available for these arguments)
-int conv3_wino4_gnb_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (g.mode != VAE_MODE_DGRAD || a.gnb_x == nullptr || a.gnb_groups <= 0 || a.N % a.gnb_groups != 0 || a.ldc != a.N) return 0;
-  if (a.res != nullptr || a.bias != nullptr || a.out_bf16) return 0;
-  if ((size_t)g.Ho * g.Wo * a.ldc * 4u >= BUF_MAX) return 0;
-  return (g.Wo / FTW) * (g.Ho / FTH);
-}
+// chunks per image of the statistics epilogue and of the GroupNorm-backward epilogue
+int conv3_wino4_gstat_chunks(const vae_igemm_args& a) { return wino::gstat_chunks(a, FTH, FTW); }
+int conv3_wino4_gnb_chunks(const vae_igemm_args& a) { return wino::gnb_chunks(a, FTH, FTW); }
 
 int launch_wino4_weights(const vae_igemm_args& a, float* U, hipStream_t st) {
-  const int64_t n = (int64_t)a.N * a.K;
-  hipLaunchKernelGGL(wino4_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.W, a.N, a.K, a.g.mode == VAE_MODE_DGRAD ? 1 : 0,
-                     a.sn, a.sk, a.st, U);
-  return 0;
+  return wino::launch_weights(wino4_weights_kernel, a, a.g.mode == VAE_MODE_DGRAD, U, st);
 }
 
 template <int XF>
@@ -659,7 +574,7 @@ static int launch_wino4_t(const vae_igemm_args& a, const float* U, hipStream_t s
   const int64_t nt = (int64_t)tilesN * tx * ty * g.B;
   if (nt > 0x7fffffffLL) return VAE_EINVAL;
   constexpr size_t xcd_u = (size_t)9 << 20;  // U images up to 9 MB (36 positions; 128 and 256 channels): the channel blocks of a tile share an XCD
-  const int xcd_sp = (tilesN > 1 && (size_t)a.K * FPOS * a.N * 4u <= xcd_u && ((int64_t)tx * ty * g.B) % 8 == 0) ? 1 : 0;
+  const int xcd_sp = wino::xcd_spatial(tilesN, wino::u_bytes(a.K / FBK, FPOS, a.N), xcd_u, (int64_t)tx * ty * g.B);
   hipLaunchKernelGGL((conv3_wino4_kernel<XF>), dim3((unsigned)nt), dim3(FNT), 0, st, a, U, tx, ty, xcd_sp);
   return 0;
 }

@@ -183,7 +183,7 @@ void rows_kernel_name(const RowsSel& s, char* buf, int n) {
   switch (s.k) {
     case RowsKernel::UpWino: snprintf(buf, n, "conv3_upwino_kernel<%s>", TF[a.g.mode == VAE_MODE_UP2X_DGRAD]); break;
     case RowsKernel::Wino4: snprintf(buf, n, "conv3_wino4_kernel<%d>", a.xf); break;
-    case RowsKernel::Wino: snprintf(buf, n, "conv3_wino_kernel<%d,%d>", a.xf, conv3_wino_nb()); break;
+    case RowsKernel::Wino: snprintf(buf, n, "conv3_wino_kernel<%d,%d>", a.xf, CONV3_WINO_NB); break;
     case RowsKernel::WideBf16: snprintf(buf, n, "conv3_wide_bf16_kernel<%s,%d>", TF[dg], a.tapmask != 0 ? 2 : 3); break;
     case RowsKernel::TileBf16:  // (a phase form never reads an operand image there)
       snprintf(buf, n, "conv3_tile_bf16_kernel<%s,%s,%d,%s>", TF[dg], TF[up], a.xf, TF[a.A16 != nullptr && !rows_is_phase(a)]);

@@ -24,7 +24,9 @@ int conv3_wide_bf16_gstat_chunks(const vae_igemm_args& a);
 int launch_conv3_wide_bf16(const vae_igemm_args& a, hipStream_t st);
 // conv3_wino.hip / conv3_wino4.hip / conv3_upwino.hip: fp32 Winograd F(2x2,3x3), F(4x4,3x3), the upsampler's 9 positions
 bool conv3_wino_eligible(const vae_igemm_args& a);
-int conv3_wino_nb();
+// channel blocks (of 32) per F(2x2) workgroup: 2 = 64 channels, 128 VGPRs per wave, TWO workgroups per CU (the template also
+// instantiates with 4 = 128 channels, one workgroup per CU: measured 4-10 % slower in round 2 and no longer built)
+constexpr int CONV3_WINO_NB = 2;
 int conv3_wino_gstat_chunks(const vae_igemm_args& a);
 int conv3_wino_gnb_chunks(const vae_igemm_args& a);
 int launch_wino_weights(const vae_igemm_args& a, float* U, hipStream_t st);

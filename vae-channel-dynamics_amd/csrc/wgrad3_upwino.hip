@@ -10,15 +10,18 @@
 // (row 0 of dW: dy0 (x[i-1] - x[i]) + (dy0 + dy1) x[i] = dy0 x[i-1] + dy1 x[i]: tap kh = 0 meets x[i-1] from the even output row
 // and x[i] from the odd one.)  Per position a GEMM  M_p[ci][co] = sum_pixels V_p[pixel][ci] * D_p[pixel][co].
 //
-// Kernel: as wgrad3_wino.hip -- a unit = 8 low-resolution pixels of one row (a 2 x 16 strip of dY); per unit the 3 x 10-pixel halo
-// of x and the strip of dY go to LDS untransformed, transposed to [row][channel][x]; a wave builds its MFMA operands while
-// reading them; split-K slabs [split][9][Cin][Cout]; wgrad_wino_reduce_kernel<9> (igemm.hip, one body for both schemes) sums the
-// slabs in fixed order, applies A''^T . A'' and writes OHWI.  Workgroup = 8 waves = 32 ci x 128 co x 9 positions: wave w owns position w (all four 32-channel blocks of co), and
-// the NINTH position is split by channel block over waves 0..3 -- one per SIMD (wave k of a workgroup runs on SIMD k % 4), so every
-// SIMD carries 36 MFMAs per step.  (A first version with one position per wave and 9 waves put three waves of every workgroup
-// on SIMD 0: 0.51 of the matrix peak.)  One workgroup per CU at 158 registers (a 128-register build spilled 27, with scratch reloads
-// inside the loop); two staging register sets, the next-but-one unit requested behind the first channel block's MFMAs.
-#include "common.h"
+// Kernel: the scheme of wgrad3_wino.hip, sharing with it by name (wino_common.h) split_tile_of_workgroup (without the rule for
+// 2 and 4 splits), unit_range, slab_store, bias_tail and the eligibility preamble -- a unit = 8 low-resolution pixels of one
+// row (a 2 x 16 strip of dY); per unit the 3 x 10-pixel halo of x and the strip of dY go to LDS untransformed, transposed to
+// [row][channel][x]; a wave builds its MFMA operands while reading them; split-K slabs [split][9][Cin][Cout];
+// wgrad_wino_reduce_kernel<9> (igemm.hip, one body for both schemes) sums the slabs in fixed order, applies A''^T . A'' and
+// writes OHWI.  Workgroup = 8 waves = 32 ci x 128 co x 9 positions: wave w owns position w (all four 32-channel blocks of co),
+// and the NINTH position is split by channel block over waves 0..3 -- one per SIMD (wave k of a workgroup runs on SIMD k % 4),
+// so every SIMD carries 36 MFMAs per step.  (A first version with one position per wave and 9 waves put three waves of every
+// workgroup on SIMD 0: 0.51 of the matrix peak.)  One workgroup per CU at 158 registers (a 128-register build spilled 27, with
+// scratch reloads inside the loop); two staging register sets, the next-but-one unit requested behind the first channel block's
+// MFMAs.
+#include "wino_common.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -38,23 +41,13 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;  // Hs x Ws: the low-resolution x; Ho x Wo = 2 Hs x 2 Ws: dY
   const int tilesN = p.N / GCI, ntile = tilesN * (p.M / GCO);
-  int tile, split;
-  {  // the tiles of one split walk through the same pixels: ids congruent mod 8 share an XCD's L2 (see wgrad3_wino.hip)
-    const int L = blockIdx.x, ns = p.nsplit;
-    if (ns % 8 == 0) {
-      const int j = L >> 3;
-      tile = j % ntile;
-      split = (j / ntile) * 8 + (L & 7);
-    } else {
-      tile = L % ntile;
-      split = L / ntile;
-    }
-  }
+  const wino::SplitTile wg = wino::split_tile_of_workgroup<false>(blockIdx.x, p.nsplit, ntile);  // (2 or 4 splits: tile fastest)
+  const int tile = wg.tile, split = wg.split;
   const int tm = tile / tilesN, tn = tile % tilesN;
   const int m0 = tm * GCO, n0 = tn * GCI;
-  const int64_t per = (nunits + p.nsplit - 1) / p.nsplit;
-  const int64_t ubeg = split * per, uend = min(nunits, ubeg + per);
-  const int nu = (int)max((int64_t)0, uend - ubeg);
+  const wino::UnitRange ur = wino::unit_range(nunits, p.nsplit, split);
+  const int64_t ubeg = ur.ubeg;
+  const int nu = ur.nu;
   const int upi = g.Hs * strips;  // units per image
   const bool do_bias = (p.bias_partial != nullptr) && tn == 0;
 
@@ -225,29 +218,9 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
 
   // ---- epilogue: slab [split][9 positions][Cin][Cout]; lanes along co (128-byte rows) ----
   float* __restrict__ O = p.partial + (int64_t)split * NPOS * p.N * p.M;
-#pragma unroll
-  for (int nb = 0; nb < GNB; ++nb)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int ci = n0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      O[((int64_t)wave * p.N + ci) * p.M + m0 + nb * 32 + lr] = acc[nb][e];
-    }
-  if (wave < 4) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int ci = n0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      O[((int64_t)8 * p.N + ci) * p.M + m0 + wave * 32 + lr] = accx[e];
-    }
-  }
-  if (do_bias) {  // workgroup-uniform: thread sums of its channel quad -> over the 16 columns of the strip
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float sv = bsum[e];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) sv += __shfl_xor(sv, o, 64);
-      if (xx == 0) p.bias_partial[(int64_t)split * p.M + m0 + 4 * yq + e] = sv;
-    }
-  }
+  wino::slab_store<GNB>(O, wave, p.N, p.M, n0, m0, 0, acc, lr, lh);
+  if (wave < 4) wino::slab_store<1>(O, 8, p.N, p.M, n0, m0, wave, &accx, lr, lh);
+  if (do_bias) wino::bias_tail(bsum, xx, p.bias_partial, (int64_t)split * p.M + m0 + 4 * yq);  // workgroup-uniform
 }
 
 }  // namespace
@@ -256,14 +229,9 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
 // 8 | low-resolution width, 32 | Cin, 128 | Cout
 bool wgrad3_upwino_eligible(const vae_wgrad_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.prec != VAE_PREC_F32 || a.X16 != nullptr || a.dY16 != nullptr || a.dY == nullptr || a.batch != 1 || a.alpha != 1.0f) return false;
-  if (a.x_bf16 || a.y_bf16 || a.xf != VAE_XF_NONE) return false;
-  if (g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.mode != VAE_MODE_UP2X) return false;
-  if (a.tapmask != 0 || a.y_step > 1 || g.Ho != 2 * g.Hs || g.Wo != 2 * g.Ws) return false;
-  if (g.Ws % 8 != 0 || a.N % GCI != 0 || a.M % GCO != 0 || g.Cs % 4 != 0 || a.ldy % 4 != 0 || g.Cs < a.N) return false;
-  if (!aligned16(a.X) || !aligned16(a.dY)) return false;
-  if ((size_t)g.B * g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX || (size_t)g.B * g.Ho * g.Wo * a.ldy * 4u >= BUF_MAX) return false;
-  return true;
+  if (!wino::wgrad_eligible_common(a, GCI, GCO) || a.x_bf16 || a.y_bf16 || a.xf != VAE_XF_NONE) return false;
+  if (g.mode != VAE_MODE_UP2X || g.Ho != 2 * g.Hs || g.Wo != 2 * g.Ws) return false;
+  return g.Ws % 8 == 0 && g.Cs >= a.N;
 }
 
 int64_t wgrad3_upwino_units(const vae_conv_geom& g) { return (int64_t)g.B * g.Hs * (g.Ws / 8); }

@@ -19,7 +19,9 @@
 //     (column sums of dY) rides along as in the direct kernel.
 // Numerics: measured against the direct kernel in tests/test_kernels_gpu.py (the transform-domain sums cancel in the output
 // transform, so the error is a few 1e-6 of the gradient scale instead of 1e-7; the parity bar is 1e-4).
-#include "common.h"
+// Shared with wgrad3_upwino.hip (wino_common.h): workgroup id -> (tile, split), the split's unit range, the slab store, the bias
+// tail and the eligibility preamble.
+#include "wino_common.h"
 #ifndef VAE_ABLATE
 #define VAE_ABLATE 0  // diagnostic builds (tools/ablation_builds.sh, wrong results): bit 0 no global loads, 1 no LDS stores, 4 no barrier
 #endif
@@ -48,29 +50,13 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = p.N / GCI, ntile = tilesN * (p.M / GCO);
-  // Workgroup id -> (tile, split).  Hardware deals consecutive ids round-robin over the 8 XCDs (one L2 each); the tiles of one
-  // split walk through the SAME pixels (every ci block re-reads the dY strip, every co block the X halo), so they are given
-  // ids congruent mod 8: one L2 (or 8 / nsplit of them) fetches a split's rows once.
-  int tile, split;
-  {
-    const int L = blockIdx.x, ns = p.nsplit;
-    if (ns % 8 == 0) {
-      const int j = L >> 3;
-      tile = j % ntile;
-      split = (j / ntile) * 8 + (L & 7);
-    } else if ((ns == 2 || ns == 4) && ntile % (8 / ns) == 0) {
-      split = (L & 7) % ns;
-      tile = (L >> 3) * (8 / ns) + (L & 7) / ns;
-    } else {
-      tile = L % ntile;
-      split = L / ntile;
-    }
-  }
+  const wino::SplitTile wg = wino::split_tile_of_workgroup<true>(blockIdx.x, p.nsplit, ntile);  // (with the rule for 2 and 4 splits)
+  const int tile = wg.tile, split = wg.split;
   const int tm = tile / tilesN, tn = tile % tilesN;
   const int m0 = tm * GCO, n0 = tn * GCI;
-  const int64_t per = (nunits + p.nsplit - 1) / p.nsplit;
-  const int64_t ubeg = split * per, uend = min(nunits, ubeg + per);
-  const int nu = (int)max((int64_t)0, uend - ubeg);
+  const wino::UnitRange ur = wino::unit_range(nunits, p.nsplit, split);
+  const int64_t ubeg = ur.ubeg;
+  const int nu = ur.nu;
   const int upi = (g.Ho / 2) * strips;  // units per image
   const bool do_bias = (p.bias_partial != nullptr) && tn == 0;
 #ifdef VAE_WGRAD_TIMING  // debug build (tools/wgrad_timing.py): shader-clock stamps of waves 0 and 4 (the two waves of SIMD 0) of workgroups 0..7 -> p.out,
@@ -368,26 +354,9 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
 #endif
   // ---- epilogue: slab [split][16 positions][Cin][Cout]; lanes along co (128-byte rows) ----
   float* __restrict__ O = p.partial + (int64_t)split * 16 * p.N * p.M;
-#pragma unroll
-  for (int pi = 0; pi < 2; ++pi) {
-    const int pos = wi * 4 + 2 * jh + pi;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int ci = n0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        O[((int64_t)pos * p.N + ci) * p.M + m0 + nb * 32 + lr] = acc[pi][nb][e];
-      }
-  }
-  if (do_bias) {  // workgroup-uniform: thread sums of its channel quad -> over the 16 columns of the strip
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float s = bsum[e];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
-      if (xx == 0) p.bias_partial[(int64_t)split * p.M + m0 + 4 * yq + e] = s;
-    }
-  }
+  wino::slab_store<4>(O, wi * 4 + 2 * jh, p.N, p.M, n0, m0, 0, acc[0], lr, lh);  // the wave's two positions
+  wino::slab_store<4>(O, wi * 4 + 2 * jh + 1, p.N, p.M, n0, m0, 0, acc[1], lr, lh);
+  if (do_bias) wino::bias_tail(bsum, xx, p.bias_partial, (int64_t)split * p.M + m0 + 4 * yq);  // workgroup-uniform
 }
 
 }  // namespace
@@ -395,13 +364,8 @@ __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, i
 // plain 3x3 stride-1 pad-1 layer in fp32 with 16-pixel strips, 32 | Cin, 128 | Cout
 bool wgrad3_wino_eligible(const vae_wgrad_args& a) {
   const vae_conv_geom& g = a.g;
-  if (a.prec != VAE_PREC_F32 || a.X16 != nullptr || a.dY16 != nullptr || a.dY == nullptr || a.batch != 1 || a.alpha != 1.0f) return false;
-  if (g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.mode != VAE_MODE_FWD) return false;
-  if (a.tapmask != 0 || a.y_step > 1 || g.Ho != g.Hs || g.Wo != g.Ws) return false;
-  if (g.Ho % 2 != 0 || g.Wo % 16 != 0 || a.N % GCI != 0 || a.M % GCO != 0 || g.Cs % 4 != 0 || a.ldy % 4 != 0) return false;
-  if (!aligned16(a.X) || !aligned16(a.dY)) return false;
-  if ((size_t)g.B * g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX || (size_t)g.B * g.Ho * g.Wo * a.ldy * 4u >= BUF_MAX) return false;
-  return true;
+  if (!wino::wgrad_eligible_common(a, GCI, GCO) || g.mode != VAE_MODE_FWD || g.Ho != g.Hs || g.Wo != g.Ws) return false;
+  return g.Ho % 2 == 0 && g.Wo % 16 == 0;
 }
 
 int64_t wgrad3_wino_units(const vae_conv_geom& g) { return (int64_t)g.B * (g.Ho / 2) * (g.Wo / 16); }
