@@ -386,6 +386,13 @@ int vae_sqnorm(const float* g, int64_t n, float* ws, int32_t nblk, float* out, v
 int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm,
               float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
               int32_t step, void* stream);
+/* vae_adamw plus, in the same pass and thread, the exponential moving average of the weights: e' = fmaf(omd, p' - e, e) with
+ * omd = (float)(1 - ema_decay) and p' the updated weight; ema_decay == 0 stores p' itself (e' == p' bit for bit).  p, m, v come
+ * out bit-identical to vae_adamw on the same inputs.  e: n floats, 16-byte aligned, overlapping none of p, g, m, v;
+ * ema_decay in [0, 1).  Anything else is VAE_EINVAL and no launch.                                                          */
+int vae_adamw_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm,
+                  float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  int32_t step, double ema_decay, void* stream);
 /* dead-weight scan (deadneuron.py:78-115): per segment, the count of |w| < thr and the sum of |w|.
  * seg_off [nseg][2] = {begin,end} element offsets into w (segments need not be adjacent).  The segments are scanned in
  * chunks of vae_dead_scan_chunk() elements, one workgroup per chunk: seg_chunk0 [nseg+1] = prefix sum of the segments'

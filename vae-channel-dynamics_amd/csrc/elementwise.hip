@@ -317,9 +317,19 @@ __global__ __launch_bounds__(256) void sqnorm_final_kernel(const float* __restri
 struct AdamArgs {
   float max_norm, decay, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
 };
+// EMA: the same pass also moves the weight average e towards the new p (vaehip.h); first: e' = p' (the first update, decay 0)
+struct EmaArgs {
+  float* e;
+  float omd;  // 1 - decay
+  int first;
+};
+__device__ __forceinline__ float ema_next(float e, float pp, const EmaArgs& x) { return x.first ? pp : fmaf(x.omd, pp - e, e); }
+
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, const float* __restrict__ sqnorm,
-                                                    AdamArgs a) {
+                                                    AdamArgs a, EmaArgs x) {
+  float* __restrict__ e = x.e;
   float clip = 1.0f;
   if (a.max_norm > 0.f) clip = fminf(1.0f, a.max_norm / (sqrtf(sqnorm[0]) + 1e-6f));
   const int64_t n4 = n >> 2;
@@ -328,19 +338,23 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
     f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
     f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+    f32x4 ev;
+    if (EMA) ev = *reinterpret_cast<f32x4*>(e + i * 4);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gv[e] * clip;
-      float pp = pv[e] * a.decay;
-      const float mm = mv[e] + (gg - mv[e]) * a.omb1;
-      const float v2 = vv[e] * a.beta2 + a.omb2 * gg * gg;
+    for (int k = 0; k < 4; ++k) {
+      const float gg = gv[k] * clip;
+      float pp = pv[k] * a.decay;
+      const float mm = mv[k] + (gg - mv[k]) * a.omb1;
+      const float v2 = vv[k] * a.beta2 + a.omb2 * gg * gg;
       const float denom = sqrtf(v2) / a.bc2_sqrt + a.eps;
       pp = pp - a.step_size * (mm / denom);
-      pv[e] = pp; mv[e] = mm; vv[e] = v2;
+      pv[k] = pp; mv[k] = mm; vv[k] = v2;
+      if (EMA) ev[k] = ema_next(ev[k], pp, x);
     }
     *reinterpret_cast<f32x4*>(p + i * 4) = pv;
     *reinterpret_cast<f32x4*>(m + i * 4) = mv;
     *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+    if (EMA) *reinterpret_cast<f32x4*>(e + i * 4) = ev;
   }
   if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
@@ -349,9 +363,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const float mm = m[i] + (gg - m[i]) * a.omb1;
     const float v2 = v[i] * a.beta2 + a.omb2 * gg * gg;
     const float denom = sqrtf(v2) / a.bc2_sqrt + a.eps;
-    p[i] = pp - a.step_size * (mm / denom);
+    pp = pp - a.step_size * (mm / denom);
+    p[i] = pp;
     m[i] = mm;
     v[i] = v2;
+    if (EMA) e[i] = ema_next(e[i], pp, x);
   }
 }
 
@@ -559,11 +575,13 @@ extern "C" int vae_sqnorm(const float* g, int64_t n, float* ws, int32_t nblk, fl
   return VAE_OK;
 }
 
-extern "C" int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm, float max_norm, double lr,
-                         double beta1, double beta2, double eps, double weight_decay, int32_t step, void* stream) {
-  VAE_CHECK(p && g && m && v && n > 0 && step >= 1, "adamw: bad args");
-  VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "adamw: clipping needs sqnorm");
-  VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: unaligned");
+// one host half for vae_adamw (e == nullptr) and vae_adamw_ema
+static int adamw_launch(const char* who, float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm,
+                        float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
+                        double ema_decay, void* stream) {
+  VAE_CHECK(p && g && m && v && n > 0 && step >= 1, "%s: bad args", who);
+  VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "%s: clipping needs sqnorm", who);
+  VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e), "%s: unaligned", who);
   // scalar prep exactly as torch.optim.adamw._single_tensor_adamw (python doubles)
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -576,9 +594,31 @@ extern "C" int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n
   a.step_size = (float)(lr / bc1);
   a.bc2_sqrt = (float)sqrt(bc2);
   a.eps = (float)eps;
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a);
-  VAE_LAUNCH_CHECK("adamw");
+  EmaArgs x{e, (float)(1.0 - ema_decay), ema_decay == 0.0 ? 1 : 0};
+  const dim3 grid(ew_blocks(n / 4 + 1));
+  if (e)
+    hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a, x);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a, x);
+  VAE_LAUNCH_CHECK(who);
   return VAE_OK;
+}
+
+extern "C" int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const float* sqnorm, float max_norm, double lr,
+                         double beta1, double beta2, double eps, double weight_decay, int32_t step, void* stream) {
+  return adamw_launch("adamw", p, g, m, v, nullptr, n, sqnorm, max_norm, lr, beta1, beta2, eps, weight_decay, step, 0.0, stream);
+}
+
+extern "C" int vae_adamw_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm, float max_norm,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step, double ema_decay,
+                             void* stream) {
+  VAE_CHECK(e && n > 0, "adamw_ema: bad args");
+  VAE_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, "adamw_ema: ema_decay %g outside [0, 1)", ema_decay);
+  // e is read and written in the pass that writes p, m, v and reads g: n floats of it must lie clear of each of them
+  const uintptr_t lo = (uintptr_t)e, hi = lo + (uintptr_t)n * 4u;
+  for (const float* o : {(const float*)p, g, (const float*)m, (const float*)v})
+    VAE_CHECK(!o || hi <= (uintptr_t)o || (uintptr_t)o + (uintptr_t)n * 4u <= lo, "adamw_ema: e overlaps p, g, m or v");
+  return adamw_launch("adamw_ema", p, g, m, v, e, n, sqnorm, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema_decay, stream);
 }
 
 extern "C" int vae_dead_scan_chunk(void) { return DEAD_CHUNK; }

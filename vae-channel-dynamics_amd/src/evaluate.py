@@ -45,7 +45,19 @@ def parse_args():
     p.add_argument("--logit_lens_projection_type", type=str, default="mini_decoder_single_channel",
                    choices=["mini_decoder_single_channel", "mini_decoder_full_map"])
     p.add_argument("--logit_lens_mini_decoder_input_channels", type=int, default=None)
+    # not a flag of the reference: evaluate <checkpoint_path>/vae_ema, the averaged weights train.py saves with training.use_ema
+    # (`--use_ema` or `--use_ema true`; `--use_ema false` evaluates the raw weights and says so in eval_metrics.txt)
+    p.add_argument("--use_ema", nargs="?", const=True, default=None, type=lambda x: (str(x).lower() == "true"))
     return p.parse_args()
+
+
+def model_directory(checkpoint_path: str, use_ema) -> str:
+    """<checkpoint_path>/vae, or vae_ema when asked for; a missing directory ends the program with status 1"""
+    model_path = os.path.join(checkpoint_path, "vae_ema" if use_ema else "vae")
+    if not os.path.isdir(model_path):
+        logger.error(f"{'EMA ' if use_ema else ''}VAE model directory not found at: {model_path}")
+        sys.exit(1)
+    return model_path
 
 
 def to_unit(t: torch.Tensor) -> torch.Tensor:
@@ -89,6 +101,8 @@ def save_png(t: torch.Tensor, path: str):
 def main():
     args = parse_args()
     config = load_config(args.config_path)
+    if args.use_ema:  # a wrong checkpoint path is reported before anything else is touched
+        model_directory(args.checkpoint_path, True)
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: evaluation runs on the HIP engine (no CPU fallback)")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -96,10 +110,7 @@ def main():
     if args.output_dir is None:
         args.output_dir = os.path.join(args.checkpoint_path, f"eval_results_{args.eval_split}")
     os.makedirs(args.output_dir, exist_ok=True)
-    model_path = os.path.join(args.checkpoint_path, "vae")
-    if not os.path.isdir(model_path):
-        logger.error(f"VAE model directory not found at: {model_path}")
-        sys.exit(1)
+    model_path = model_directory(args.checkpoint_path, args.use_ema)
     w = SDXLVAEWrapper(pretrained_model_name_or_path=model_path, device=device)
     w.vae.eval()
     data_cfg = config.get("data", {})
@@ -152,6 +163,8 @@ def main():
         f.write(f"Average KL: {avg_kl}\n")
         f.write(f"Average PSNR: {psnr}\n")
         f.write(f"Average SSIM: {ssim}\n")
+        if args.use_ema is not None:
+            f.write(f"Weights: {'ema' if args.use_ema else 'raw'}\n")
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ import math
 import os
 import pickle
 import random
+import re
 import sys
 import time
 
@@ -182,14 +183,21 @@ def valid_batch(batch) -> bool:
     return pv is not None and pv.ndim == 4 and pv.shape[0] > 0
 
 
+STATE_FILES = ("model.safetensors", "optimizer.bin", "scheduler.bin", "trainer_state.bin")
+
+
 def save_state(path: str, wrapper, trainer, rank: int = 0):
-    """file layout of accelerate.save_state (accelerate/utils/constants.py:20-31) used by train.py:358-362,392-405."""
+    """file layout of accelerate.save_state (accelerate/utils/constants.py:20-31) used by train.py:358-362,392-405, plus
+    trainer_state.bin: what a restart needs beside those (step counters, the gradient sum of a pending accumulation window,
+    the generator).  With training.use_ema the weight average rides in optimizer.bin."""
     from safetensors.torch import save_file
     os.makedirs(path, exist_ok=True)
     sd = {k: v.detach().cpu().contiguous() for k, v in wrapper.state_dict().items()}
     save_file(sd, os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
-    torch.save(trainer.optimizer.state_dict(), os.path.join(path, "optimizer.bin"))
-    torch.save(trainer.lr_scheduler.state_dict(), os.path.join(path, "scheduler.bin"))
+    tsd = trainer.state_dict()
+    torch.save(tsd.pop("optimizer"), os.path.join(path, "optimizer.bin"))
+    torch.save(tsd.pop("lr_scheduler"), os.path.join(path, "scheduler.bin"))
+    torch.save(tsd, os.path.join(path, "trainer_state.bin"))
     states = {"step": trainer.global_step, "random_state": random.getstate(), "numpy_random_seed": np.random.get_state(),
               "torch_manual_seed": torch.get_rng_state(),
               "torch_cuda_manual_seed": torch.cuda.get_rng_state_all() if torch.cuda.is_available() else None}
@@ -197,10 +205,74 @@ def save_state(path: str, wrapper, trainer, rank: int = 0):
         pickle.dump(states, f)
 
 
+def load_state(path: str, wrapper, trainer, rank: int = 0) -> int:
+    """restores what save_state wrote: the model into the arena, the trainer state (optimizer with its weight average,
+    scheduler, step counters, pending gradient sum, generator) and the Python / numpy / torch / torch.cuda RNG states of
+    random_states_<rank>.pkl (a rank without a file of its own keeps its RNG).  Returns the optimizer step to continue from.
+
+    Not restored: in a one-process run the order of the resumed epoch is a fresh shuffle (the RandomSampler draws from the
+    torch RNG when the iterator is made), and the in-memory histories of ActivityMonitor and DeadNeuronTracker cover only
+    the steps since the resume."""
+    from safetensors.torch import load_file
+    missing = [n for n in STATE_FILES if not os.path.isfile(os.path.join(path, n))]
+    if missing:
+        raise FileNotFoundError(f"{path} is not a training state written by save_state: missing {', '.join(missing)}")
+    wrapper.load_state_dict(load_file(os.path.join(path, "model.safetensors")))
+    tsd = torch.load(os.path.join(path, "trainer_state.bin"), map_location="cpu", weights_only=False)
+    tsd["optimizer"] = torch.load(os.path.join(path, "optimizer.bin"), map_location="cpu", weights_only=False)
+    tsd["lr_scheduler"] = torch.load(os.path.join(path, "scheduler.bin"), map_location="cpu", weights_only=False)
+    trainer.load_state_dict(tsd)
+    rpath = os.path.join(path, f"random_states_{rank}.pkl")
+    if os.path.isfile(rpath):
+        with open(rpath, "rb") as f:
+            states = pickle.load(f)
+        random.setstate(states["random_state"])
+        np.random.set_state(states["numpy_random_seed"])
+        torch.set_rng_state(states["torch_manual_seed"])
+        if states.get("torch_cuda_manual_seed") is not None and torch.cuda.is_available():
+            torch.cuda.set_rng_state_all(states["torch_cuda_manual_seed"])
+    else:
+        logger.warning(f"{rpath} not found: rank {rank} keeps its RNG state")
+    return trainer.global_step
+
+
+def ema_settings(training_cfg: dict):
+    """training.use_ema / training.ema_decay (not keys of the reference) -> (use_ema, ema_decay)"""
+    decay = float(training_cfg.get("ema_decay", 0.9999))
+    if not 0.0 < decay < 1.0:
+        raise ValueError(f"training.ema_decay={decay!r}: must lie in (0, 1)")
+    return bool(training_cfg.get("use_ema", False)), decay
+
+
+def resolve_resume(resume, output_dir: str, prefix: str = "chkpt"):
+    """training.resume_from_checkpoint -> directory to load, or None to start fresh.  "latest": the highest-numbered
+    <prefix>-<step> directory under the run's output_dir (None when there is none); a path: that directory itself."""
+    if not resume:
+        return None
+    if resume != "latest":
+        return str(resume)
+    best, best_step = None, -1
+    if os.path.isdir(output_dir):
+        for name in os.listdir(output_dir):
+            m = re.fullmatch(re.escape(prefix) + r"-(\d+)", name)
+            if m and os.path.isdir(os.path.join(output_dir, name)) and int(m.group(1)) > best_step:
+                best, best_step = os.path.join(output_dir, name), int(m.group(1))
+    return best
+
+
 def run_validation(trainer: HipTrainer, val_dataloader, kl_weight: float, global_step: int, mlog: MetricLogger, device, world: int):
     """train.py:53-97: eval forward with mode(), SUM-reduced MSE and kl().sum(), per-sample averages.
-    Hooks/trackers stay attached, so validation forwards enter the monitor buffer exactly as in the reference."""
-    logger.info(f"--- Running Validation for Global Step: {global_step} ---")
+    Hooks/trackers stay attached, so validation forwards enter the monitor buffer exactly as in the reference.
+    With training.use_ema the pass runs a second time on the averaged weights and logs the same keys under validation_ema/."""
+    m = _validation_pass(trainer, val_dataloader, kl_weight, global_step, mlog, device, world, "validation")
+    if trainer.optimizer.use_ema:
+        with trainer.ema_weights():
+            _validation_pass(trainer, val_dataloader, kl_weight, global_step, mlog, device, world, "validation_ema")
+    return m
+
+
+def _validation_pass(trainer, val_dataloader, kl_weight, global_step, mlog, device, world, prefix):
+    logger.info(f"--- Running Validation for Global Step: {global_step}{' (EMA weights)' if prefix != 'validation' else ''} ---")
     trainer.wrapper.eval()
     sums = torch.zeros(3, device=device, dtype=torch.float64)  # rec_sum, kl_sum, samples
     for batch, ok_everywhere, _ in agreed_batches(val_dataloader, world):
@@ -219,7 +291,7 @@ def run_validation(trainer: HipTrainer, val_dataloader, kl_weight: float, global
     avg_kl = kl_sum / n if n > 0 else 0
     avg = avg_rec + kl_weight * avg_kl
     logger.info(f"  Avg Validation Loss (Total): {avg:.4e}, Rec: {avg_rec:.4e}, KL: {avg_kl:.4e}; validated on {int(n)} samples.")
-    m = {"validation/avg_total_loss": avg, "validation/avg_reconstruction_loss": avg_rec, "validation/avg_kl_divergence": avg_kl}
+    m = {f"{prefix}/avg_total_loss": avg, f"{prefix}/avg_reconstruction_loss": avg_rec, f"{prefix}/avg_kl_divergence": avg_kl}
     mlog.log(m, global_step)
     trainer.wrapper.train()
     return m
@@ -247,6 +319,9 @@ def main():
     grad_ckpt = training_cfg.get("gradient_checkpointing", False)
     if grad_ckpt not in (False, None, "decoder", True):
         raise NotImplementedError(f"training.gradient_checkpointing={grad_ckpt!r}: only 'decoder' exists")
+    # not keys of the reference either: a fused fp32 average of the weights, and continuing from a state save_state wrote
+    use_ema, ema_decay = ema_settings(training_cfg)
+    resume = training_cfg.get("resume_from_checkpoint", None)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -320,7 +395,8 @@ def main():
         eps=training_cfg.get("adam_epsilon", 1e-08), weight_decay=training_cfg.get("adam_weight_decay", 1e-2),
         max_grad_norm=max_grad_norm, kl_weight=kl_weight, lr_warmup_steps=int(training_cfg.get("lr_warmup_steps", 100)),
         max_train_steps=max_train_steps, scheduler_steps_per_update=world,  # accelerate steps the scheduler `world` times
-        mixed_precision=mixed_precision, gradient_accumulation_steps=grad_accum, checkpoint_decoder=bool(grad_ckpt))
+        mixed_precision=mixed_precision, gradient_accumulation_steps=grad_accum, checkpoint_decoder=bool(grad_ckpt),
+        use_ema=use_ema, ema_decay=ema_decay)
 
     core_vae = vae_wrapper.vae
     dnt_cfg = config.get("dead_neuron_tracking", {})
@@ -346,8 +422,18 @@ def main():
 
     logger.info(f"***** Running training: {num_train_epochs} epochs x {steps_per_epoch} steps, batch {bs}/GPU x {world} GPU *****")
     global_step = 0
+    resume_dir = resolve_resume(resume, output_dir, ckpt_prefix)
+    if resume_dir is not None:
+        global_step = load_state(resume_dir, vae_wrapper, trainer, rank)
+        logger.info(f"Resumed from {resume_dir}: continuing after optimizer step {global_step}")
+    elif resume:
+        logger.info(f"resume_from_checkpoint: {resume}: no {ckpt_prefix}-<step> under {output_dir}, starting fresh")
+    first_epoch = global_step // steps_per_epoch
+    # batches of the resumed epoch that the saved updates (and a pending accumulation window) consumed
+    skip_batches = (global_step % steps_per_epoch) * grad_accum + trainer.pending_micro_batches
+    step0 = global_step
     t_start = time.time()
-    for epoch in range(num_train_epochs):
+    for epoch in range(first_epoch, num_train_epochs):
         vae_wrapper.train()
         if hasattr(train_dataloader.sampler, "set_epoch"):
             train_dataloader.sampler.set_epoch(epoch)
@@ -355,6 +441,9 @@ def main():
         steps_in_epoch = 0
         sc = torch.zeros(3, device=device)
         for batch, ok_everywhere, last_batch in agreed_batches(train_dataloader, world):
+            if skip_batches > 0:
+                skip_batches -= 1
+                continue
             if not ok_everywhere:  # all ranks skip the batch, or none does
                 if last_batch and trainer.pending_micro_batches:
                     trainer.flush()  # the pass ends on a skipped batch: update with what has accumulated
@@ -397,7 +486,7 @@ def main():
                     mlog.log({"train_loss_step": step_loss, "lr": trainer.lr_scheduler.get_last_lr()[0], "epoch_current": epoch,
                               **activity_logs}, global_step)
                     logger.info(f"step {global_step}/{max_train_steps} loss {step_loss:.4e} lr {trainer.lr_scheduler.get_last_lr()[0]:.3e} "
-                                f"({(time.time() - t_start) / global_step * 1e3:.0f} ms/step)")
+                                f"({(time.time() - t_start) / (global_step - step0) * 1e3:.0f} ms/step)")
             if dnt and global_step % dnt_interval == 0:
                 dnt.track_dead_neurons(core_vae, global_step)
             if global_step % save_interval == 0 and is_main:
@@ -429,6 +518,9 @@ def main():
         final_dir = os.path.join(output_dir, "final_model")
         save_state(final_dir, vae_wrapper, trainer)
         core_vae.save_pretrained(os.path.join(final_dir, "vae"))  # what evaluate.py loads (evaluate.py:91-102)
+        if use_ema:
+            with trainer.ema_weights():
+                core_vae.save_pretrained(os.path.join(final_dir, "vae_ema"))  # evaluate.py --use_ema
         logger.info(f"Final training state and unwrapped VAE saved under {final_dir}")
         if monitor:
             recs = monitor.export_all_processed_data_to_records()

@@ -1174,3 +1174,10 @@ def adamw(p, g, m, v, sqn: Optional[torch.Tensor], max_norm: float, lr: float, b
           wd: float, step: int):
     lib.call("vae_adamw", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(sqn), float(max_norm), float(lr), float(beta1),
              float(beta2), float(eps), float(wd), int(step), _stream())
+
+
+def adamw_ema(p, g, m, v, e, sqn: Optional[torch.Tensor], max_norm: float, lr: float, beta1: float, beta2: float, eps: float,
+              wd: float, step: int, ema_decay: float):
+    """adamw plus e <- e + (1 - ema_decay) (p' - e) in the same pass (ema_decay == 0: e <- p')"""
+    lib.call("vae_adamw_ema", _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), _p(sqn), float(max_norm), float(lr), float(beta1),
+             float(beta2), float(eps), float(wd), int(step), float(ema_decay), _stream())

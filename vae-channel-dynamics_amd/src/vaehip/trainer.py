@@ -2,6 +2,7 @@
 fwd + loss + bwd (+ bucketed RCCL gradient mean) + fused clip/AdamW + LambdaLR, no host sync."""
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Optional
 
 import torch
@@ -27,7 +28,7 @@ class HipTrainer:
                  kl_weight=1e-6, lr_warmup_steps=100, max_train_steps=1000, scheduler_steps_per_update: int = 1,
                  bucket_mb: float = 64.0, generator: Optional[torch.Generator] = None, mixed_precision: str = "no",
                  gradient_accumulation_steps: int = 1, checkpoint_decoder: bool = False, time_comm: bool = False,
-                 one_rank_exchange: bool = False):
+                 one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999):
         self.wrapper = wrapper
         self.vae = wrapper.vae
         self.kl_weight = float(kl_weight)
@@ -44,7 +45,7 @@ class HipTrainer:
         self.bucket_mb = float(bucket_mb)
         self.time_comm = bool(time_comm)
         self.optimizer = FusedAdamW(self.vae, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                    max_grad_norm=max_grad_norm)
+                                    max_grad_norm=max_grad_norm, use_ema=use_ema, ema_decay=ema_decay)
         self.lr_scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lr_lambda_factory(lr_warmup_steps, max_train_steps))
         # accelerate steps the scheduler num_processes times per optimizer step (accelerate/scheduler.py:72-82)
         self.scheduler_steps_per_update = int(scheduler_steps_per_update)
@@ -166,6 +167,52 @@ class HipTrainer:
         for _ in range(self.scheduler_steps_per_update):
             self.lr_scheduler.step()
         self.global_step += 1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside, the arena holds the averaged weights (and optimizer.ema the raw ones): eval_step, save_pretrained and
+        state_dict read the average, and in bf16 mode the next forward repacks the bf16 image from it.  The two buffers are
+        exchanged back on exit, bit for bit.  Not for use between the micro-batches of one update's backward passes."""
+        opt = self.optimizer
+        if not opt.use_ema:
+            raise RuntimeError("ema_weights(): this trainer was built with use_ema=False")
+        flat = opt._ensure().flat
+
+        def exchange():
+            with torch.no_grad():
+                tmp = flat.clone()
+                flat.copy_(opt.ema)
+                opt.ema.copy_(tmp)
+        exchange()
+        try:
+            yield
+        finally:
+            exchange()
+
+    def state_dict(self) -> dict:
+        """everything a restart needs beside the weights: optimizer (with the weight average), scheduler, step counters,
+        the gradient sum of a pending accumulation window, the generator."""
+        sd = {"optimizer": self.optimizer.state_dict(), "lr_scheduler": self.lr_scheduler.state_dict(),
+              "global_step": self.global_step, "micro_step": self.micro_step,
+              "accum": self._accum.detach().cpu() if (self.micro_step > 0 and self._accum is not None) else None,
+              "generator": self.generator.get_state() if self.generator is not None else None}
+        return sd
+
+    def load_state_dict(self, sd: dict):
+        """the weights must be in the arena already (an optimizer state without an average starts it from them)"""
+        self.optimizer.load_state_dict(sd["optimizer"])
+        self.lr_scheduler.load_state_dict(sd["lr_scheduler"])
+        self.global_step = int(sd["global_step"])
+        self.micro_step = int(sd.get("micro_step", 0))
+        acc = sd.get("accum")
+        if acc is not None:
+            self._accum = acc.to(self.vae.arena.flat.device, dtype=torch.float32).clone()
+        elif self.micro_step:
+            raise ValueError("trainer state has pending micro-batches but no accumulated gradient")
+        if sd.get("generator") is not None:
+            if self.generator is None:
+                raise ValueError("trainer state holds a generator state, but this trainer has no generator")
+            self.generator.set_state(sd["generator"])
 
     def exposed_comm_ms(self) -> float:
         """time the compute stream waited in reducer.finish() since the last call (0 when the exchange was hidden under
