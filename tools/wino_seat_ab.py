@@ -1,4 +1,4 @@
-"""A/B of two (or more) builds of the fp32 Winograd convolutions in one process: this build against the parent commit's
+"""A/B of two (or more) builds of the fp32 Winograd convolutions -- or, `--only bf16`, of the bf16 halo-tile family -- in one process: this build against the parent commit's
 libvaehip.so (built in a scratch worktree; nothing of it is committed), further builds optional (a lever of
 one kernel switched the other way, e.g. conv3_wino4.hip compiled with -DVAE_W4_SWAVE=0 and linked into another file).
 
@@ -19,7 +19,13 @@ With a third library named parent2 (a second copy of the parent's file) the run 
 is twice the largest |median(parent2) / median(parent) - 1| over that kernel's timed cases, and `within_margin` says whether
 the new build's median stays inside it on every case (exit status 2 if not; 1 if anything differs in a bit).
 
-usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up]"""
+`--only bf16`: csrc/conv3_tile_bf16.hip, conv3_wide_bf16.hip and wgrad3_tile_bf16.hip at prec = PREC_BF16 through vae_igemm_rows /
+vae_wgrad (weight image from each library's vae_pack_bf16, operand images tensor.bfloat16(), split count of vae_wgrad_plan unless
+the case fixes one): outputs, `gstat` workspaces, slabs and bias partials bit for bit on the small cases (BF16_SMALL: every path the
+shared header csrc/bf16_tile_common.h owns), which together must launch every instantiation the dispatcher can reach (exit status
+1 otherwise); timed on the 3x3 layers of the bf16 step at 256^2, batch 32 (BF16_STEP).
+
+usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16]"""
 import argparse
 import ctypes as C
 import json
@@ -49,6 +55,50 @@ WINO2 += [("c3", m, 16, hw, hw, ci, co, e, True) for ci, co, hw in [(128, 128, 2
           for m, e in (("fwd", True), ("dgrad", True), ("fwd", "xf"))]
 UP = [("c3up", m, 16, hw, hw, ci, co, False, True) for ci, co, hw in [(512, 512, 32), (512, 512, 64), (256, 256, 128)] for m in ("fwd", "dgrad", "wgrad")]
 
+# ---- the bf16 halo-tile family: ("bf16", form, B, H, W, Cin, Cout, knobs, timed).  Forms: fwd / dgrad of a "c3" layer, up2x (forward
+# over the virtual upsample; its one-pass dgrad is a flat-kernel launch), phase_fwd / phase_dgrad (one phase convolution of an upsampler), wgrad of kind c3 / c3s2 /
+# c3up, wgrad_phase.  Knobs: a16 / x16 / y16 operand as a bf16 image, xf, out16, res, gstat, nobias, pad (ldc = N + pad), ns (split
+# count), opts (library options for the case).  (H, W: the layer's forward input map)
+def _b(form, B, H, W, Ci, Co, timed=False, **knobs):
+    return ("bf16", form, B, H, W, Ci, Co, knobs, timed)
+
+
+_XF3 = (ops.XF_NONE, ops.XF_AFFINE, ops.XF_AFFINE_SILU)
+BF16_SMALL = (
+    # conv3_tile_bf16_kernel: a grid of 30 (no multiple of 8); 640 tiles on 512 workgroups; channel tails; both outputs; residual;
+    # statistics at 4, 8, 16 channels per group; the three transforms; operand images; up2x; a tap-masked phase
+    [_b("fwd", 1, 40, 96, 64, 128, xf=xf) for xf in _XF3] + [_b("up2x", 1, 20, 48, 64, 128, xf=xf) for xf in _XF3]
+    + [_b("fwd", 5, 128, 128, 32, 128, xf=ops.XF_AFFINE_SILU, res=True, gstat=True), _b("fwd", 1, 40, 96, 72, 136, out16=True, res=True),
+       _b("dgrad", 1, 40, 96, 136, 72), _b("dgrad", 1, 40, 96, 64, 128, a16=True, out16=True), _b("fwd", 1, 40, 96, 64, 128, a16=True, out16=True, nobias=True),
+       _b("up2x", 1, 20, 48, 64, 128, a16=True), _b("phase_fwd", 1, 40, 96, 64, 128), _b("phase_dgrad", 1, 40, 96, 64, 128)]
+    + [_b("fwd", 1, 8, 32, 32, Co, gstat=True, out16=o16, res=o16) for Co, o16 in ((128, False), (256, True), (512, False), (512, True))]
+    # conv3_wide_bf16_kernel: 192 tiles (one per workgroup), 320 (one and two), a grid of 253; both directions; the epilogue variants
+    + [_b("fwd", B, 64, 64, 64, 512, a16=True, out16=True, **kn) for B, kn in ((3, {}), (5, {}), (5, {"opts": {"wide_reserved_cus": 3}}), (3, {"pad": 2}))]
+    + [_b("dgrad", B, 64, 64, 512, 64, a16=True, out16=True, **kn) for B, kn in ((3, {}), (5, {"opts": {"wide_reserved_cus": 3}}))]
+    + [_b("fwd", 3, 64, 64, 256, 512, a16=True, out16=o16, res=True, gstat=gs) for o16, gs in ((False, False), (True, False), (True, True), (False, True))]
+    + [_b("fwd", B, 64, 64, 64, Co, a16=True, out16=o16, gstat=True) for B, Co, o16 in ((12, 128, True), (6, 256, False), (6, 256, True))]
+    + [_b("phase_fwd", 3, 64, 64, 64, 512, a16=True, out16=True), _b("phase_dgrad", 3, 64, 64, 512, 64, a16=True, out16=True)]
+    # weight gradients: 0, 1, 2, 5 units per split; split counts that are and are not multiples of 8; a row tail; bias partials on
+    # and off; up2x, stride 2, a tap-masked phase; the storage combinations and transforms of the register-staged kernel
+    + [_b("wgrad", B, H, 32, 64, 128, x16=True, y16=True, ns=ns, nobias=nb) for B, H, ns, nb in ((1, 2, 2, False), (2, 2, 1, True), (1, 10, 1, False), (2, 8, 8, False), (2, 8, 3, True))]
+    + [_b("wgrad", 2, 4, 32, 64, 136, x16=True, y16=True, ns=2), _b("wgrad_c3up", 2, 2, 16, 64, 128, x16=True, y16=True, ns=2),
+       _b("wgrad_c3s2", 2, 8, 64, 64, 128, x16=True, y16=True, ns=3), _b("wgrad_phase", 2, 4, 32, 64, 128, x16=True, y16=True, ns=2)]
+    + [_b(f, 2, 4, 32, 64, 136, x16=x16, y16=y16, xf=xf, ns=2, nobias=x16, opts={"no_wgrad_dma": 1}) for f in ("wgrad", "wgrad_c3up")
+       for x16, xf in ((False, ops.XF_NONE), (True, ops.XF_NONE), (False, ops.XF_AFFINE), (False, ops.XF_AFFINE_SILU)) for y16 in (False, True)])
+_STEP16 = [(128, 128, 256), (256, 128, 256), (256, 256, 128), (512, 256, 128), (512, 512, 64)]
+BF16_STEP = ([_b(m, 32, hw, hw, ci, co, True, a16=True, out16=True, nobias=not e, res=e and m == "fwd", gstat=e and m == "fwd")
+              for ci, co, hw in _STEP16 for m, e in (("fwd", False), ("fwd", True), ("dgrad", False))]
+             + [_b("wgrad", 32, hw, hw, ci, co, True, x16=True, y16=True) for ci, co, hw in _STEP16]
+             + [_b("wgrad_c3s2", 32, hw, hw, c, c, True, x16=True, y16=True) for c, hw in ((128, 256), (256, 128), (512, 64))]
+             + [_b("wgrad_c3up", 32, 64, 64, 256, 256, True, x16=True, y16=True)])
+# every instantiation of the three files that the dispatcher selects (conv3_tile_eligible refuses a fused transform on a dgrad)
+TF = ("false", "true")
+BF16_NAMES = ({f"conv3_tile_bf16_kernel<{TF[dg]},{TF[up]},{xf},{TF[i]}>" for dg, up in ((0, 0), (0, 1), (1, 0)) for xf, i in ((0, 0), (0, 1), (1, 0), (2, 0))
+               if not (dg and xf)}
+              | {f"conv3_wide_bf16_kernel<{TF[dg]},{ks}>" for dg in (0, 1) for ks in (2, 3)}
+              | {f"wgrad3_tile_bf16_kernel<{TF[up]},{xf},{TF[x]},{TF[y]}>" for up in (0, 1) for xf, x in ((0, 0), (0, 1), (1, 0), (2, 0)) for y in (0, 1)}
+              | {"wgrad3_dma_bf16_kernel<false,1>", "wgrad3_dma_bf16_kernel<false,2>", "wgrad3_dma_bf16_kernel<true,1>"})
+
 
 def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
@@ -62,13 +112,16 @@ def _open(path):
                           ("vae_wino_weights", C.c_int, [ia, vp, vp]), ("vae_conv_gstat_chunks", C.c_int, [ia]), ("vae_conv_gnb_chunks", C.c_int, [ia]),
                           ("vae_igemm_kernel_name", C.c_int, [ia, C.c_char_p, C.c_int32]), ("vae_wgrad_wino", C.c_int, [wa, vp]),
                           ("vae_wgrad_wino_plan", C.c_int, [wa, C.POINTER(C.c_int32)]), ("vae_wgrad_wino_positions", C.c_int, [wa]),
-                          ("vae_set_option", C.c_int, [C.c_char_p, C.c_int32])):
+                          ("vae_set_option", C.c_int, [C.c_char_p, C.c_int32]), ("vae_pack_bf16", C.c_int, [vp, C.c_int64, vp, vp]),
+                          ("vae_wgrad", C.c_int, [wa, vp]), ("vae_wgrad_plan", C.c_int, [wa, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+                          ("vae_wgrad_kernel_name", C.c_int, [wa, C.c_char_p, C.c_int32])):
         getattr(dll, fn).restype, getattr(dll, fn).argtypes = res, argt
     return dll
 
 
 def _bits(a, b):
-    return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+    v = torch.int16 if a.element_size() == 2 else torch.int32
+    return bool(torch.equal(a.view(v), b.view(v)))
 
 
 class Case:
@@ -151,12 +204,103 @@ class Case:
         return launch, outs, (a, wu)
 
 
+class Bf16Case:
+    """operands of one case of the bf16 halo-tile family, filled once; arm(dll) -> (launch function, outputs of that arm)"""
+
+    def __init__(self, dev, kind, form, B, H, W, Ci, Co, kn):
+        self.dev, self.form, self.kn, self.dims, self.opts = dev, form, kn, (B, H, W, Ci, Co), kn.get("opts", {})
+        g = torch.Generator(device=dev).manual_seed(11 + Ci + 3 * Co + H + B + len(form))
+        self.wkind = form.split("_")[1] if form.startswith("wgrad_c3") else "c3"
+        up = form in ("up2x", "phase_fwd", "phase_dgrad") or self.wkind == "c3up"
+        Hy, Wy = (2 * H, 2 * W) if up else ops.out_hw(self.wkind, H, W)
+        if form == "wgrad_phase":
+            Hy, Wy = 2 * H, 2 * W  # (dY is read at every second pixel)
+        self.w = torch.randn((Co, 3, 3, Ci), device=dev, generator=g) / math.sqrt(9 * Ci)
+        self.x = torch.randn((B, H, W, Ci), device=dev, generator=g) * 1.3 + 0.2
+        self.dy = torch.randn((B, Hy, Wy, Co), device=dev, generator=g)
+        self.bias = torch.randn((Co,), device=dev, generator=g)
+        self.scale, self.shift = torch.rand((B, Ci), device=dev, generator=g) + 0.5, torch.randn((B, Ci), device=dev, generator=g)
+        self.x16, self.dy16 = self.x.bfloat16(), self.dy.bfloat16()
+        self.res = None
+
+    def _wgrad_arm(self, dll, st):
+        B, H, W, Ci, Co = self.dims
+        kn, dev, nan = self.kn, self.dev, float("nan")
+        a = (ops.wgrad_phase_args(B, H, W, Co, Ci, prec=ops.PREC_BF16) if self.form == "wgrad_phase"
+             else ops.wgrad_args(self.wkind, B, H, W, Ci, Co, Ci, xf=kn.get("xf", ops.XF_NONE), prec=ops.PREC_BF16))
+        a.dY, a.X = _p(self.dy16 if kn.get("y16") else self.dy), _p(self.x)
+        a.dY16, a.X16 = _p(self.dy16) if kn.get("y16") else None, _p(self.x16) if kn.get("x16") else None
+        if a.xf:
+            a.scale, a.shift = _p(self.scale), _p(self.shift)
+        n, fus = C.c_int32(0), C.c_int32(0)
+        assert dll.vae_wgrad_plan(C.byref(a), C.byref(n), C.byref(fus)) == 0 and n.value > 0 and (fus.value or not a.xf)
+        ns = kn.get("ns", n.value)
+        slab = torch.full((ns, 9 * Ci * Co), nan, device=dev)
+        a.nsplit, a.partial, a.out = ns, _p(slab), _p(slab)
+        outs = {"slab": slab}
+        if not kn.get("nobias"):
+            outs["bias_partial"] = torch.full((ns, Co), nan, device=dev)
+            a.bias_partial = _p(outs["bias_partial"])
+        buf = C.create_string_buffer(128)
+        dll.vae_wgrad_kernel_name(C.byref(a), buf, 128)
+        self.kernel = buf.value.decode()
+
+        def launch():
+            rc = dll.vae_wgrad(C.byref(a), st)
+            assert rc == 0, rc
+        return launch, outs, (a,)
+
+    def arm(self, dll, st):
+        if self.form.startswith("wgrad"):
+            return self._wgrad_arm(dll, st)
+        B, H, W, Ci, Co = self.dims
+        kn, dev, form = self.kn, self.dev, self.form
+        dg = form in ("dgrad", "phase_dgrad")
+        if form in ("phase_fwd", "phase_dgrad"):
+            a = ops.phase_args(B, H, W, Co, Ci, dg, prec=ops.PREC_BF16)
+        elif dg:
+            a = ops.dgrad_args("c3", B, H, W, Co, Ci, prec=ops.PREC_BF16)
+        else:
+            a = ops.fwd_args("c3up" if form == "up2x" else "c3", B, H, W, Ci, Co, Ci, xf=kn.get("xf", ops.XF_NONE), prec=ops.PREC_BF16)
+        src, src16 = (self.dy, self.dy16) if dg else (self.x, self.x16)
+        full = form not in ("phase_fwd",) and not kn.get("pad")  # (a phase forward writes every second pixel, a padded row its first N columns)
+        oshape = (B, H, W, a.N + kn.get("pad", 0)) if dg else (B, *self.dy.shape[1:3], a.N + kn.get("pad", 0))
+        odt = torch.bfloat16 if kn.get("out16") else torch.float32
+        out = torch.full(oshape, float("nan") if full else 0.0, device=dev, dtype=odt)
+        wh = torch.full((self.w.numel(),), float("nan"), device=dev, dtype=torch.bfloat16)
+        assert dll.vae_pack_bf16(_p(self.w), self.w.numel(), _p(wh), st) == 0
+        a.A, a.A16, a.W, a.Wh, a.C, a.ldc = _p(src), _p(src16) if kn.get("a16") else None, _p(self.w), _p(wh), _p(out), oshape[-1]
+        a.out_bf16 = int(bool(kn.get("out16")))
+        a.bias = None if (kn.get("nobias") or dg) else _p(self.bias)
+        if a.xf:
+            a.scale, a.shift = _p(self.scale), _p(self.shift)
+        outs = {"out": out, "Wh": wh}
+        if kn.get("res"):
+            if self.res is None:
+                self.res = torch.randn(oshape, device=dev, generator=torch.Generator(device=dev).manual_seed(5)).to(odt)
+            a.res, a.res_bf16 = _p(self.res), a.out_bf16
+        if kn.get("gstat"):
+            a.gstat_groups = 32
+            nch = dll.vae_conv_gstat_chunks(C.byref(a))
+            assert nch > 0, "no statistics epilogue for this case"
+            outs["gstat"] = torch.full((B, nch, 32, 2), float("nan"), device=dev)
+            a.gstat = _p(outs["gstat"])
+        buf = C.create_string_buffer(128)
+        dll.vae_igemm_kernel_name(C.byref(a), buf, 128)
+        self.kernel = buf.value.decode()
+
+        def launch():
+            rc = dll.vae_igemm_rows(C.byref(a), st)
+            assert rc == 0, rc
+        return launch, outs, (a, wh)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs="+", help="NEW.so PARENT.so [name=OTHER.so ...]")
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up"])
+    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16"])
     arg = ap.parse_args()
     assert len(arg.libs) >= 2, "two libraries: this build and the parent's"
     names = ["new", "parent"] + [s.split("=", 1)[0] for s in arg.libs[2:]]
@@ -164,13 +308,17 @@ def main():
     dev = torch.device("cuda:0")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     cases = WINO2 if arg.only == "wino2" else (STEP + SMALL if arg.only != "up" else []) + (UP if arg.only != "wino4" else [])
+    if arg.only == "bf16":
+        cases = BF16_SMALL + BF16_STEP
     for d in dlls:  # (an option of the library, so of every copy)
         d.vae_set_option(b"no_wino4", 1 if arg.only == "wino2" else 0)
     rows, all_equal = [], True
     for kind, mode, B, H, W, Ci, Co, epi, timed in cases:
-        c = Case(dev, kind, mode, B, H, W, Ci, Co, epi)
+        c = (Bf16Case if kind == "bf16" else Case)(dev, kind, mode, B, H, W, Ci, Co, epi)
         first, eq, launches, keep = None, {}, [], []
         for i, d in enumerate(dlls):  # one arm's outputs at a time beside the first's
+            for o, v in getattr(c, "opts", {}).items():  # (a library option the case runs under: set on every copy, cleared below)
+                d.vae_set_option(o.encode(), v)
             launch, outs, alive = c.arm(d, st)
             launch()
             torch.cuda.synchronize()
@@ -207,6 +355,9 @@ def main():
                     row[f"{nm}_over_parent"] = round(row[nm]["median_ms"] / row["parent"]["median_ms"], 4)
         print(json.dumps(row), flush=True)
         rows.append(row)
+        for d in dlls:
+            for o in getattr(c, "opts", {}):
+                d.vae_set_option(o.encode(), 0)
         del c, first, launches, keep
         torch.cuda.empty_cache()
     res = {"libs": dict(zip(names, [os.path.basename(s.split("=", 1)[-1]) for s in arg.libs])), "launches_per_arm": arg.launches,
@@ -225,6 +376,10 @@ def main():
     timed_rows = [r for r in rows if "parent" in r and "wino4" in r["kernel"]]
     if timed_rows:  # the step's F(4x4) launches, one of each: sum of the medians per arm
         res["wino4_sum_of_medians_ms"] = {nm: round(sum(r[nm]["median_ms"] for r in timed_rows), 4) for nm in names}
+    if arg.only == "bf16":  # the small cases together reach every instantiation the dispatcher selects
+        res["instantiations_not_launched"] = sorted(BF16_NAMES - {r["kernel"] for r in rows if "parent" not in r})
+        print("instantiations not launched:", res["instantiations_not_launched"])
+        all_equal = all_equal and not res["instantiations_not_launched"]
     if arg.out:
         with open(arg.out, "w") as f:
             json.dump(res, f, indent=1)

@@ -314,7 +314,7 @@ int conv3_tile_gstat_chunks(const vae_igemm_args& a) {
   return (g.Wo / TW) * (g.Ho / TH);
 }
 
-int launch_conv3_tile(const vae_igemm_args& a, bool bkm, hipStream_t st) {
+int launch_conv3_tile(const vae_igemm_args& a, hipStream_t st) {
   const vae_conv_geom& g = a.g;
   const int tx = g.Wo / TW, ty = g.Ho / TH;
   const int64_t nblk = (int64_t)((a.N + BN - 1) / BN) * tx * ty * g.B;

@@ -22,25 +22,18 @@
 //     (the next step's weight wait then does not wait for the slower HBM halo loads);
 // Forward reads both operands as 16-byte k-contiguous fragments; dgrad keeps the weight tile in its memory order
 // ([k = co][n = ci]) and reads it with the transposing LDS load (ds_read_b64_tr_b16).
-#include "bf16_frag.h"
-#include <algorithm>
+#include "bf16_tile_common.h"
 #include <type_traits>
+
+using namespace bf16_tile;
+using namespace bf16_tile::conv;  // the schedule, weight stage and epilogue pieces shared with conv3_wide_bf16.hip
 
 namespace {
 
-constexpr int BK = 32, TH = 4, TW = 32, HW_ = TW + 2, HP = (TH + 2) * HW_;  // 204 halo pixels
-constexpr int LDH = BK + 8;                 // halo row stride in bf16 (80 B: conflict-free ds_read_b128)
-constexpr int BN = 128, NT = 256;
+constexpr int TH = 4, HP = (TH + 2) * HW_;  // 204 halo pixels
 constexpr int SH = HP * LDH;                // halo stage (bf16 elements)
 constexpr int HQ = HP * (BK / 4);           // float4 slots of one halo (1632)
 constexpr int HI = (HQ + NT - 1) / NT;      // 7
-constexpr int LDBK = BK + 8;                // weight tile [n][k] row stride (forward)
-constexpr int LDBN = BN + 32;               // weight tile [k][n] row stride (dgrad): 320 B => tr reads conflict-free
-constexpr int SB1 = BN * LDBK;              // one tap of a weight stage; BN * LDBK == BK * LDBN
-static_assert(BN * LDBK == BK * LDBN, "forward and dgrad weight tiles have the same LDS size");
-constexpr int SB = 3 * SB1;                 // weight stage: the 3 taps of one kernel row
-
-struct TileId { int b, y0, x0, n0, lin; };
 
 template <bool DG, bool UP, int XF, bool A16>
 __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p, int tiles_x, int tiles_y, int ntiles) {
@@ -64,35 +57,17 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
   const int rmask = ((tmask & 7) ? 1 : 0) | (((tmask >> 3) & 7) ? 2 : 0) | (((tmask >> 6) & 7) ? 4 : 0);
   const int cmask = (tmask | (tmask >> 3) | (tmask >> 6)) & 7;
   const int kw0 = (cmask & 1) ? 0 : 1, ngrp = 2 * __builtin_popcount(cmask);  // active columns kw0.., 2 k-groups each
-  const size_t img_bytes = (size_t)(g.Hs * as) * (g.Ws * as) * g.Cs * 4u;
   const auto rsW = VAE_BUF_RSRC(p.Wh, (size_t)(DG ? p.K * p.sk : p.N * p.sn) * 2u);
   const int Hb = UP ? 2 * g.Hs : g.Hs, Wb = UP ? 2 * g.Ws : g.Ws;
   const int kchunks = (p.K + BK - 1) / BK;
   const int steps = 3 * kchunks;            // one step = one kernel row (3 taps) of one channel chunk
 
-  // persistent schedule: consecutive logical ids (co-tile / x neighbours, which share halo rows) run on the same
-  // XCD (hardware places workgroup i on XCD i % 8) and therefore meet in the same L2
   const int G = gridDim.x;
-  const int first = (G % 8 == 0) ? (blockIdx.x % 8) * (G / 8) + blockIdx.x / 8 : blockIdx.x;
-  auto decode = [&](int t) {
-    TileId id;
-    id.lin = t / tilesN;
-    const int tn = t - id.lin * tilesN;
-    int r = id.lin;
-    const int tx = r % tiles_x; r /= tiles_x;
-    const int ty = r % tiles_y;
-    id.b = r / tiles_y;
-    id.y0 = ty * TH; id.x0 = tx * TW; id.n0 = tn * BN;
-    return id;
-  };
+  const int first = first_tile(G, blockIdx.x);
+  auto decode = [&](int t) { return conv::decode<TH>(t, tilesN, tiles_x, tiles_y); };
 
   f32x16 acc[2][2];  // [row of the wave's row pair][32-channel block]
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  clear_acc(acc);
 
   // ---- operand staging (register-staged) ----
   constexpr int NW = 3 * BN * BK / 8 / NT;  // 6 uint4 of bf16 weights per thread and step
@@ -108,13 +83,13 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
   // addresses and masks out of the persistent loop and keep them in VGPRs (60+ registers, i.e. spills at the
   // 256-register budget of 2 waves per SIMD); recomputing them costs a few VALU instructions per step.
   auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
-  auto load_halo = [&](const TileId& id, int c0, bool valid) {
+  auto load_halo = [&](const Tile& id, int c0, bool valid) {
     const unsigned Hv = valid ? (unsigned)Hb : 0u;  // an invalid request: every row out of range (no branch on `valid`)
     const int ltid = opaque(tid), hk4 = ltid & (BK / 4 - 1);  // the thread's 4 channels: same for all its slots
     if (A16) {
       const int hk8 = ltid & (BK / 8 - 1);
       const int c8 = c0 + hk8 * 8;
-      const auto rsA16 = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.A16) + (int64_t)id.b * g.Hs * g.Ws * g.Cs, img_bytes / 2);
+      const auto rsA16 = image_rsrc(reinterpret_cast<const u16*>(p.A16), id.b, g.Hs, g.Ws, g.Cs);
 #pragma unroll
       for (int i = 0; i < HI16; ++i) {
         const int q = ltid + NT * i;
@@ -129,7 +104,7 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
     }
     hmask = 0;
     const int c = c0 + hk4 * 4;
-    const auto rsA = VAE_BUF_RSRC(p.A + (int64_t)id.b * (g.Hs * as) * (g.Ws * as) * g.Cs, img_bytes);
+    const auto rsA = image_rsrc(p.A, id.b, g.Hs * as, g.Ws * as, g.Cs);
     if (XF != VAE_XF_NONE) {
       const int cs = min(c, p.K - 4);
       rsc = *reinterpret_cast<const f32x4*>(p.scale + (int64_t)id.b * g.Cs + cs);
@@ -195,7 +170,7 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
     for (int i = 0; i < NW; ++i) {
       const int tap = kh * 3 + (i >> 1);
       const int rem = ltid + NT * (i & 1);
-      unsigned off;
+      unsigned off;  // (as in conv3_wide_bf16.hip; behind a shared function this kernel's VGPR count moves by 7-10)
       if (!DG) {
         const int n = n0 + (rem >> 2), c = c0 + (rem & 3) * 8;
         off = (n < Nv && c < p.K) ? (unsigned)((n * (int)p.sn + tap * (int)p.st + c) * 2) : BUF_OOB;
@@ -209,14 +184,10 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
   auto store_w = [&](const uint4* srcreg, u16* sB) {
     const int ltid = opaque(tid);
 #pragma unroll
-    for (int i = 0; i < NW; ++i) {
-      const int rem = ltid + NT * (i & 1);
-      u16* dst = sB + (i >> 1) * SB1 + (DG ? (rem >> 4) * LDB + (rem & 15) * 8 : (rem >> 2) * LDB + (rem & 3) * 8);
-      *reinterpret_cast<uint4*>(dst) = srcreg[i];
-    }
+    for (int i = 0; i < NW; ++i) *reinterpret_cast<uint4*>(sB + weight_piece_lds<DG>(i, ltid + NT * (i & 1))) = srcreg[i];
   };
 
-  // lane's address pattern for the transposing read: group row q, column quad pp
+  // lane's address pattern for the transposing read: group row q, column quad pp (shared with bBase below they cost dgrad 3 registers)
   const int trq = (lane & 15) >> 2, trp = lane & 3, trh = (lane >> 4) & 1;
   // one step: 6 MFMA groups (3 taps x 2 k-groups of 16 channels), each 2 pixel-row x 2 channel-block fragments and
   // 4 MFMAs; the fragments of group i+1 are requested before the MFMAs of group i are issued
@@ -265,7 +236,7 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
 
   int t = first;
   if (t >= ntiles) return;  // uniform per workgroup
-  TileId cur = decode(t);
+  Tile cur = decode(t);
   // Every step issues the same loads in the same order (a request that has no target -- nothing follows the last
   // tile -- is made with every lane out of range): hipcc's waitcnt pass then knows exactly how many younger loads may
   // stay in flight at each wait.  With conditional loads it assumes the fewest and waits for the halo at every step.
@@ -280,7 +251,7 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
   while (true) {
     const int tnext = t + G;
     const bool has_next = tnext < ntiles;
-    const TileId nxt = decode(has_next ? tnext : t);
+    const Tile nxt = decode(has_next ? tnext : t);
     for (int cch = 0; cch < kchunks; ++cch) {
       const bool last = cch + 1 == kchunks;
       // where the chunk after this one lives: this tile's next chunk, or the first chunk of the next tile (if any)
@@ -315,9 +286,8 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
     // outputs and the residual go through buffer descriptors over this tile's image: a pixel / channel outside the
     // tensor is an out-of-range offset (load reads 0, store is dropped), so the 16 residual loads of a block are issued
     // back to back and there is no branch per element
-    const size_t obytes = (size_t)(g.Ho * cs) * (g.Wo * cs) * p.ldc * 4u;
-    const auto rsC = VAE_BUF_RSRC(p.C + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, obytes);
-    const auto rsR = VAE_BUF_RSRC((p.res ? p.res : p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, obytes);
+    const auto rsC = image_rsrc(p.C, cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
+    const auto rsR = image_rsrc(p.res ? p.res : p.C, cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
     float tsum[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, gs1[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, gs2[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
     float gpv[2][2] = {{0.f, 0.f}, {0.f, 0.f}};  // statistics as shifted sums around the lane's first value
     // the bias values of this lane's channels, loaded once per tile before the first store (per block each load sat behind the
@@ -341,12 +311,10 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
       for (int ni = 0; ni < 2; ++ni) {
         const int col = cur.n0 + wn * 64 + ni * 32 + lr;
         const bool colok = col < p.N && oy < g.Ho;
-        if (p.out_bf16) {  // uniform: bf16 output.  Adjacent lanes hold adjacent channels of the same pixels: they swap every other
-          // register, so each lane ends up with two channels of 8 pixels (4-byte stores, 4-byte loads of the bf16 residual); the
-          // statistics describe the ROUNDED values (see conv3_wide_bf16.hip); no tracker with it
-          const size_t ob16 = (size_t)(g.Ho * cs) * (g.Wo * cs) * p.ldc * 2u;
-          const auto rsC16 = VAE_BUF_RSRC(reinterpret_cast<u16*>(p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, ob16);
-          const auto rsR16 = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.res ? p.res : p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, ob16);
+        if (p.out_bf16) {  // uniform: bf16 output (pack_pair: a lane ends up with two channels of 8 pixels; 4-byte stores, 4-byte loads
+          // of the bf16 residual); the statistics describe the ROUNDED values (see conv3_wide_bf16.hip); no tracker with it
+          const auto rsC16 = image_rsrc(reinterpret_cast<u16*>(p.C), cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
+          const auto rsR16 = image_rsrc(reinterpret_cast<const u16*>(p.res ? p.res : p.C), cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
           const bool odd = lr & 1;
           const float b0 = pbias[ni][0], b1 = pbias[ni][1];  // (rows beyond the image: the stores are out of range)
           unsigned o16[8], rr[8];
@@ -363,18 +331,10 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
           }
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            const float a0 = p.alpha * acc[mi][ni][2 * j], a1 = p.alpha * acc[mi][ni][2 * j + 1];
-            const float recv = lane_xor1(odd ? a0 : a1);
-            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-            bf16x2_t h;
-            h[0] = (__bf16)((odd ? recv : a0) + b0 + __builtin_bit_cast(float, rr[j] << 16));
-            h[1] = (__bf16)((odd ? a1 : recv) + b1 + __builtin_bit_cast(float, rr[j] & 0xffff0000u));
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h), rsC16, o16[j], 0, 0);
-            const float q0 = (float)h[0], q1 = (float)h[1];
-            if (j == 0) gpv[mi][ni] = q0;
-            const float d0 = q0 - gpv[mi][ni], d1 = q1 - gpv[mi][ni];
-            gs1[mi][ni] += d0 + d1;
-            gs2[mi][ni] += d0 * d0 + d1 * d1;
+            const Pair16 h = pack_pair<true>(p.alpha * acc[mi][ni][2 * j], p.alpha * acc[mi][ni][2 * j + 1], odd, b0, b1, rr[j]);  // (no residual: + 0)
+            __builtin_amdgcn_raw_buffer_store_b32(h.word, rsC16, o16[j], 0, 0);
+            if (j == 0) gpv[mi][ni] = h.q0;
+            shifted_add_pair(gpv[mi][ni], gs1[mi][ni], gs2[mi][ni], h.q0, h.q1);
             acc[mi][ni][2 * j] = 0.f;
             acc[mi][ni][2 * j + 1] = 0.f;
           }
@@ -399,30 +359,18 @@ __global__ __launch_bounds__(NT, 2) void conv3_tile_bf16_kernel(vae_igemm_args p
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, off[r], 0, 0);
           tsum[mi][ni] += (off[r] != BUF_OOB) ? fabsf(v) : 0.f;
           if (r == 0) gpv[mi][ni] = v;
-          const float dv = v - gpv[mi][ni];  // (the statistics epilogue only runs on full tiles)
-          gs1[mi][ni] += dv;
-          gs2[mi][ni] += dv * dv;
+          shifted_add(gpv[mi][ni], gs1[mi][ni], gs2[mi][ni], v);
           acc[mi][ni][r] = 0.f;
         }
       }
     }
-    if (p.gstat) {  // uniform: GroupNorm moments of this tile's outputs, layout of vae_gn_stats_partial with one chunk per wave-row
-      // band of the tile (2 rows x 32 pixels): the lane's two rows are merged in place, the group's lanes by DPP moves, and the
-      // first lane writes -- no LDS round trip, no barrier (see conv3_wide_bf16.hip)
+    if (p.gstat) {  // uniform: GroupNorm moments of this tile's outputs, one chunk per wave-row band (2 rows x 32 pixels): the
+      // lane's two rows are merged in place, then gstat_write
       const int cpg = p.N / p.gstat_groups;  // channels per group (4, 8 or 16)
-      const int tile_in_img = cur.lin - cur.b * (tiles_x * tiles_y);
-      float* gbase = p.gstat + (((int64_t)cur.b * (tiles_x * tiles_y) + tile_in_img) * 2 + wm) * p.gstat_groups * 2;
+      float* gbase = gstat_band(p, cur, tiles_x, tiles_y, wm);
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const MeanM2 rows = mm2_merge_equal(mm2_from_shifted(gpv[0][ni], gs1[0][ni], gs2[0][ni], 16.f),
-                                            mm2_from_shifted(gpv[1][ni], gs1[1][ni], gs2[1][ni], 16.f), 16.f);
-        const MeanM2 a = mm2_wave_group(rows, cpg, 32.f);
-        if (lh == 0 && (lr & (cpg - 1)) == 0) {
-          float* o = gbase + ((cur.n0 + wn * 64 + ni * 32 + lr) / cpg) * 2;
-          o[0] = a.m;
-          o[1] = a.M2;
-        }
-      }
+      for (int ni = 0; ni < 2; ++ni)
+        gstat_write(rows2(gpv[0][ni], gs1[0][ni], gs2[0][ni], gpv[1][ni], gs1[1][ni], gs2[1][ni]), 32.f, cpg, gbase, cur.n0 + wn * 64 + ni * 32 + lr, lr, lh);
     }
     if (p.track) {  // uniform; the last loop barrier separated the halo reads from this reuse of its space
       float* red = reinterpret_cast<float*>(smem);  // [4 rows][BN] fp32 = 2 KB of the 16 KB halo stage
@@ -462,26 +410,17 @@ void launch_xf(const vae_igemm_args& a, dim3 grid, int tx, int ty, int nt, hipSt
 }  // namespace
 
 // chunks per image of the statistics epilogue: one per 2-row band of a 4 x 32-pixel tile (0 = not available for these arguments)
-int conv3_tile_bf16_gstat_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (a.gstat_groups <= 0 || a.N % BN != 0 || a.N % a.gstat_groups != 0 || g.mode == VAE_MODE_DGRAD || a.c_step > 1) return 0;
-  const int cpg = a.N / a.gstat_groups;
-  if (cpg != 4 && cpg != 8 && cpg != 16) return 0;
-  return (g.Wo / TW) * (g.Ho / 2);
-}
+int conv3_tile_bf16_gstat_chunks(const vae_igemm_args& a) { return gstat_chunks(a, 2, false); }
 
 // the kernel reads the weights from their bf16 image in 16-byte (8-element) pieces: they must be aligned and never
 // straddle a row end
 bool conv3_tile_bf16_packed(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  const size_t as = a.a_step > 1 ? a.a_step : 1, cs = a.c_step > 1 ? a.c_step : 1;
-  const bool fits32 = (size_t)g.Hs * g.Ws * g.Cs * 4u * as * as < BUF_MAX && (size_t)g.Ho * g.Wo * a.ldc * 4u * cs * cs < BUF_MAX &&  // one image per descriptor
-                      (size_t)std::max((int64_t)a.K * a.sk, (int64_t)a.N * a.sn) * 2u < BUF_MAX;
-  return a.Wh != nullptr && aligned16(a.Wh) && aligned16(a.A) && fits32 && a.K % 8 == 0 && a.N % 8 == 0 && a.st % 8 == 0 &&
+  const bool fits32 = descriptors_fit(a.g, a.a_step, a.ldc, a.c_step, std::max((int64_t)a.K * a.sk, (int64_t)a.N * a.sn), a.Wh, a.A);
+  return a.Wh != nullptr && fits32 && a.K % 8 == 0 && a.N % 8 == 0 && a.st % 8 == 0 &&
          (a.sn == 1 || a.sn % 8 == 0) && (a.sk == 1 || a.sk % 8 == 0);
 }
 
-int launch_conv3_tile_bf16(const vae_igemm_args& a, bool bkm, hipStream_t st) {
+int launch_conv3_tile_bf16(const vae_igemm_args& a, hipStream_t st) {
   const vae_conv_geom& g = a.g;
   if (!conv3_tile_bf16_packed(a)) return VAE_EINVAL;
   const int tx = g.Wo / TW, ty = g.Ho / TH;

@@ -25,30 +25,22 @@
 // {kw0, kw0+1} of the 3x3 window on the low-resolution grid -- 2 stages per chunk, 2 kernel rows per stage (16 of the 36
 // tap-MACs per low-resolution pixel are computed, none masked), operand pixel (y,x) at (y*a_step+a_oy, x*a_step+a_ox) of the
 // image, output pixel at (y*c_step+c_oy, x*c_step+c_ox).
-#include "bf16_frag.h"
+#include "bf16_tile_common.h"
 #ifndef VAE_ABLATE
 #define VAE_ABLATE 0
 #endif
-#include <algorithm>
 #include <type_traits>
+
+using namespace bf16_tile;
+using namespace bf16_tile::conv;  // the schedule, weight stage and epilogue pieces shared with conv3_tile_bf16.hip
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr int BK = 32, TH = 8, TW = 32, HW_ = TW + 2, HROWS = TH + 2, HP = HROWS * HW_;  // 340 halo pixels
-constexpr int LDH = BK + 8;        // halo pixel stride in bf16 (80 B: conflict-free 16-byte row reads)
+constexpr int TH = 8, HROWS = TH + 2, HP = HROWS * HW_;  // 340 halo pixels
 constexpr int SH = HP * LDH;       // one halo buffer (13600 bf16 = 27200 B)
-constexpr int BN = 128, NT = 256;
-constexpr int LDBK = BK + 8;       // forward weight tile [n][k]
-constexpr int LDBN = BN + 32;      // dgrad weight tile [k][n] (320 B rows: the transposing reads are conflict-free)
-constexpr int SB1 = BN * LDBK;     // one tap (5120 bf16); BN * LDBK == BK * LDBN
-static_assert(BN * LDBK == BK * LDBN, "forward and dgrad weight tiles have the same LDS size");
-constexpr int SB = 3 * SB1;        // one stage: the 3 taps of a kernel column (30720 B)
 constexpr int LDS_BYTES = (2 * SH + 3 * SB) * 2;  // 146560 B
 constexpr int HQ = HP * (BK / 8);                 // 1360 x 16 B halo slots
 constexpr int HI = (HQ + NT - 1) / NT;            // 6 per thread
-
-struct Tile { int b, y0, x0, n0, lin; };
 
 template <bool DG, int KS>
 __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p, int tiles_x, int tiles_y, int ntiles, int kh0, int kw0) {
@@ -69,30 +61,14 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
   const int tilesN = (p.N + BN - 1) / BN;
   const int nch = (p.K + BK - 1) / BK;
   const int as = (KS == 2 && p.a_step > 1) ? p.a_step : 1, cs = (KS == 2 && p.c_step > 1) ? p.c_step : 1;
-  const size_t img_bytes = (size_t)(g.Hs * as) * (g.Ws * as) * g.Cs * 2u;
   const auto rsW = VAE_BUF_RSRC(p.Wh, (size_t)(DG ? p.K * p.sk : p.N * p.sn) * 2u);
 
   const int G = gridDim.x;
-  const int first = (G % 8 == 0) ? (blockIdx.x % 8) * (G / 8) + blockIdx.x / 8 : blockIdx.x;  // neighbours share an XCD's L2
-  auto decode = [&](int t) {
-    Tile id;
-    id.lin = t / tilesN;
-    const int tn = t - id.lin * tilesN;
-    int r = id.lin;
-    const int tx = r % tiles_x; r /= tiles_x;
-    const int ty = r % tiles_y;
-    id.b = r / tiles_y;
-    id.y0 = ty * TH; id.x0 = tx * TW; id.n0 = tn * BN;
-    return id;
-  };
+  const int first = first_tile(G, blockIdx.x);
+  auto decode = [&](int t) { return conv::decode<TH>(t, tilesN, tiles_x, tiles_y); };
 
   f32x16 acc[4][2];  // [output row of the wave][32-channel block]
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[r][ni][e] = 0.f;
+  clear_acc(acc);
 
   // ---------------- staging: global -> registers -> LDS, one piece (16 B per thread) at a time ----------------
   // weight stream: the position of the NEXT stage to request (tile, chunk, kernel column)
@@ -127,9 +103,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
     }
   };
   auto w_store_piece = [&](int set, int i, u16* sB) {
-    const int rem = tid + NT * (i & 1);
-    u16* dst = sB + (i >> 1) * SB1 + (DG ? (rem >> 4) * LDB + (rem & 15) * 8 : (rem >> 2) * LDB + (rem & 3) * 8);
-    *reinterpret_cast<uint4*>(dst) = rw[set][i];
+    *reinterpret_cast<uint4*>(sB + weight_piece_lds<DG>(i, tid + NT * (i & 1))) = rw[set][i];
   };
   // halo stream: the NEXT channel chunk to request
   int h_t = first, h_c = 0;
@@ -142,7 +116,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
     const int hy = h_id.y0 - 1 + ir, hx = h_id.x0 - 1 + jc;
     const int c = h_c * BK + k8 * 8;
     const bool ok = h_ok && (q < HQ) && ((unsigned)hy < (unsigned)g.Hs) && ((unsigned)hx < (unsigned)g.Ws) && (c < p.K);
-    const auto rsA = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.A16) + (int64_t)h_id.b * (g.Hs * as) * (g.Ws * as) * g.Cs, img_bytes);
+    const auto rsA = image_rsrc(reinterpret_cast<const u16*>(p.A16), h_id.b, g.Hs * as, g.Ws * as, g.Cs);
     const unsigned off = (KS == 2) ? (unsigned)((((hy * as + p.a_oy) * (g.Ws * as) + hx * as + p.a_ox) * g.Cs + c) * 2)
                                    : (unsigned)(((hy * g.Ws + hx) * g.Cs + c) * 2);
     rh[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, ok ? off : BUF_OOB, 0, 0));
@@ -323,15 +297,13 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
 
     // ---------------- epilogue ----------------
     TSTAMP(1);
-    const size_t obytes = (size_t)(g.Ho * cs) * (g.Wo * cs) * p.ldc * 4u;
-    const auto rsC = VAE_BUF_RSRC(p.C + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, obytes);
-    const auto rsR = VAE_BUF_RSRC((p.res ? p.res : p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, obytes);
+    const auto rsC = image_rsrc(p.C, cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
+    const auto rsR = image_rsrc(p.res ? p.res : p.C, cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
     float gs1[4][2], gs2[4][2], gpv[4][2];  // statistics as shifted sums around the lane's first value
     if (p.out_bf16) {
-      // bf16 output (uniform): adjacent lanes hold adjacent channels of the same 16 pixels; they swap every other register, so a
-      // lane ends up with BOTH channels of its pair at 8 pixels, adds the bias of both (and the bf16 residual, res_bf16: 4-byte
-      // loads) and rounds once.  The statistics epilogue below sums the ROUNDED values (the tensor as stored); a lane's 16 values
-      // still belong to one group, so the group merge is the same as for fp32 outputs.
+      // bf16 output (uniform): pack_pair leaves a lane with BOTH channels of its pair at 8 pixels (the bf16 residual, res_bf16: 4-byte
+      // loads).  The statistics epilogue below sums the ROUNDED values (the tensor as stored); a lane's 16 values still belong to
+      // one group, so the group merge is the same as for fp32 outputs.
       // Without a residual (every dgrad, conv1 of a block) the rounded pairs then go through two more exchanges -- lanes 2 apart
       // (quad permute, 4 channels x 4 pixels), lanes 4 apart (bank-masked row shifts, 8 channels x 2 pixels) -- and leave as TWO
       // 16-byte stores per 32 x 32 block instead of eight 4-byte ones.  One wave per SIMD, nothing beside it: the 64 store
@@ -340,9 +312,8 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
       // per (residual, statistics, wide stores): without them the residual and statistics arithmetic ran on zeros (21 vector
       // instructions per pair of values where a dgrad needs 11).
       const bool odd = lr & 1, bit1 = lr & 2;
-      const size_t ob16 = (size_t)(g.Ho * cs) * (g.Wo * cs) * p.ldc * 2u;
-      const auto rsC16 = VAE_BUF_RSRC(reinterpret_cast<u16*>(p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, ob16);
-      const auto rsR16 = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.res ? p.res : p.C) + (int64_t)cur.b * (g.Ho * cs) * (g.Wo * cs) * p.ldc, ob16);
+      const auto rsC16 = image_rsrc(reinterpret_cast<u16*>(p.C), cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
+      const auto rsR16 = image_rsrc(reinterpret_cast<const u16*>(p.res ? p.res : p.C), cur.b, g.Ho * cs, g.Wo * cs, p.ldc);
       const unsigned pstep = (unsigned)(cs * p.ldc * 2);  // bytes per pixel step of the row grid
       // (the bias: once per tile, see the top of the tile loop.  Loaded per 16-pixel block, each load sat behind the previous block's
       // stores and its wait -- vmcnt counts stores too -- made every block wait for the write acknowledgements of the one before)
@@ -386,27 +357,12 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
             unsigned P[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-              const float a0 = acc[r][ni][2 * j], a1 = acc[r][ni][2 * j + 1];
-              const float recv = lane_xor1(odd ? a0 : a1);
-              typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-              bf16x2_t h;
-              float v0 = (odd ? recv : a0) + b0, v1 = (odd ? a1 : recv) + b1;
-              if constexpr (RES) {
-                v0 += __builtin_bit_cast(float, rr[q][j] << 16);
-                v1 += __builtin_bit_cast(float, rr[q][j] & 0xffff0000u);
-              }
-              h[0] = (__bf16)v0;
-              h[1] = (__bf16)v1;
-              P[j] = __builtin_bit_cast(unsigned, h);
+              const Pair16 h = pack_pair<RES>(acc[r][ni][2 * j], acc[r][ni][2 * j + 1], odd, b0, b1, RES ? rr[q][j] : 0u);
+              P[j] = h.word;
               if constexpr (!WIDE) __builtin_amdgcn_raw_buffer_store_b32(P[j], rsC16, off2(r, ni, j), 0, 0);
               if constexpr (GST) {  // ONE pivot for the lane's 64 values of a channel block (its first), two independent chains of sums
-                const float q0 = (float)h[0], q1 = (float)h[1];
-                if (r == 0 && j == 0) spv[ni] = q0;
-                const float d0 = q0 - spv[ni], d1 = q1 - spv[ni];  // (the statistics epilogue only runs on full tiles)
-                sv1[ni][0] += d0;
-                sv1[ni][1] += d1;
-                sv2[ni][0] = fmaf(d0, d0, sv2[ni][0]);
-                sv2[ni][1] = fmaf(d1, d1, sv2[ni][1]);
+                if (r == 0 && j == 0) spv[ni] = h.q0;
+                shifted_add_pair_fma(spv[ni], sv1[ni], sv2[ni], h.q0, h.q1);
               }
               acc[r][ni][2 * j] = 0.f;
               acc[r][ni][2 * j + 1] = 0.f;
@@ -490,9 +446,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
             const float v = acc[r][ni][e] + bv + rv[q][e];
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, offset(r, ni, e), 0, 0);
             if (e == 0) gpv[r][ni] = v;
-            const float dv = v - gpv[r][ni];  // (the statistics epilogue only runs on full tiles)
-            gs1[r][ni] += dv;
-            gs2[r][ni] += dv * dv;
+            shifted_add(gpv[r][ni], gs1[r][ni], gs2[r][ni], v);
             acc[r][ni][e] = 0.f;
           }
         }
@@ -504,26 +458,17 @@ __global__ __launch_bounds__(NT, 1) void conv3_wide_bf16_kernel(vae_igemm_args p
       // DPP moves, and the first lane of a group writes -- no LDS round trip, no workgroup barrier (the tile-level merge of round 2
       // cost 3.5 us per tile, tools/wide_timing.py)
       const int cpg = p.N / p.gstat_groups;  // channels per group (4, 8 or 16)
-      const int tile_in_img = cur.lin - cur.b * (tiles_x * tiles_y);
-      float* gbase = p.gstat + (((int64_t)cur.b * (tiles_x * tiles_y) + tile_in_img) * 2 + wm) * p.gstat_groups * 2;
+      float* gbase = gstat_band(p, cur, tiles_x, tiles_y, wm);
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         MeanM2 lane64;
         if (p.out_bf16) {  // uniform: one set of shifted sums over the lane's 64 values
           lane64 = mm2_from_shifted(gpv[0][ni], gs1[0][ni], gs2[0][ni], 64.f);
         } else {
-          const MeanM2 r01 = mm2_merge_equal(mm2_from_shifted(gpv[0][ni], gs1[0][ni], gs2[0][ni], 16.f),
-                                             mm2_from_shifted(gpv[1][ni], gs1[1][ni], gs2[1][ni], 16.f), 16.f);
-          const MeanM2 r23 = mm2_merge_equal(mm2_from_shifted(gpv[2][ni], gs1[2][ni], gs2[2][ni], 16.f),
-                                             mm2_from_shifted(gpv[3][ni], gs1[3][ni], gs2[3][ni], 16.f), 16.f);
-          lane64 = mm2_merge_equal(r01, r23, 32.f);
+          lane64 = mm2_merge_equal(rows2(gpv[0][ni], gs1[0][ni], gs2[0][ni], gpv[1][ni], gs1[1][ni], gs2[1][ni]),
+                                   rows2(gpv[2][ni], gs1[2][ni], gs2[2][ni], gpv[3][ni], gs1[3][ni], gs2[3][ni]), 32.f);
         }
-        const MeanM2 a = mm2_wave_group(lane64, cpg, 64.f);
-        if (lh == 0 && (lr & (cpg - 1)) == 0) {
-          float* o = gbase + ((cur.n0 + wn * 64 + ni * 32 + lr) / cpg) * 2;
-          o[0] = a.m;
-          o[1] = a.M2;
-        }
+        gstat_write(lane64, 64.f, cpg, gbase, cur.n0 + wn * 64 + ni * 32 + lr, lr, lh);
       }
     }
     TSTAMP(3);
@@ -574,26 +519,18 @@ bool conv3_wide_bf16_eligible(const vae_igemm_args& a) {
     if (!phase_block(a.tapmask, &kh0, &kw0) || a.gstat) return false;
     if ((a.a_step > 1 && a.a_step != 2) || (a.c_step > 1 && a.c_step != 2)) return false;
   }
-  const size_t as = a.a_step > 1 ? a.a_step : 1, cs = a.c_step > 1 ? a.c_step : 1;
   if (!(g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_DGRAD) || g.Ho != g.Hs || g.Wo != g.Ws) return false;
   if (g.Wo % TW != 0 || g.Ho % TH != 0 || a.K % (2 * BK) != 0 || a.N % 8 != 0 || a.N <= 32 || g.Cs % 8 != 0 || a.st % 8 != 0) return false;
   if (g.mode == VAE_MODE_FWD && !(a.sk == 1 && a.sn % 8 == 0)) return false;
   if (g.mode == VAE_MODE_DGRAD && !(a.sn == 1 && a.sk % 8 == 0)) return false;
   // storage: the operand comes as an image (A16; a_bf16 is the flat kernels' flag); a bf16 output takes a bf16 residual, an fp32 one an fp32 one
   if (a.a_bf16 || (a.out_bf16 && a.ldc % 2 != 0) || (a.res != nullptr && (a.res_bf16 != 0) != (a.out_bf16 != 0))) return false;
-  if (!aligned16(a.A16) || !aligned16(a.Wh)) return false;
-  if ((size_t)g.Hs * g.Ws * g.Cs * 4u * as * as >= BUF_MAX || (size_t)g.Ho * g.Wo * a.ldc * 4u * cs * cs >= BUF_MAX) return false;
-  if ((size_t)std::max((int64_t)a.K * a.sk, (int64_t)a.N * a.sn) * 2u >= BUF_MAX) return false;
+  if (!descriptors_fit(g, a.a_step, a.ldc, a.c_step, std::max((int64_t)a.K * a.sk, (int64_t)a.N * a.sn), a.A16, a.Wh)) return false;
   const int64_t nt = (int64_t)((a.N + BN - 1) / BN) * (g.Wo / TW) * (g.Ho / TH) * g.B;
   return nt >= 192 && nt <= 0x7fffffffLL;
 }
-int conv3_wide_bf16_gstat_chunks(const vae_igemm_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (a.gstat_groups <= 0 || a.N % BN != 0 || a.N % a.gstat_groups != 0 || g.mode == VAE_MODE_DGRAD || a.c_step > 1 || a.tapmask != 0) return 0;
-  const int cpg = a.N / a.gstat_groups;
-  if (cpg != 4 && cpg != 8 && cpg != 16) return 0;
-  return (g.Wo / TW) * (g.Ho / 4);  // one chunk per wave-row band of a tile (4 rows x 32 pixels x the group's channels)
-}
+// one chunk per wave-row band of a tile (4 rows x 32 pixels x the group's channels); none for a phase convolution
+int conv3_wide_bf16_gstat_chunks(const vae_igemm_args& a) { return gstat_chunks(a, 4, a.tapmask != 0); }
 
 template <bool DG, int KS>
 static int launch_wide(const vae_igemm_args& a, int tx, int ty, int64_t nt, int kh0, int kw0, hipStream_t st) {

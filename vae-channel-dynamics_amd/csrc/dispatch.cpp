@@ -425,8 +425,8 @@ extern "C" int vae_igemm_rows(const vae_igemm_args* ap, void* stream) {
     case RowsKernel::Wino4: rc = launch_conv3_wino4(a, a.Wu, st); what = "conv3_wino4"; break;
     case RowsKernel::Wino: rc = launch_conv3_wino(a, a.Wu, st); what = "conv3_wino"; break;
     case RowsKernel::WideBf16: rc = launch_conv3_wide_bf16(a, st); what = "conv3_wide_bf16"; break;
-    case RowsKernel::TileBf16: rc = launch_conv3_tile_bf16(a, s.bkm, st); what = "conv3_tile_bf16"; break;
-    case RowsKernel::Tile: rc = launch_conv3_tile(a, s.bkm, st); what = "conv3_tile"; break;
+    case RowsKernel::TileBf16: rc = launch_conv3_tile_bf16(a, st); what = "conv3_tile_bf16"; break;
+    case RowsKernel::Tile: rc = launch_conv3_tile(a, st); what = "conv3_tile"; break;
     case RowsKernel::ThinBf16: rc = launch_conv_thin_bf16(a, st); what = "conv_thin_bf16"; break;
     case RowsKernel::SmallK: rc = launch_conv_smallk(a, st); what = "conv_smallk"; break;
     case RowsKernel::ThinnBf16: rc = launch_conv_thinn_bf16(a, st); what = "conv_thinn_bf16"; break;

@@ -14,10 +14,10 @@ int launch_wgrad_bf16(const vae_wgrad_args& a, hipStream_t st);
 // conv3_tile.hip / conv3_tile_bf16.hip: 3x3 stride-1 halo tiles (fp32 / bf16; the two share the tile shape and epilogue layout)
 bool conv3_tile_eligible(const vae_igemm_args& a, bool vec, bool bkm);
 int conv3_tile_gstat_chunks(const vae_igemm_args& a);
-int launch_conv3_tile(const vae_igemm_args& a, bool bkm, hipStream_t st);
+int launch_conv3_tile(const vae_igemm_args& a, hipStream_t st);
 bool conv3_tile_bf16_packed(const vae_igemm_args& a);  // the bf16 image of the weights the bf16 kernel reads
 int conv3_tile_bf16_gstat_chunks(const vae_igemm_args& a);
-int launch_conv3_tile_bf16(const vae_igemm_args& a, bool bkm, hipStream_t st);
+int launch_conv3_tile_bf16(const vae_igemm_args& a, hipStream_t st);
 // conv3_wide_bf16.hip: both operands bf16 images, 8 x 32-pixel tiles
 bool conv3_wide_bf16_eligible(const vae_igemm_args& a);
 int conv3_wide_bf16_gstat_chunks(const vae_igemm_args& a);

@@ -13,46 +13,26 @@
 // the earlier 32 co x 64 ci split read 1 + 6 = 7 KB for the same 6 MFMAs).
 // Two kernels: wgrad3_tile_bf16_kernel stages through registers (any storage combination, fused GroupNorm / SiLU of X); wgrad3_dma_bf16_kernel
 // (further down; both operands as bf16 images, stride 1 or 2) stages by LDS-DMA into swizzled images -- what a bf16 step runs.
-#include "bf16_frag.h"
+#include "bf16_tile_common.h"
 #ifndef VAE_ABLATE
 #define VAE_ABLATE 0  // diagnostic builds (tools/ablation_builds.sh, wrong results): bit 0 no global loads / DMA pieces fetch nothing, 1 no LDS stores, 4 no barrier
 #endif
 
+using namespace bf16_tile;
+using namespace bf16_tile::wgrad;  // roles, unit cursor, slab and bias tails: what the two kernels of this file share
+
 namespace {
 
-
-constexpr int TH = 2, TW = 32, UPX = TH * TW;   // 64 pixels per unit
+constexpr int TH = 2, UPX = TH * TW;            // 64 pixels per unit
 constexpr int HWD = TW + 2, HPX = (TH + 2) * HWD;  // 136 halo pixels
-constexpr int BMT = 128, BNT = 64;
 constexpr int LDA = BMT + 32;                   // dY image row stride (320 B: tr reads conflict-free)
 constexpr int LDH = BNT + 32;                   // halo image row stride (192 B)
 constexpr int SA = UPX * LDA, SH = HPX * LDH;   // u16 elements
 constexpr int STAGE = SA + SH;
-constexpr int NT = 768;
 constexpr int AQ = UPX * (BMT / 4);             // dY float4 slots (2048)
 constexpr int AI = (AQ + NT - 1) / NT;          // 3
 constexpr int HQ = HPX * (BNT / 4);             // halo float4 slots (2176)
 constexpr int HI = (HQ + NT - 1) / NT;          // 3
-
-
-
-// Workgroup id -> (column = (co tile, ci tile), split).  The hardware deals consecutive workgroup ids round-robin over the 8 XCDs
-// (one L2 each).  The columns of one split stream through the SAME pixels at the same pace (every ci tile re-reads the dY rows,
-// every co tile the X halo): with id = column + columns * split the 8 columns of a 256 -> 256 layer sat on 8 different XCDs and
-// every L2 fetched the split's pixels for itself -- 1.08 GB per launch from the memory side, 3.9 TB/s, which is what the staging
-// cost (the kernel ran 0.276 ms with its DMA pieces, 0.218 with the same instructions fetching nothing).  Here XCD x takes the
-// splits congruent x mod 8, all columns of a split together: one L2 fetches a split's pixels once.
-__device__ __forceinline__ void wg_column_split(int nsplit, int& column, int& split) {
-  const int cols = gridDim.x, L = blockIdx.y * cols + blockIdx.x;
-  if (nsplit % 8 == 0) {
-    const int j = L >> 3;
-    column = j % cols;
-    split = (j / cols) * 8 + (L & 7);
-  } else {
-    column = blockIdx.x;
-    split = blockIdx.y;
-  }
-}
 
 // Y16: dY comes as a bf16 image (vae_wgrad_args.dY16): 16-byte loads written to LDS as they are
 template <bool UP, int XF, bool X16, bool Y16>
@@ -61,31 +41,15 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
   __shared__ __attribute__((aligned(16))) u16 smem[2 * STAGE + SSB];
   float* sS = reinterpret_cast<float*>(smem + 2 * STAGE);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 31, lh = lane >> 5;
-  const int mt = wave & 1, nt = (wave >> 1) & 1, tg = wave >> 2;  // 64-row co block, 32-column ci block, filter row kh
-  const int trq = (lane & 15) >> 2, trp = lane & 3, trh = (lane >> 4) & 1;
+  const Role ro = role<UP>(p, tiles_x, tiles_y, nunits);
+  const int tid = ro.tid, lr = ro.lr, lh = ro.lh, mt = ro.mt, nt = ro.nt, tg = ro.tg, trq = ro.trq, trp = ro.trp, trh = ro.trh;
+  const int m0 = ro.m0, n0 = ro.n0, nu = ro.nu, Hb = ro.Hb, Wb = ro.Wb, ys = ro.ys, wmask = ro.wmask;
+  const bool do_bias = ro.do_bias;
   const vae_conv_geom g = p.g;
-  const int tilesN = p.N / BNT;
-  int colw, split;
-  wg_column_split(p.nsplit, colw, split);
-  const int tm = colw / tilesN, tn = colw % tilesN;
-  const int m0 = tm * BMT, n0 = tn * BNT;
-  const int64_t per = (nunits + p.nsplit - 1) / p.nsplit;
-  const int64_t ubeg = split * per, uend = min(nunits, ubeg + per);
-  const int nu = (int)max((int64_t)0, uend - ubeg);
-  const int Hb = UP ? 2 * g.Hs : g.Hs, Wb = UP ? 2 * g.Ws : g.Ws;
-  const bool do_bias = (p.bias_partial != nullptr) && tn == 0;
-  const int units_per_img = tiles_x * tiles_y;
-  // phase convolutions of an upsampler (vaehip.h): dY is a sub-sampled view (pixel (y,x) at (y*ys+y_oy, x*ys+y_ox)) and only the
-  // taps of tapmask are computed -- a wave whose kernel row is masked out only helps with the staging, the others skip the
-  // masked columns (their accumulators stay zero and are written as zeros)
-  const int ys = (!UP && p.y_step > 1) ? p.y_step : 1;
-  const int wmask = ((p.tapmask ? p.tapmask : 0x1ff) >> (3 * tg)) & 7;
 
-  const int b_lo = nu > 0 ? (int)(ubeg / units_per_img) : 0;
+  const int b_lo = nu > 0 ? (int)(ro.ubeg / ro.units_per_img) : 0;
   if (XF != VAE_XF_NONE && nu > 0) {
-    const int nb = (int)((uend - 1) / units_per_img) - b_lo + 1;
+    const int nb = (int)((ro.uend - 1) / ro.units_per_img) - b_lo + 1;
     const int nent = min(nb * BNT, SS_HALF);
     for (int i = tid; i < nent; i += NT) {
       const int j = i / BNT, c = i - j * BNT;
@@ -95,12 +59,7 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
   }
 
   f32x16 acc[3][2];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][mi][r] = 0.f;
+  clear_acc(acc);
 
   // with a bf16 activation image (X16) a halo slot is 8 channels = one 16-byte load, written to LDS as it is
   constexpr int HQ16 = HPX * (BNT / 8), HI16 = (HQ16 + NT - 1) / NT;  // 1088 slots, 2 per thread
@@ -120,32 +79,20 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
     return wave_s * 64 + l;
   };
 
-  // the unit to request next, decoded once and then advanced (image, tile row, tile column): no division per step
-  int nb_ = 0, nty_ = 0, ntx_ = 0, nleft_ = nu;
-  if (nu > 0) {
-    nb_ = (int)(ubeg / units_per_img);
-    const int rem = (int)(ubeg - (int64_t)nb_ * units_per_img);
-    nty_ = rem / tiles_x;
-    ntx_ = rem - nty_ * tiles_x;
-  }
+  UnitCursor cursor(ro, tiles_x);
   auto load_regs = [&]() {
     const int tid = fresh_tid();
     const int a4 = tid & 31;  // dY column quad (NT % 32 == 0: the same for every slot of this thread)
-    const bool valid = nleft_ > 0;
+    const Unit un = cursor.next(tiles_x, tiles_y);
+    const bool valid = un.valid;
     const int AQv = valid ? AQ : 0;
     const unsigned Hv = valid ? (unsigned)Hb : 0u;
-    const int b = nb_;
-    const int y0 = nty_ * TH, x0 = ntx_ * TW;
-    --nleft_;
-    if (++ntx_ == tiles_x) {
-      ntx_ = 0;
-      if (++nty_ == tiles_y) { nty_ = 0; ++nb_; }
-    }
+    const int b = un.b;
+    const int y0 = un.ty * TH, x0 = un.tx * TW;
     // buffer descriptors (common.h) over this unit's image of dY and of X: out-of-range offsets read zeros
-    const auto rsX = VAE_BUF_RSRC(p.X + (int64_t)b * g.Hs * g.Ws * g.Cs, (size_t)g.Hs * g.Ws * g.Cs * 4u);
+    const auto rsX = image_rsrc(p.X, b, g.Hs, g.Ws, g.Cs);
     if (Y16) {
-      const auto rsY16 = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.dY16) + (int64_t)b * (g.Ho * ys) * (g.Wo * ys) * p.ldy,
-                                      (size_t)(g.Ho * ys) * (g.Wo * ys) * p.ldy * 2u);
+      const auto rsY16 = image_rsrc(reinterpret_cast<const u16*>(p.dY16), b, g.Ho * ys, g.Wo * ys, p.ldy);
       const int AQ16v = valid ? AQ16 : 0;
 #pragma unroll
       for (int i = 0; i < AI16; ++i) {
@@ -155,7 +102,7 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
         ra16[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsY16, (q < AQ16v && c < p.M) ? (unsigned)((pix * p.ldy + c) * 2) : BUF_OOB, 0, 0));
       }
     } else {
-      const auto rsY = VAE_BUF_RSRC(p.dY + (int64_t)b * (g.Ho * ys) * (g.Wo * ys) * p.ldy, (size_t)(g.Ho * ys) * (g.Wo * ys) * p.ldy * 4u);
+      const auto rsY = image_rsrc(p.dY, b, g.Ho * ys, g.Wo * ys, p.ldy);
 #pragma unroll
       for (int i = 0; i < (Y16 ? 1 : AI); ++i) {
         const int q = tid + NT * i;
@@ -166,7 +113,7 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
       }
     }
     if (X16) {
-      const auto rsX16 = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.X16) + (int64_t)b * g.Hs * g.Ws * g.Cs, (size_t)g.Hs * g.Ws * g.Cs * 2u);
+      const auto rsX16 = image_rsrc(reinterpret_cast<const u16*>(p.X16), b, g.Hs, g.Ws, g.Cs);
 #pragma unroll
       for (int i = 0; i < HI16; ++i) {
         const int q = tid + NT * i;
@@ -204,13 +151,7 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
         const int q = tid + NT * i;
         if (q < AQ16) {
           *reinterpret_cast<uint4*>(&sA[(q >> 4) * LDA + (q & 15) * 8]) = ra16[i];
-          if (do_bias) {  // column sums of the bf16 values, in fp32 (NT % 16 == 0: a thread keeps its 8 columns)
-            const uint4 r = ra16[i];
-            bsum[0] += __builtin_bit_cast(float, r.x << 16); bsum[1] += __builtin_bit_cast(float, r.x & 0xffff0000u);
-            bsum[2] += __builtin_bit_cast(float, r.y << 16); bsum[3] += __builtin_bit_cast(float, r.y & 0xffff0000u);
-            bsum2[0] += __builtin_bit_cast(float, r.z << 16); bsum2[1] += __builtin_bit_cast(float, r.z & 0xffff0000u);
-            bsum2[2] += __builtin_bit_cast(float, r.w << 16); bsum2[3] += __builtin_bit_cast(float, r.w & 0xffff0000u);
-          }
+          if (do_bias) add_bf16x8(bsum, bsum2, ra16[i]);  // column sums of the bf16 values, in fp32 (NT % 16 == 0: a thread keeps its 8 columns)
         }
       }
     } else {
@@ -301,49 +242,8 @@ __global__ __launch_bounds__(NT) void wgrad3_tile_bf16_kernel(vae_wgrad_args p, 
     }
   }
 
-  const int64_t ld = (int64_t)9 * p.N;
-  float* __restrict__ O = (p.nsplit == 1 ? p.out : p.partial + (int64_t)split * p.M * ld);
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int tap = tg * 3 + t;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const int col = n0 + nt * 32 + lr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + mt * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < p.M) O[(int64_t)row * ld + (int64_t)tap * p.N + col] = p.alpha * acc[t][mi][r];
-      }
-    }
-  }
-  if (do_bias && Y16) {
-    f32x4* red = reinterpret_cast<f32x4*>(smem);  // [NT/16][16][2]: thread t holds columns (t & 15) * 8 .. + 7
-    red[tid * 2] = bsum;
-    red[tid * 2 + 1] = bsum2;
-    __syncthreads();
-    if (tid < BMT / 4) {  // quad `tid` of the 128 columns = half (tid & 1) of column group tid >> 1
-      f32x4 t4 = {0.f, 0.f, 0.f, 0.f};
-      for (int r = 0; r < NT / 16; ++r) t4 += red[(r * 16 + (tid >> 1)) * 2 + (tid & 1)];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + tid * 4 + e;
-        if (m < p.M) p.bias_partial[(int64_t)split * p.M + m] = t4[e];
-      }
-    }
-  } else if (do_bias) {
-    f32x4* red = reinterpret_cast<f32x4*>(smem);  // [NT/32][32]
-    red[tid] = bsum;
-    __syncthreads();
-    if (tid < BMT / 4) {
-      f32x4 t4 = {0.f, 0.f, 0.f, 0.f};
-      for (int r = 0; r < NT / 32; ++r) t4 += red[r * 32 + tid];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + tid * 4 + e;
-        if (m < p.M) p.bias_partial[(int64_t)split * p.M + m] = t4[e];
-      }
-    }
-  }
+  store_slab(p, ro, acc);
+  if (do_bias) bias_reduce<Y16 ? 2 : 1>(reinterpret_cast<f32x4*>(smem), p, ro, bsum, bsum2);  // uniform
 }
 
 
@@ -384,32 +284,15 @@ __global__ __launch_bounds__(NT) void wgrad3_dma_bf16_kernel(vae_wgrad_args p, i
   constexpr int NKG = UPXS / 16;                                    // 16-pixel k-groups of a unit
   extern __shared__ __attribute__((aligned(1024))) unsigned char dsm[];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 31, lh = lane >> 5;
-  const int mt = wave & 1, nt = (wave >> 1) & 1, tg = wave >> 2;  // 64-row co block, 32-column ci block, filter row kh
-  const int trq = (lane & 15) >> 2, trp = lane & 3, trh = (lane >> 4) & 1;
+  const Role ro = role<UP>(p, tiles_x, tiles_y, nunits);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;  // (the lane's own constants spelled out: taken from `ro` this kernel needs one register more)
+  const int lh = lane >> 5, mt = wave & 1, nt = (wave >> 1) & 1, tg = wave >> 2, trq = (lane & 15) >> 2, trp = lane & 3, trh = (lane >> 4) & 1;
+  const int m0 = ro.m0, n0 = ro.n0, nu = ro.nu, Hb = ro.Hb, Wb = ro.Wb, ys = ro.ys, wmask = ro.wmask;
+  const bool do_bias = ro.do_bias;
   const vae_conv_geom g = p.g;
-  const int tilesN = p.N / BNT;
-  int colw, split;
-  wg_column_split(p.nsplit, colw, split);
-  const int tm = colw / tilesN, tn = colw % tilesN;
-  const int m0 = tm * BMT, n0 = tn * BNT;
-  const int64_t per = (nunits + p.nsplit - 1) / p.nsplit;
-  const int64_t ubeg = split * per, uend = min(nunits, ubeg + per);
-  const int nu = (int)max((int64_t)0, uend - ubeg);
-  const int Hb = UP ? 2 * g.Hs : g.Hs, Wb = UP ? 2 * g.Ws : g.Ws;
-  const bool do_bias = (p.bias_partial != nullptr) && tn == 0;
-  const int units_per_img = tiles_x * tiles_y;
-  const int ys = (!UP && p.y_step > 1) ? p.y_step : 1;
-  const int wmask = ((p.tapmask ? p.tapmask : 0x1ff) >> (3 * tg)) & 7;
 
   f32x16 acc[3][2];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][mi][r] = 0.f;
+  clear_acc(acc);
 
   // ---- this lane's share of the wave's three pieces: what it fetches (per-unit part added in request()) ----
   // piece id = 3 wave + j: 0..15 dY (pixels 4 id ..), 16..32 halo (halo pixels 8 (id - 16) ..), 33..35 nothing
@@ -435,41 +318,25 @@ __global__ __launch_bounds__(NT) void wgrad3_dma_bf16_kernel(vae_wgrad_args p, i
     }
   }
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)dsm);
-  // the unit to request next (image, tile row, tile column), advanced without divisions
-  int nb_ = 0, nty_ = 0, ntx_ = 0, nleft_ = nu;
-  if (nu > 0) {
-    nb_ = (int)(ubeg / units_per_img);
-    const int rem = (int)(ubeg - (int64_t)nb_ * units_per_img);
-    nty_ = rem / tiles_x;
-    ntx_ = rem - nty_ * tiles_x;
-  }
+  UnitCursor cursor(ro, tiles_x);
   auto request = [&](int buf) {  // the three pieces of the next unit into stage `buf`; beyond the range: descriptors of size 0 (zeros)
-    const bool valid = nleft_ > 0;
-    const int b = nb_, y0 = nty_ * UTH, x0 = ntx_ * TW;
-    --nleft_;
-    if (++ntx_ == tiles_x) {
-      ntx_ = 0;
-      if (++nty_ == tiles_y) { nty_ = 0; ++nb_; }
-    }
+    const Unit un = cursor.next(tiles_x, tiles_y);
+    const int b = un.b, y0 = un.ty * UTH, x0 = un.tx * TW;
+    // (image_rsrc with a size of 0, spelled out: through the shared function every request costs five more scalar instructions)
     const size_t ybytes = (size_t)(g.Ho * ys) * (g.Wo * ys) * p.ldy * 2u, xbytes = (size_t)g.Hs * g.Ws * g.Cs * 2u;
-    const auto rsY = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.dY16) + (int64_t)b * (g.Ho * ys) * (g.Wo * ys) * p.ldy, valid ? ybytes : (size_t)0);
-    const auto rsX = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.X16) + (int64_t)b * g.Hs * g.Ws * g.Cs, valid ? xbytes : (size_t)0);
+    const auto rsY = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.dY16) + (int64_t)b * (g.Ho * ys) * (g.Wo * ys) * p.ldy, un.valid ? ybytes : (size_t)0);
+    const auto rsX = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.X16) + (int64_t)b * g.Hs * g.Ws * g.Cs, un.valid ? xbytes : (size_t)0);
     const unsigned ybase = (unsigned)((((y0 * ys + p.y_oy) * (g.Wo * ys) + x0 * ys + p.y_ox) * p.ldy) * 2);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)buf * (unsigned)DSTAGE + (unsigned)(wave * 3 + j) * 1024u);
-      unsigned keep;
       if (kind[j] == 0) {  // uniform
-        const unsigned off = yoff[j] == BUF_OOB ? BUF_OOB : yoff[j] + ybase;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "s"(dst), "v"(off), "s"(rsY) : "memory");
+        dma_piece(dst, yoff[j] == BUF_OOB ? BUF_OOB : yoff[j] + ybase, rsY);
       } else {
         const int hy = STR == 2 ? 2 * y0 + hir[j] : y0 - 1 + hir[j], hx = STR == 2 ? 2 * x0 + hjc[j] : x0 - 1 + hjc[j];
         const bool ok = kind[j] == 1 && ((unsigned)hy < (unsigned)Hb) && ((unsigned)hx < (unsigned)Wb) && hc[j] < p.N;
         const int sy = UP ? (hy >> 1) : hy, sx = UP ? (hx >> 1) : hx;
-        const unsigned off = ok ? (unsigned)(((sy * g.Ws + sx) * g.Cs + hc[j]) * 2) : BUF_OOB;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "s"(dst), "v"(off), "s"(rsX) : "memory");
+        dma_piece(dst, ok ? (unsigned)(((sy * g.Ws + sx) * g.Cs + hc[j]) * 2) : BUF_OOB, rsX);
       }
     }
   };
@@ -540,13 +407,7 @@ __global__ __launch_bounds__(NT) void wgrad3_dma_bf16_kernel(vae_wgrad_args p, i
   auto bias_sums = [&](const unsigned char* st) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      if (bofs[i] >= 0) {
-        const uint4 r = *reinterpret_cast<const uint4*>(st + bofs[i]);
-        bsum[0] += __builtin_bit_cast(float, r.x << 16); bsum[1] += __builtin_bit_cast(float, r.x & 0xffff0000u);
-        bsum[2] += __builtin_bit_cast(float, r.y << 16); bsum[3] += __builtin_bit_cast(float, r.y & 0xffff0000u);
-        bsum2[0] += __builtin_bit_cast(float, r.z << 16); bsum2[1] += __builtin_bit_cast(float, r.z & 0xffff0000u);
-        bsum2[2] += __builtin_bit_cast(float, r.w << 16); bsum2[3] += __builtin_bit_cast(float, r.w & 0xffff0000u);
-      }
+      if (bofs[i] >= 0) add_bf16x8(bsum, bsum2, *reinterpret_cast<const uint4*>(st + bofs[i]));
     }
   };
 
@@ -570,36 +431,8 @@ __global__ __launch_bounds__(NT) void wgrad3_dma_bf16_kernel(vae_wgrad_args p, i
     __syncthreads();
   }
 
-  const int64_t ld = (int64_t)9 * p.N;
-  float* __restrict__ O = (p.nsplit == 1 ? p.out : p.partial + (int64_t)split * p.M * ld);
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int tap = tg * 3 + t;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const int col = n0 + nt * 32 + lr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + mt * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < p.M) O[(int64_t)row * ld + (int64_t)tap * p.N + col] = p.alpha * acc[t][mi][r];
-      }
-    }
-  }
-  if (do_bias) {
-    f32x4* red = reinterpret_cast<f32x4*>(dsm);  // [NT/16][16][2]: thread t holds columns (t & 15) * 8 .. + 7
-    red[tid * 2] = bsum;
-    red[tid * 2 + 1] = bsum2;
-    __syncthreads();
-    if (tid < BMT / 4) {  // quad `tid` of the 128 columns = half (tid & 1) of column group tid >> 1
-      f32x4 t4 = {0.f, 0.f, 0.f, 0.f};
-      for (int r = 0; r < NT / 16; ++r) t4 += red[(r * 16 + (tid >> 1)) * 2 + (tid & 1)];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + tid * 4 + e;
-        if (m < p.M) p.bias_partial[(int64_t)split * p.M + m] = t4[e];
-      }
-    }
-  }
+  store_slab(p, ro, acc);
+  if (do_bias) bias_reduce<2>(reinterpret_cast<f32x4*>(dsm), p, ro, bsum, bsum2);  // uniform
 }
 
 }  // namespace
@@ -614,17 +447,15 @@ bool wgrad3_tile_bf16_eligible(const vae_wgrad_args& a, bool vec, bool dma) {
   const vae_conv_geom& g = a.g;
   if (vec && a.batch == 1 && wgrad3_s2_geom(a)) {
     if (!dma || a.M <= 32 || a.N % BNT != 0 || g.Wo % TW != 0) return false;
-    return (size_t)g.Ho * g.Wo * a.ldy * 4u < BUF_MAX && (size_t)g.Hs * g.Ws * g.Cs * 4u < BUF_MAX;
+    return descriptors_fit(g, 1, a.ldy, 1, 0);
   }
   if (!vec || a.batch != 1 || g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return false;
   if (a.M <= 32 || a.N % BNT != 0 || g.Wo % TW != 0 || g.Ho % TH != 0) return false;
   if (g.mode == VAE_MODE_FWD && !(g.Ho == g.Hs && g.Wo == g.Ws)) return false;
   if (g.mode == VAE_MODE_UP2X && !(g.Ho == 2 * g.Hs && g.Wo == 2 * g.Ws)) return false;
   if (g.mode == VAE_MODE_DGRAD) return false;
-  const size_t ys = a.y_step > 1 ? a.y_step : 1;
-  if ((ys > 1 || a.tapmask != 0) && g.mode != VAE_MODE_FWD) return false;
-  if ((size_t)g.Ho * g.Wo * a.ldy * 4u * ys * ys >= BUF_MAX || (size_t)g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX) return false;  // one image per descriptor
-  return true;
+  if ((a.y_step > 1 || a.tapmask != 0) && g.mode != VAE_MODE_FWD) return false;
+  return descriptors_fit(g, 1, a.ldy, a.y_step, 0);
 }
 // the LDS-DMA kernel: both operands as 16-byte-aligned bf16 images whose rows are whole 16-byte pieces
 bool wgrad3_dma_bf16_operands(const vae_wgrad_args& a) {
