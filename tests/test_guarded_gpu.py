@@ -33,6 +33,7 @@ import torch
 import torch.nn.functional as F
 
 from guarded import GuardedPool, guarded
+from norm_refs import SHAPES
 from test_act16_gpu import FWD_CASES as ACT16_FWD_CASES
 from test_dispatch_table import FAMILIES, _family
 from test_kernels_gpu import (BF16_CONV_CASES, BF16_FLAT_CASES, BF16_UPCONV_PHASE_CASES, CONV_CASES, GEMM_CASES, GN_FUSED_CASES,
@@ -398,8 +399,12 @@ def test_guarded_bf16_gradient_images(cuda):
 
 
 # ------------------------------------------------------------------------------------------------- GroupNorm, moments
+# (the small edge shapes of tests/norm_refs.py: fewer pixels than pixel rows, the clamped backward tail, an empty last chunk, B >= 64)
+GN_EDGE_CASES = [SHAPES[k] for k in ("one_pixel", "seven_pixels", "tail_c256", "tail_c512", "last_empty", "b65")]
+
+
 @pytest.mark.parametrize("store16", [False, True])
-@pytest.mark.parametrize("B,C,H,W", GN_RAGGED_CASES[:2] + [(2, 128, 16, 16), (1, 512, 6, 10)])
+@pytest.mark.parametrize("B,C,H,W", GN_RAGGED_CASES[:2] + [(2, 128, 16, 16), (1, 512, 6, 10)] + GN_EDGE_CASES)
 def test_guarded_groupnorm(cuda, B, C, H, W, store16):
     """gn_stats (ragged chunk plans: trailing chunks start beyond H*W), gn_apply, gn_apply_bf16, gn_track, gn_bwd with and
     without `add`, fp32 and bf16 storage"""

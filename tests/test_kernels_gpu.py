@@ -1,6 +1,9 @@
 """Per-kernel parity: every HIP entry point (through the C ABI) against a plain PyTorch fp32
 CPU reference of the same op, on seeded inputs.  Tolerances: fp32 MFMA is an exact-product
-fp32 fmaf chain, so differences are summation-order only (1e-5 relative to the operand scale)."""
+fp32 fmaf chain, so differences are summation-order only (1e-5 relative to the operand scale).
+
+The GroupNorm, tracker and dead-weight kernels at their edge shapes and values, against float64: tests/test_norm_edges_gpu.py
+(references and builders in tests/norm_refs.py, proved on the CPU by tests/test_norm_edges_host.py)."""
 import math
 import os
 

@@ -61,11 +61,13 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const void* __res
   const int per = (HW + nchunk - 1) / nchunk;
   const int p0 = chunk * per, p1 = min(HW, p0 + per);
   const int64_t xb4 = (int64_t)b * HW * l.Q;
-  // shifted sums around the thread's first value (no cancellation), then centred moments, merged over the group's threads
+  // shifted sums around a pivot from the thread's first quad (no cancellation), then centred moments, merged over the group's
+  // threads.  The pivot is the median of three of the quad's values, so that one outlier cannot become it: around a pivot of
+  // 1e4 among N(0, 1) every d is -1e4 and s1 grows to cnt * 1e4, whose ulp then swallows the values (mean off by 2e-5).
   float pv = 0.f, s1 = 0.f, s2 = 0.f, cnt = 0.f;
   for (int pix = p0 + l.pr; pix < p1; pix += l.PR) {
     f32x4 v = load4x<XBF>(x, xb4 + (int64_t)pix * l.Q + l.cq);
-    if (cnt == 0.f) pv = v[0];
+    if (cnt == 0.f) pv = __builtin_amdgcn_fmed3f(v[0], v[1], v[2]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float d = v[e] - pv;
