@@ -393,6 +393,25 @@ int vae_adamw(float* p, const float* g, float* m, float* v, int64_t n, const flo
 int vae_adamw_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm,
                   float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
                   int32_t step, double ema_decay, void* stream);
+/* The two calls above over a table of ranges of the buffers instead of [0, n): what an optimizer step needs when part of the
+ * model is frozen (training.trainable_modules).  The table is the one of vae_dead_scan below: seg_off [nseg][2] = {begin, end}
+ * element offsets, sorted, disjoint, every begin a multiple of 4; seg_chunk0 [nseg+1] = prefix sum of ceil(len / chunk) with
+ * chunk = vae_dead_scan_chunk(); nchunk = seg_chunk0[nseg].  Both tables are device memory; one workgroup per chunk, so the
+ * work is one launch whatever the number of ranges.  Nothing outside the ranges is read or written (g may hold anything there).
+ * vae_sqnorm_ranges: the sum of g*g over the ranges; every chunk writes its fp32 partial to ws [nchunk], and the second stage
+ * (vae_sqnorm's) adds them in double in a fixed order -> out[0], bitwise repeatable.
+ * vae_adamw_ranges: vae_adamw (e == NULL) or vae_adamw_ema (e: the average) on the elements of the ranges, one launch; the
+ * element arithmetic is the same device function, so with the same *sqnorm value p, m, v, e inside the ranges come out
+ * bit-identical to those calls.  Checked on the host: pointers, nseg > 0, nchunk >= nseg, 16-byte alignment of g, p, m, v, e,
+ * and with e: ema_decay in [0, 1) and e closer to p, g, m or v than the extent the counts prove ((nchunk - nseg) * chunk +
+ * nseg elements).  The table's contents are the caller's to check (vaehip.trainable.RangeTable does).  A violation is VAE_EINVAL
+ * and no launch. */
+int vae_sqnorm_ranges(const float* g, const int64_t* seg_off, const int32_t* seg_chunk0, int32_t nseg, int32_t nchunk,
+                      float* ws, float* out, void* stream);
+int vae_adamw_ranges(float* p, const float* g, float* m, float* v, float* e_or_null, const int64_t* seg_off,
+                     const int32_t* seg_chunk0, int32_t nseg, int32_t nchunk, const float* sqnorm, float max_norm, double lr,
+                     double beta1, double beta2, double eps, double weight_decay, int32_t step, double ema_decay,
+                     void* stream);
 /* dead-weight scan (deadneuron.py:78-115): per segment, the count of |w| < thr and the sum of |w|.
  * seg_off [nseg][2] = {begin,end} element offsets into w (segments need not be adjacent).  The segments are scanned in
  * chunks of vae_dead_scan_chunk() elements, one workgroup per chunk: seg_chunk0 [nseg+1] = prefix sum of the segments'

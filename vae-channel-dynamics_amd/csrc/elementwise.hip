@@ -325,13 +325,38 @@ struct EmaArgs {
 };
 __device__ __forceinline__ float ema_next(float e, float pp, const EmaArgs& x) { return x.first ? pp : fmaf(x.omd, pp - e, e); }
 
+// the update of one element: the only copy of the arithmetic, shared by adamw_kernel and adamw_ranges_kernel so that both
+// give the same bits for the same operands (torch.optim.adamw._single_tensor_adamw, clip folded into the gradient)
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float clip, const AdamArgs& a) {
+  const float gg = g * clip;
+  float pp = p * a.decay;
+  const float mm = m + (gg - m) * a.omb1;
+  const float v2 = v * a.beta2 + a.omb2 * gg * gg;
+  const float denom = sqrtf(v2) / a.bc2_sqrt + a.eps;
+  pp = pp - a.step_size * (mm / denom);
+  p = pp; m = mm; v = v2;
+}
+__device__ __forceinline__ float adam_clip(const AdamArgs& a, const float* __restrict__ sqnorm) {
+  return a.max_norm > 0.f ? fminf(1.0f, a.max_norm / (sqrtf(sqnorm[0]) + 1e-6f)) : 1.0f;
+}
+template <bool EMA>
+__device__ __forceinline__ void adam_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, float* __restrict__ e, int64_t i, float clip, const AdamArgs& a,
+                                            const EmaArgs& x) {
+  float pp = p[i], mm = m[i], v2 = v[i];
+  adam_elem(pp, g[i], mm, v2, clip, a);
+  p[i] = pp;
+  m[i] = mm;
+  v[i] = v2;
+  if (EMA) e[i] = ema_next(e[i], pp, x);
+}
+
 template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, const float* __restrict__ sqnorm,
                                                     AdamArgs a, EmaArgs x) {
   float* __restrict__ e = x.e;
-  float clip = 1.0f;
-  if (a.max_norm > 0.f) clip = fminf(1.0f, a.max_norm / (sqrtf(sqnorm[0]) + 1e-6f));
+  const float clip = adam_clip(a, sqnorm);
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
@@ -342,12 +367,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     if (EMA) ev = *reinterpret_cast<f32x4*>(e + i * 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float gg = gv[k] * clip;
-      float pp = pv[k] * a.decay;
-      const float mm = mv[k] + (gg - mv[k]) * a.omb1;
-      const float v2 = vv[k] * a.beta2 + a.omb2 * gg * gg;
-      const float denom = sqrtf(v2) / a.bc2_sqrt + a.eps;
-      pp = pp - a.step_size * (mm / denom);
+      float pp = pv[k], mm = mv[k], v2 = vv[k];
+      adam_elem(pp, gv[k], mm, v2, clip, a);
       pv[k] = pp; mv[k] = mm; vv[k] = v2;
       if (EMA) ev[k] = ema_next(ev[k], pp, x);
     }
@@ -358,16 +379,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
   if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
-    const float gg = g[i] * clip;
-    float pp = p[i] * a.decay;
-    const float mm = m[i] + (gg - m[i]) * a.omb1;
-    const float v2 = v[i] * a.beta2 + a.omb2 * gg * gg;
-    const float denom = sqrtf(v2) / a.bc2_sqrt + a.eps;
-    pp = pp - a.step_size * (mm / denom);
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = v2;
-    if (EMA) e[i] = ema_next(e[i], pp, x);
+    adam_scalar<EMA>(p, g, m, v, e, i, clip, a, x);
   }
 }
 
@@ -385,6 +397,78 @@ __device__ __forceinline__ int dead_find_segment(const int32_t* __restrict__ seg
     if (seg_chunk0[mid] <= chunk) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+// ---------------- grad norm + AdamW over a table of arena ranges ----------------
+// The table idiom of the dead-weight scan: seg_off holds [begin, end) pairs, seg_chunk0 the prefix sum of their chunk counts,
+// one workgroup per chunk of DEAD_CHUNK elements, whatever the number of ranges (about 100 ranges of 128..512 floats when only
+// the GroupNorms train, one of 49 M when the decoder does).  Nothing outside the ranges is read or written: the gradient buffer
+// holds stale values there.  Range starts are multiples of 4 elements, so with 16-byte aligned bases every chunk takes the
+// float4 body; a chunk that does not start on 16 bytes takes the scalar loop for all of it.
+struct RangeChunk {
+  int64_t b, e;  // this workgroup's elements [b, e)
+};
+__device__ __forceinline__ RangeChunk range_chunk(const int64_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk0, int nseg) {
+  const int chunk = blockIdx.x;
+  const int s = dead_find_segment(seg_chunk0, nseg, chunk);
+  RangeChunk r;
+  r.b = seg_off[2 * s] + (int64_t)(chunk - seg_chunk0[s]) * DEAD_CHUNK;
+  r.e = min(seg_off[2 * s + 1], r.b + DEAD_CHUNK);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void sqnorm_ranges_kernel(const float* __restrict__ g, const int64_t* __restrict__ seg_off,
+                                                            const int32_t* __restrict__ seg_chunk0, int nseg, float* __restrict__ ws) {
+  __shared__ float red[4];
+  const RangeChunk r = range_chunk(seg_off, seg_chunk0, nseg);
+  const bool vec = ((reinterpret_cast<uintptr_t>(g + r.b)) & 15u) == 0;
+  const int n4 = vec ? (int)((r.e - r.b) >> 2) : 0;
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + r.b);
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const f32x4 v = g4[i];
+    s += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+  }
+  for (int64_t i = r.b + ((int64_t)n4 << 2) + threadIdx.x; i < r.e; i += 256) {
+    const float v = g[i];
+    s += v * v;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;  // every chunk writes its partial: the workspace needs no clearing
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const int64_t* __restrict__ seg_off,
+                                                           const int32_t* __restrict__ seg_chunk0, int nseg,
+                                                           const float* __restrict__ sqnorm, AdamArgs a, EmaArgs x) {
+  float* __restrict__ e = x.e;
+  const float clip = adam_clip(a, sqnorm);
+  const RangeChunk r = range_chunk(seg_off, seg_chunk0, nseg);
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(p + r.b) | reinterpret_cast<uintptr_t>(g + r.b) | reinterpret_cast<uintptr_t>(m + r.b) |
+                         reinterpret_cast<uintptr_t>(v + r.b) | (EMA ? reinterpret_cast<uintptr_t>(e + r.b) : 0);
+  const int n4 = (bits & 15u) == 0 ? (int)((r.e - r.b) >> 2) : 0;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const int64_t o = r.b + ((int64_t)i << 2);
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + o);
+    f32x4 gv = *reinterpret_cast<const f32x4*>(g + o);
+    f32x4 mv = *reinterpret_cast<f32x4*>(m + o);
+    f32x4 vv = *reinterpret_cast<f32x4*>(v + o);
+    f32x4 ev;
+    if (EMA) ev = *reinterpret_cast<f32x4*>(e + o);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pp = pv[k], mm = mv[k], v2 = vv[k];
+      adam_elem(pp, gv[k], mm, v2, clip, a);
+      pv[k] = pp; mv[k] = mm; vv[k] = v2;
+      if (EMA) ev[k] = ema_next(ev[k], pp, x);
+    }
+    *reinterpret_cast<f32x4*>(p + o) = pv;
+    *reinterpret_cast<f32x4*>(m + o) = mv;
+    *reinterpret_cast<f32x4*>(v + o) = vv;
+    if (EMA) *reinterpret_cast<f32x4*>(e + o) = ev;
+  }
+  for (int64_t i = r.b + ((int64_t)n4 << 2) + threadIdx.x; i < r.e; i += 256) adam_scalar<EMA>(p, g, m, v, e, i, clip, a, x);
 }
 
 // ADAPT: count |w| < athr[seg] (and < thr when use_fixed) instead of |w| < thr, no sum
@@ -575,14 +659,8 @@ extern "C" int vae_sqnorm(const float* g, int64_t n, float* ws, int32_t nblk, fl
   return VAE_OK;
 }
 
-// one host half for vae_adamw (e == nullptr) and vae_adamw_ema
-static int adamw_launch(const char* who, float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm,
-                        float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
-                        double ema_decay, void* stream) {
-  VAE_CHECK(p && g && m && v && n > 0 && step >= 1, "%s: bad args", who);
-  VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "%s: clipping needs sqnorm", who);
-  VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e), "%s: unaligned", who);
-  // scalar prep exactly as torch.optim.adamw._single_tensor_adamw (python doubles)
+// scalar prep exactly as torch.optim.adamw._single_tensor_adamw (python doubles)
+static AdamArgs adam_args(float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step) {
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
   AdamArgs a;
@@ -594,6 +672,17 @@ static int adamw_launch(const char* who, float* p, const float* g, float* m, flo
   a.step_size = (float)(lr / bc1);
   a.bc2_sqrt = (float)sqrt(bc2);
   a.eps = (float)eps;
+  return a;
+}
+
+// one host half for vae_adamw (e == nullptr) and vae_adamw_ema
+static int adamw_launch(const char* who, float* p, const float* g, float* m, float* v, float* e, int64_t n, const float* sqnorm,
+                        float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
+                        double ema_decay, void* stream) {
+  VAE_CHECK(p && g && m && v && n > 0 && step >= 1, "%s: bad args", who);
+  VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "%s: clipping needs sqnorm", who);
+  VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e), "%s: unaligned", who);
+  const AdamArgs a = adam_args(max_norm, lr, beta1, beta2, eps, weight_decay, step);
   EmaArgs x{e, (float)(1.0 - ema_decay), ema_decay == 0.0 ? 1 : 0};
   const dim3 grid(ew_blocks(n / 4 + 1));
   if (e)
@@ -619,6 +708,44 @@ extern "C" int vae_adamw_ema(float* p, const float* g, float* m, float* v, float
   for (const float* o : {(const float*)p, g, (const float*)m, (const float*)v})
     VAE_CHECK(!o || hi <= (uintptr_t)o || (uintptr_t)o + (uintptr_t)n * 4u <= lo, "adamw_ema: e overlaps p, g, m or v");
   return adamw_launch("adamw_ema", p, g, m, v, e, n, sqnorm, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema_decay, stream);
+}
+
+
+extern "C" int vae_sqnorm_ranges(const float* g, const int64_t* seg_off, const int32_t* seg_chunk0, int32_t nseg, int32_t nchunk, float* ws,
+                                 float* out, void* stream) {
+  VAE_CHECK(g && seg_off && seg_chunk0 && ws && out && nseg > 0 && nchunk >= nseg, "sqnorm_ranges: bad args");
+  VAE_CHECK(aligned16(g), "sqnorm_ranges: unaligned");
+  hipLaunchKernelGGL(sqnorm_ranges_kernel, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, g, seg_off, seg_chunk0, nseg, ws);
+  hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nchunk, out);
+  VAE_LAUNCH_CHECK("sqnorm_ranges");
+  return VAE_OK;
+}
+
+extern "C" int vae_adamw_ranges(float* p, const float* g, float* m, float* v, float* e, const int64_t* seg_off, const int32_t* seg_chunk0,
+                                int32_t nseg, int32_t nchunk, const float* sqnorm, float max_norm, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, int32_t step, double ema_decay, void* stream) {
+  VAE_CHECK(p && g && m && v && seg_off && seg_chunk0 && nseg > 0 && nchunk >= nseg && step >= 1, "adamw_ranges: bad args");
+  VAE_CHECK(max_norm <= 0.f || sqnorm != nullptr, "adamw_ranges: clipping needs sqnorm");
+  VAE_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e), "adamw_ranges: unaligned");
+  if (e) {
+    VAE_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, "adamw_ranges: ema_decay %g outside [0, 1)", ema_decay);
+    // the table lives on the device; what the host knows is that the last range ends at or beyond `least` elements (every range
+    // has an element, every chunk but a range's last is full), so buffers closer than that overlap inside the ranges
+    const uintptr_t least = ((uintptr_t)(nchunk - nseg) * DEAD_CHUNK + (uintptr_t)nseg) * 4u;
+    const uintptr_t lo = (uintptr_t)e, hi = lo + least;
+    for (const float* o : {(const float*)p, g, (const float*)m, (const float*)v})
+      VAE_CHECK(hi <= (uintptr_t)o || (uintptr_t)o + least <= lo, "adamw_ranges: e overlaps p, g, m or v");
+  }
+  const AdamArgs a = adam_args(max_norm, lr, beta1, beta2, eps, weight_decay, step);
+  EmaArgs x{e, (float)(1.0 - ema_decay), ema_decay == 0.0 ? 1 : 0};
+  if (e)
+    hipLaunchKernelGGL(adamw_ranges_kernel<true>, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, p, g, m, v, seg_off, seg_chunk0, nseg,
+                       sqnorm, a, x);
+  else
+    hipLaunchKernelGGL(adamw_ranges_kernel<false>, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, p, g, m, v, seg_off, seg_chunk0, nseg,
+                       sqnorm, a, x);
+  VAE_LAUNCH_CHECK("adamw_ranges");
+  return VAE_OK;
 }
 
 extern "C" int vae_dead_scan_chunk(void) { return DEAD_CHUNK; }

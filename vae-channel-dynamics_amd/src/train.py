@@ -244,6 +244,19 @@ def ema_settings(training_cfg: dict):
     return bool(training_cfg.get("use_ema", False)), decay
 
 
+def trainable_setting(training_cfg: dict):
+    """training.trainable_modules (not a key of the reference) -> the `trainable` argument of HipTrainer: absent or 'all' trains
+    everything, 'decoder' / 'encoder' are the shorthands of vaehip.trainable, a list holds module-name prefixes of the VAE"""
+    v = training_cfg.get("trainable_modules", "all")
+    if v is None:
+        return "all"
+    if isinstance(v, str):
+        return v
+    if isinstance(v, (list, tuple)) and all(isinstance(x, str) for x in v):
+        return [x[4:] if x.startswith("vae.") else x for x in v]  # the tracking keys of the YAMLs carry the wrapper's `vae.`
+    raise ValueError(f"training.trainable_modules={v!r}: expected 'all', 'decoder', 'encoder' or a list of module-name prefixes")
+
+
 def resolve_resume(resume, output_dir: str, prefix: str = "chkpt"):
     """training.resume_from_checkpoint -> directory to load, or None to start fresh.  "latest": the highest-numbered
     <prefix>-<step> directory under the run's output_dir (None when there is none); a path: that directory itself."""
@@ -322,6 +335,8 @@ def main():
     # not keys of the reference either: a fused fp32 average of the weights, and continuing from a state save_state wrote
     use_ema, ema_decay = ema_settings(training_cfg)
     resume = training_cfg.get("resume_from_checkpoint", None)
+    # not a key of the reference: which parameters train ('all', 'decoder', 'encoder' or module-name prefixes); the rest is frozen
+    trainable = trainable_setting(training_cfg)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -396,7 +411,10 @@ def main():
         max_grad_norm=max_grad_norm, kl_weight=kl_weight, lr_warmup_steps=int(training_cfg.get("lr_warmup_steps", 100)),
         max_train_steps=max_train_steps, scheduler_steps_per_update=world,  # accelerate steps the scheduler `world` times
         mixed_precision=mixed_precision, gradient_accumulation_steps=grad_accum, checkpoint_decoder=bool(grad_ckpt),
-        use_ema=use_ema, ema_decay=ema_decay)
+        use_ema=use_ema, ema_decay=ema_decay, trainable=trainable)
+    n_tr = sum(p.numel() for p in vae_wrapper.vae.parameters() if p.requires_grad)
+    logger.info(f"trainable_modules={trainable!r}: {n_tr} of {sum(p.numel() for p in vae_wrapper.vae.parameters())} parameters train, "
+                f"in {len(trainer.trainable_ranges)} arena range(s)")
 
     core_vae = vae_wrapper.vae
     dnt_cfg = config.get("dead_neuron_tracking", {})

@@ -253,8 +253,27 @@ class ParamArena:
         return self.view_of(self.grad if target is None else target, p, self.offset_of[id(p)])
 
     def attach_grads(self):
+        """a trainable parameter's .grad is its view of the gradient arena; a frozen one's is None (the torch convention)"""
         for _, p, o, _n in self.entries:
-            p.grad = self.view_of(self.grad, p, o)
+            p.grad = self.view_of(self.grad, p, o) if p.requires_grad else None
+
+    def trainable_ranges(self) -> List[Tuple[int, int]]:
+        """merged [begin, end) element runs of the entries with requires_grad, in arena order.  A run covers the zero padding
+        between two trainable neighbours (padding has zero gradient and stays zero under the update, as in the whole-arena
+        step); its last entry ends where its elements end, except the arena's last, whose run ends at `total`, so that an
+        all-trainable model is the one range [0, total)."""
+        runs: List[List[int]] = []
+        for i, (_, p, o, n) in enumerate(self.entries):
+            if not p.requires_grad:
+                continue
+            nxt = self.entries[i + 1][2] if i + 1 < len(self.entries) else self.total
+            if runs and runs[-1][2] == o:
+                runs[-1][1], runs[-1][2] = o + n, nxt
+            else:
+                runs.append([o, o + n, nxt])
+        if runs and runs[-1][2] == self.total:
+            runs[-1][1] = self.total
+        return [(b, e) for b, e, _nxt in runs]
 
     def owns(self, module: nn.Module) -> bool:
         base = self.flat.data_ptr()

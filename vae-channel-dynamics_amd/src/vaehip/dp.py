@@ -32,8 +32,13 @@ class GradBucketReducer:
     whole range is final are all-reduced asynchronously; finish() waits and averages."""
 
     def __init__(self, flat_grad: torch.Tensor, group=None, bucket_mb: float = 64.0, time_finish: bool = False,
-                 one_rank_exchange: bool = False):
+                 one_rank_exchange: bool = False, span: Optional[Tuple[int, int]] = None):
         self.flat = flat_grad
+        # span [lo, hi): the only part of flat_grad that is exchanged (frozen parameters: from the first trainable offset to
+        # the end of the last trainable range).  Offsets stay arena offsets, for the buckets and for ready(low).
+        self.span = (0, flat_grad.numel()) if span is None else (int(span[0]), int(span[1]))
+        if not (0 <= self.span[0] < self.span[1] <= flat_grad.numel()) or self.span[0] % 4:
+            raise ValueError(f"span {self.span} is not a 4-aligned slice of {flat_grad.numel()} elements")
         # one_rank_exchange: issue the collectives on a ONE-rank group as well (they are identities there).  A self-test of the
         # RCCL lines on a one-GPU box -- communicator, ReduceOp.AVG, async work objects against kernels launched through the raw
         # stream pointer, the stream waits of finish() -- not something a training run sets.
@@ -47,7 +52,8 @@ class GradBucketReducer:
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.active = self.world > 1 or (self.one_rank_exchange and dist.is_initialized())
-        self.buckets = plan_buckets(flat_grad.numel(), int(bucket_mb * (1 << 20) / 4))
+        lo0 = self.span[0]
+        self.buckets = [(lo + lo0, hi + lo0) for lo, hi in plan_buckets(self.span[1] - lo0, int(bucket_mb * (1 << 20) / 4))]
         self._next = 0
         self._works = []
         backend = dist.get_backend(group) if dist.is_initialized() else "none"

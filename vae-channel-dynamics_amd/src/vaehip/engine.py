@@ -67,6 +67,14 @@ class Engine:
         self.checkpoint_decoder = False
         self._ckpt = False    # inside a region whose segments are checkpointed
         self._replay = False  # True while a checkpointed segment is re-run: trackers / hooks already fired
+        # frozen parameters (requires_grad False).  _live: while a forward runs, whether a layer that owns a trainable parameter
+        # has executed already, i.e. whether the gradient of the CURRENT activation is wanted.  A block records a backward only
+        # if it is live at its input or trains something itself, and its closure launches only what a trainable parameter or a
+        # live input needs: no weight gradient for a frozen layer, nothing at all before the first trainable layer.  Outside a
+        # pass that sets it (forward_backward, the autograd pair) it is True: whoever records a block by hand wants its dx.
+        self._live = True
+        self._tr_key: Optional[tuple] = None
+        self._tr: Dict[int, bool] = {}
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -113,6 +121,31 @@ class Engine:
         if self.arena.flat.device.type != "cuda":
             raise RuntimeError("the VAE parameters are on %s; the HIP engine needs a GPU (there is no CPU fallback); "
                                "call .to('cuda') first" % self.arena.flat.device)
+
+    def _sync_trainable(self):
+        """read requires_grad of every parameter (once per recorded pass: the set may change between passes)"""
+        key = tuple(p.requires_grad for _, p, _o, _n in self.arena.entries)
+        if key != self._tr_key:
+            self._tr_key, self._tr = key, {}
+
+    def _trains(self, *mods) -> bool:
+        """does any of these modules own a trainable parameter"""
+        for m in mods:
+            if m is None:
+                continue
+            t = self._tr.get(id(m))
+            if t is None:
+                t = self._tr[id(m)] = any(p.requires_grad for p in m.parameters())
+            if t:
+                return True
+        return False
+
+    def _enter(self, tape, *mods):
+        """a block that owns `mods` starts executing: (record a backward?, is the gradient of its input wanted?)"""
+        live_in = self._live
+        own = self._trains(*mods)
+        self._live = live_in or own
+        return tape is not None and (live_in or own), live_in
 
     def _g(self, p: Optional[nn.Parameter]):
         return None if p is None else self.arena.grad_view(p, self._gtarget)
@@ -310,15 +343,22 @@ class Engine:
         a16, self._last16 = self._last16, None
         return a16 if recording else None
 
-    def _conv_bwd(self, m, x, dy, xf, st, need_dx=True, x16=None, dx_to_gn=False, dx_dtype=None, norm=None):
+    def _conv_bwd(self, m, x, dy, xf, st, need_dx=True, x16=None, dx_to_gn=False, dx_dtype=None, norm=None, want_dx=True):
         """dy: fp32 (possibly carrying a bf16 image) or bf16; dx_to_gn: the input gradient goes to a GroupNorm backward and
         nowhere else, so bf16 mode may store it as bf16 even with fp32 activation storage; dx_dtype: storage of the input
-        gradient when the default (ops.conv_dgrad) is not wanted"""
+        gradient when the default (ops.conv_dgrad) is not wanted.  need_dx: the layer HAS an input gradient (all but the
+        encoder's first); want_dx: somebody reads it (False when nothing upstream trains).  The weight and bias gradient is
+        launched unless both are frozen, on the operands a full backward would give it (the bf16 gradient image below is made
+        as if dx were wanted), so a trainable parameter's gradient does not depend on what else is frozen."""
         kind = getattr(m, "kind", "c1")
+        need_dw = self._trains(m)
+        want_dx = need_dx and want_dx
+        if not need_dw and not want_dx:
+            return None
         # norm: the GroupNorm(+SiLU) between x and this convolution, whose backward consumes the input gradient next: the dgrad
         # epilogue can leave that backward's first pass (ops.conv_dgrad gnb)
         gnb = None
-        if norm is not None and need_dx and st is not None and xf in (XF_AFFINE, XF_AFFINE_SILU):
+        if norm is not None and want_dx and st is not None and xf in (XF_AFFINE, XF_AFFINE_SILU):
             gnb = ops.GnCtx(x, st, norm.weight, norm.bias, xf == XF_AFFINE_SILU, norm.num_groups)
         if (need_dx and dy.dtype == torch.float32 and getattr(dy, "_b16", None) is None
                 and ops.grad_image_ok(kind, x.shape[:3] + (m.weight.shape[1],), m.weight.shape[0], m.weight.shape[1])):
@@ -327,8 +367,9 @@ class Engine:
             dy._b16 = ops.pack_bf16(dy, torch.empty(dy.shape, device=dy.device, dtype=torch.bfloat16))
         if x16 is not None and x16.dtype == torch.float32:  # the fp32 activation image of _conv: already transformed
             x, xf, st, x16 = x16, XF_NONE, None, None
-        ops.conv_wgrad(dy, x, kind, self._g(m.weight), self._g(m.bias), xf=xf, stats=st, x16=x16)
-        if need_dx:
+        if need_dw:
+            ops.conv_wgrad(dy, x, kind, self._g(m.weight), self._g(m.bias), xf=xf, stats=st, x16=x16)
+        if want_dx:
             return ops.conv_dgrad(dy, m.weight, kind, (x.shape[1], x.shape[2]), out_bf16=dx_to_gn, out_dtype=dx_dtype, gnb=gnb)
         return None
 
@@ -349,25 +390,31 @@ class Engine:
 
     # ------------------------------------------------------------------ blocks
     def _plain_conv(self, m, x, tape, need_dx=True, owner=None):
+        rec, live_in = self._enter(tape, m)
         y = self._conv(m, x, XF_NONE, None)
-        if tape is not None:
+        if rec:
             def bwd(d):
-                dx = self._conv_bwd(m, x, d, XF_NONE, None, need_dx)
+                dx = self._conv_bwd(m, x, d, XF_NONE, None, need_dx, want_dx=live_in)
                 self._done(owner or m)
                 return dx
             tape.append(bwd)
         return y
 
-    def _seg(self, run, x, tape):
+    def _seg(self, run, x, tape, mod):
         """run(x, tape) -> y, checkpointed when the enclosing region asks for it: the forward records nothing and the
-        backward closure re-runs `run` on the kept input with a private tape (same kernels, bitwise the same values)."""
+        backward closure re-runs `run` on the kept input with a private tape (same kernels, bitwise the same values).
+        mod: the module `run` executes; a segment that is neither live at its input nor trains anything keeps nothing."""
         if tape is None or not self._ckpt:
             return run(x, tape)
+        live_in = self._live
         y = run(x, None)
+        if not (live_in or self._trains(mod)):
+            return y
 
         def bwd(d):
             local: list = []
             self._replay = True
+            self._live = live_in  # the replay records what the forward would have: the same wants
             try:
                 run(x, local)
             finally:
@@ -383,7 +430,7 @@ class Engine:
         self._no_hooks(r.nonlinearity, "ResnetBlock2D.nonlinearity")
         self._no_hooks(r.dropout, "ResnetBlock2D.dropout")
         self._pre(r, lambda: x)
-        rec = tape is not None
+        rec, live_in = self._enter(tape, r)
         st1 = self._gn(r.norm1, x)
         h = self._conv(r.conv1, x, XF_AFFINE_SILU, st1)
         x16 = self._take16(rec)
@@ -392,13 +439,23 @@ class Engine:
         out = self._conv(r.conv2, h, XF_AFFINE_SILU, st2, res=sc)
         h16 = self._take16(rec)
         self._post(r, lambda: x, out)
-        if tape is not None:
+        if rec:
+            # what is wanted below conv2 (execution order norm1, conv1, norm2, conv2; the shortcut reads x beside them)
+            want_g1 = live_in or self._trains(r.norm1)       # conv1's input gradient, and norm1's backward
+            want_g2 = want_g1 or self._trains(r.conv1, r.norm2)  # conv2's input gradient, and norm2's backward
+
             def bwd(dout):
-                g2 = self._conv_bwd(r.conv2, h, dout, XF_AFFINE_SILU, st2, x16=h16, dx_to_gn=True, norm=r.norm2)
-                dh = self._gn_bwd(r.norm2, h, g2, st2, True, None, conv_only=r.conv1)  # dL/dh only feeds conv1's wgrad + dgrad
-                g1 = self._conv_bwd(r.conv1, x, dh, XF_AFFINE_SILU, st1, x16=x16, dx_to_gn=True, norm=r.norm1)
-                dsc = self._conv_bwd(r.conv_shortcut, x, dout, XF_NONE, None) if r.conv_shortcut is not None else dout
-                dx = self._gn_bwd(r.norm1, x, g1, st1, True, dsc, feeds_conv3=after_conv3)
+                g2 = self._conv_bwd(r.conv2, h, dout, XF_AFFINE_SILU, st2, x16=h16, dx_to_gn=True, norm=r.norm2, want_dx=want_g2)
+                dx = None
+                if want_g2:
+                    dh = self._gn_bwd(r.norm2, h, g2, st2, True, None, conv_only=r.conv1)  # dL/dh only feeds conv1's wgrad + dgrad
+                    g1 = self._conv_bwd(r.conv1, x, dh, XF_AFFINE_SILU, st1, x16=x16, dx_to_gn=True, norm=r.norm1, want_dx=want_g1)
+                dsc = (self._conv_bwd(r.conv_shortcut, x, dout, XF_NONE, None, want_dx=live_in)
+                       if r.conv_shortcut is not None else dout)
+                if want_g1:
+                    dx = self._gn_bwd(r.norm1, x, g1, st1, True, dsc, feeds_conv3=after_conv3)
+                    if not live_in:
+                        dx = None  # a by-product of the pass that gave norm1 its gradient; nobody upstream reads it
                 if notify is True:
                     self._done(r)
                 elif notify is not False:
@@ -409,6 +466,7 @@ class Engine:
 
     def _attention(self, a, x, tape, notify=True, after_conv3=False):
         self._pre(a, lambda: x)
+        rec, live_in = self._enter(tape, a)
         B, H, W, Cc = x.shape
         T = H * W
         scale = float(Cc) ** -0.5
@@ -432,14 +490,22 @@ class Engine:
             of = ops.gemm_nn(P, vf)
             ops.ATTN_CALLS["materialised_fwd"] += 1
             saved = None
-        if tape is None:
+        if not rec:
             P = saved = None
         o = of.view(B, H, W, Cc)
         out = self._conv(a.to_out[0], o, XF_NONE, None, res=x)
         self._post(a, lambda: x, out)
-        if tape is not None:
+        if rec:
+            want_g = live_in or self._trains(a.group_norm)                 # the projections' input gradients, the norm's backward
+            want_do = want_g or self._trains(a.to_q, a.to_k, a.to_v)        # the attention's own backward
+
             def bwd(dout):
-                do = self._conv_bwd(a.to_out[0], o, dout, XF_NONE, None, dx_dtype=f32).view(B, T, Cc)
+                do = self._conv_bwd(a.to_out[0], o, dout, XF_NONE, None, dx_dtype=f32, want_dx=want_do)
+                if not want_do:
+                    if notify:
+                        self._done(a)
+                    return None
+                do = do.view(B, T, Cc)
                 if blockwise:
                     dq, dk, dv = ops.attn_bwd(saved, of, do, scale)
                 else:
@@ -448,10 +514,15 @@ class Engine:
                     dS = ops.softmax_bwd_rows_(P, dP)
                     dq = ops.gemm_nn(dS, kf, scale)
                     dk = ops.gemm_tn(dS, qf, scale)
-                g = self._conv_bwd(a.to_q, x, dq.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32)
-                g = ops.add(g, self._conv_bwd(a.to_k, x, dk.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32))
-                g = ops.add(g, self._conv_bwd(a.to_v, x, dv.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32))
-                dx = self._gn_bwd(a.group_norm, x, g, st, False, dout, feeds_conv3=after_conv3)
+                g = self._conv_bwd(a.to_q, x, dq.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32, want_dx=want_g)
+                gk = self._conv_bwd(a.to_k, x, dk.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32, want_dx=want_g)
+                gv = self._conv_bwd(a.to_v, x, dv.view(B, H, W, Cc), XF_AFFINE, st, dx_dtype=f32, want_dx=want_g)
+                dx = None
+                if want_g:
+                    g = ops.add(ops.add(g, gk), gv)
+                    dx = self._gn_bwd(a.group_norm, x, g, st, False, dout, feeds_conv3=after_conv3)
+                    if not live_in:
+                        dx = None
                 if notify:
                     self._done(a)
                 return dx
@@ -462,9 +533,9 @@ class Engine:
         self._pre(mb, lambda: x)
         # registration order (attentions, resnets) differs from execution order, so the DP watermark
         # only moves once the whole mid block is final: after resnets[0]'s backward (last on the tape)
-        h = self._seg(lambda t, tp: self._resnet(mb.resnets[0], t, tp, notify=mb, after_conv3=after_conv3), x, tape)
-        h = self._seg(lambda t, tp: self._attention(mb.attentions[0], t, tp, notify=False, after_conv3=True), h, tape)
-        h = self._seg(lambda t, tp: self._resnet(mb.resnets[1], t, tp, notify=False), h, tape)
+        h = self._seg(lambda t, tp: self._resnet(mb.resnets[0], t, tp, notify=mb, after_conv3=after_conv3), x, tape, mb.resnets[0])
+        h = self._seg(lambda t, tp: self._attention(mb.attentions[0], t, tp, notify=False, after_conv3=True), h, tape, mb.attentions[0])
+        h = self._seg(lambda t, tp: self._resnet(mb.resnets[1], t, tp, notify=False), h, tape, mb.resnets[1])
         self._post(mb, lambda: x, h)
         return h
 
@@ -480,23 +551,28 @@ class Engine:
         self._pre(blk, lambda: x)
         h = x
         for i, r in enumerate(blk.resnets):  # a resnet after the first one continues the output of the previous one's conv2
-            h = self._seg(lambda t, tp, r=r, i=i: self._resnet(r, t, tp, after_conv3=(i > 0 or first_after_conv3)), h, tape)
+            h = self._seg(lambda t, tp, r=r, i=i: self._resnet(r, t, tp, after_conv3=(i > 0 or first_after_conv3)), h, tape, r)
         extra = getattr(blk, "downsamplers", None) or getattr(blk, "upsamplers", None)
         if extra is not None:
-            h = self._seg(lambda t, tp: self._sampler(extra[0], t, tp), h, tape)
+            h = self._seg(lambda t, tp: self._sampler(extra[0], t, tp), h, tape, extra[0])
         self._post(blk, lambda: x, h)
         return h
 
     def _norm_act_conv(self, owner, x, tape):
         norm, act, conv = owner.conv_norm_out, owner.conv_act, owner.conv_out
         self._no_hooks(act, "conv_act")
+        rec, live_in = self._enter(tape, norm, conv)
         st = self._gn(norm, x)
         y = self._conv(conv, x, XF_AFFINE_SILU, st)
-        x16 = self._take16(tape is not None)
-        if tape is not None:
+        x16 = self._take16(rec)
+        if rec:
+            want_g = live_in or self._trains(norm)
+
             def bwd(d):
-                g = self._conv_bwd(conv, x, d, XF_AFFINE_SILU, st, x16=x16, dx_to_gn=True, norm=norm)
-                dx = self._gn_bwd(norm, x, g, st, True, None, feeds_conv3=True)
+                g = self._conv_bwd(conv, x, d, XF_AFFINE_SILU, st, x16=x16, dx_to_gn=True, norm=norm, want_dx=want_g)
+                dx = self._gn_bwd(norm, x, g, st, True, None, feeds_conv3=True) if want_g else None
+                if not live_in:
+                    dx = None
                 self._done(conv)
                 self._done(norm)
                 return dx
@@ -543,6 +619,7 @@ class Engine:
                 grad = tape.pop()(grad)
         finally:
             self._gtarget = None
+            self._live = True  # (a checkpointed segment's replay sets it)
         return grad
 
     # ------------------------------------------------------------------ fused train / eval step (fast path)
@@ -559,16 +636,23 @@ class Engine:
             tgt = ops.nchw_to_nhwc(pv, 3)
             te: list = []
             td: list = []
-            mom = self.encode_nhwc(x4, te)
-            e = self._eps_nhwc(eps, mom, sample_posterior, generator)
-            z, klp = ops.sample_kl(mom, e)
-            recon = self.decode_nhwc(z, td)
+            self._sync_trainable()
+            try:
+                self._live = False  # the pixels want no gradient
+                mom = self.encode_nhwc(x4, te)
+                enc_live = self._live  # False: encoder and quant_conv are frozen; te is empty, no encoder activation is kept
+                e = self._eps_nhwc(eps, mom, sample_posterior, generator)
+                z, klp = ops.sample_kl(mom, e)
+                recon = self.decode_nhwc(z, td)
+            finally:
+                self._live = True
             scalars = ops.mse_kl_loss(recon, tgt, klp, kl_weight)
             drec = ops.mse_bwd(recon, tgt, grad_scale)
             self.arena.attach_grads()
             dz = self.run_tape(td, drec, self.arena.grad)
-            dmom = ops.sample_kl_bwd(mom, e, dz, kl_weight * grad_scale)
-            self.run_tape(te, dmom, self.arena.grad)
+            if enc_live:
+                dmom = ops.sample_kl_bwd(mom, e, dz, kl_weight * grad_scale)
+                self.run_tape(te, dmom, self.arena.grad)
         if self.reducer is not None:
             self.reducer.ready(0)
         return {"scalars": scalars, "reconstruction": recon, "moments": mom, "latents": z, "kl_partial": klp}
@@ -672,8 +756,13 @@ class _EncodeFn(torch.autograd.Function):
         need = record and any(p.requires_grad for p in params)
         tape = [] if need else None
         x4 = ops.nchw_to_nhwc(x.detach().to(dtype=torch.float32).contiguous(), 4)
-        with eng._mode():
-            mom = eng.encode_nhwc(x4, tape)
+        eng._sync_trainable()
+        try:
+            eng._live = False  # the pixels want no gradient
+            with eng._mode():
+                mom = eng.encode_nhwc(x4, tape)
+        finally:
+            eng._live = True
         ctx.eng, ctx.tape, ctx.params = eng, tape, params
         return mom.permute(0, 3, 1, 2)
 
@@ -695,8 +784,13 @@ class _DecodeFn(torch.autograd.Function):
         need = record and (z.requires_grad or any(p.requires_grad for p in params))
         tape = [] if need else None
         zz = z.detach().to(dtype=torch.float32).permute(0, 2, 3, 1).contiguous()
-        with eng._mode():
-            rec = eng.decode_nhwc(zz, tape)
+        eng._sync_trainable()
+        try:
+            eng._live = bool(record and z.requires_grad)
+            with eng._mode():
+                rec = eng.decode_nhwc(zz, tape)
+        finally:
+            eng._live = True
         ctx.eng, ctx.tape, ctx.params = eng, tape, params
         return rec.permute(0, 3, 1, 2)
 
@@ -709,4 +803,4 @@ class _DecodeFn(torch.autograd.Function):
         with eng._mode(repack=False):
             dz = eng.run_tape(ctx.tape, drec.permute(0, 2, 3, 1).contiguous(), gbuf)
         grads = [eng.arena.grad_view(p, gbuf) if p.requires_grad else None for p in ctx.params]
-        return (None, None, dz.permute(0, 3, 1, 2), *grads)
+        return (None, None, None if dz is None else dz.permute(0, 3, 1, 2), *grads)

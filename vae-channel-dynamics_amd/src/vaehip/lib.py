@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 15  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 16  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -112,6 +112,8 @@ SIGNATURES = {
     "vae_sqnorm": [vp, i64, vp, i32, vp, vp],
     "vae_adamw": [vp, vp, vp, vp, i64, vp, f32, f64, f64, f64, f64, f64, i32, vp],
     "vae_adamw_ema": [vp, vp, vp, vp, vp, i64, vp, f32, f64, f64, f64, f64, f64, i32, f64, vp],
+    "vae_sqnorm_ranges": [vp, vp, vp, i32, i32, vp, vp, vp],
+    "vae_adamw_ranges": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32, f64, f64, f64, f64, f64, i32, f64, vp],
     "vae_dead_scan_chunk": [],
     "vae_dead_scan": [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp],
     "vae_dead_scan_adaptive": [vp, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp],

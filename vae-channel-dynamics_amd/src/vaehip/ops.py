@@ -1181,3 +1181,19 @@ def adamw_ema(p, g, m, v, e, sqn: Optional[torch.Tensor], max_norm: float, lr: f
     """adamw plus e <- e + (1 - ema_decay) (p' - e) in the same pass (ema_decay == 0: e <- p')"""
     lib.call("vae_adamw_ema", _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), _p(sqn), float(max_norm), float(lr), float(beta1),
              float(beta2), float(eps), float(wd), int(step), float(ema_decay), _stream())
+
+
+def sqnorm_ranges(g: torch.Tensor, table, out: torch.Tensor):
+    """sum of g*g over the ranges of `table` (a trainable.RangeTable, which checked them when it was built; nothing is checked
+    here) -> out[0]; nothing outside them is read"""
+    lib.call("vae_sqnorm_ranges", _p(g), _p(table.seg_off), _p(table.seg_chunk0), table.nseg, table.nchunk, _p(table.ws), _p(out),
+             _stream())
+    return out
+
+
+def adamw_ranges(p, g, m, v, e: Optional[torch.Tensor], table, sqn: Optional[torch.Tensor], max_norm: float, lr: float,
+                 beta1: float, beta2: float, eps: float, wd: float, step: int, ema_decay: float = 0.0):
+    """adamw (e None) / adamw_ema on the elements of the table's ranges; everything else is neither read nor written"""
+    lib.call("vae_adamw_ranges", _p(p), _p(g), _p(m), _p(v), _p(e), _p(table.seg_off), _p(table.seg_chunk0), table.nseg, table.nchunk,
+             _p(sqn), float(max_norm), float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step), float(ema_decay),
+             _stream())

@@ -10,6 +10,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from .trainable import RangeTable
 
 logger = logging.getLogger(__name__)
 
@@ -44,6 +45,27 @@ class FusedAdamW(torch.optim.Optimizer):
         self.use_ema = bool(use_ema)
         self.ema_decay = float(ema_decay)
         self.ema: Optional[torch.Tensor] = None
+        # the trainable set as merged arena ranges (refresh_trainable); _table is None when every parameter trains: the step
+        # is then vae_sqnorm + vae_adamw(_ema) over the whole arena, else the two *_ranges calls over the device table
+        self.ranges: Optional[list] = None
+        self._table: Optional[RangeTable] = None
+
+    def refresh_trainable(self):
+        """read requires_grad of the arena's parameters again (HipTrainer does when it is built and in set_trainable; a bare
+        optimizer reads it at its first step): the merged ranges, and their device table unless they are the whole arena"""
+        a = self._vae.arena
+        ranges = a.trainable_ranges()
+        if not ranges:
+            raise ValueError("no parameter of the VAE has requires_grad: the trainable set is empty")
+        if ranges != self.ranges or (self._table is not None and self._table.seg_off.device != a.flat.device):
+            self.ranges = ranges
+            whole = ranges == [(0, a.total)]
+            self._table = None if whole or a.flat.device.type != "cuda" else RangeTable(ranges, a.flat.device, a.total)
+        return self.ranges
+
+    @property
+    def all_trainable(self) -> bool:
+        return self.ranges is None or self.ranges == [(0, self._vae.arena.total)]
 
     def _ensure(self):
         a = self._vae.arena
@@ -62,6 +84,9 @@ class FusedAdamW(torch.optim.Optimizer):
             self.sqnorm = torch.zeros(1, device=a.flat.device, dtype=torch.float32)
             self._ws = torch.empty(2048, device=a.flat.device, dtype=torch.float32)
             self._arena_id = id(a)
+            self.ranges = self._table = None
+        if self.ranges is None:
+            self.refresh_trainable()
         return a
 
     def clip_grad_norm_(self, max_norm: float):
@@ -75,6 +100,12 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW needs the parameter arena on the GPU (no CPU fallback)")
         g = self.param_groups[0]
         self.step_count += 1
+        hp = (self.sqnorm, self.max_grad_norm, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count)
+        if self._table is not None:  # part of the model is frozen: norm and update over the trainable ranges only
+            ops.sqnorm_ranges(a.grad, self._table, self.sqnorm)
+            ops.adamw_ranges(a.flat, a.grad, self.exp_avg, self.exp_avg_sq, self.ema if self.use_ema else None, self._table, *hp,
+                             ema_decay_at(self.step_count, self.ema_decay) if self.use_ema else 0.0)
+            return
         ops.sqnorm(a.grad, self.sqnorm, self._ws)
         if self.use_ema:
             ops.adamw_ema(a.flat, a.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.sqnorm, self.max_grad_norm, g["lr"],
@@ -89,7 +120,8 @@ class FusedAdamW(torch.optim.Optimizer):
         return None
 
     def grad_norm(self) -> torch.Tensor:
-        """device scalar: global L2 norm of the last step's (unclipped) gradients."""
+        """device scalar: global L2 norm of the last step's (unclipped) gradients, over the trainable parameters only (what
+        clip_grad_norm_ over the parameters with a gradient gives in the reference)."""
         return torch.sqrt(self.sqnorm[0])
 
     def state_dict(self):

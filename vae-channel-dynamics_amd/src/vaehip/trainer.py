@@ -11,6 +11,7 @@ import torch.distributed as dist
 from . import ops
 from .dp import GradBucketReducer, allreduce_mean_, broadcast_params
 from .optim import FusedAdamW
+from .trainable import apply_trainable, span_of
 
 
 def lr_lambda_factory(warmup: int, max_steps: int) -> Callable[[int], float]:
@@ -23,14 +24,23 @@ def lr_lambda_factory(warmup: int, max_steps: int) -> Callable[[int], float]:
     return fn
 
 
+def _show(ranges, most: int = 6) -> str:
+    n = sum(e - b for b, e in ranges)
+    head = ", ".join(f"[{b}, {e})" for b, e in ranges[:most])
+    return f"{head}{', ...' if len(ranges) > most else ''} ({len(ranges)} range(s), {n} elements)"
+
+
 class HipTrainer:
     def __init__(self, wrapper, *, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0,
                  kl_weight=1e-6, lr_warmup_steps=100, max_train_steps=1000, scheduler_steps_per_update: int = 1,
                  bucket_mb: float = 64.0, generator: Optional[torch.Generator] = None, mixed_precision: str = "no",
                  gradient_accumulation_steps: int = 1, checkpoint_decoder: bool = False, time_comm: bool = False,
-                 one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999):
+                 one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999, trainable=None):
+        """trainable: None (requires_grad as the user left it, read now), 'all', 'decoder', 'encoder' or a list of module-name
+        prefixes (vaehip.trainable); change it later with set_trainable()."""
         self.wrapper = wrapper
         self.vae = wrapper.vae
+        apply_trainable(self.vae, trainable)
         self.kl_weight = float(kl_weight)
         self.generator = generator
         self.vae.engine.set_precision(mixed_precision)
@@ -46,6 +56,7 @@ class HipTrainer:
         self.time_comm = bool(time_comm)
         self.optimizer = FusedAdamW(self.vae, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                     max_grad_norm=max_grad_norm, use_ema=use_ema, ema_decay=ema_decay)
+        self.optimizer.refresh_trainable()
         self.lr_scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lr_lambda_factory(lr_warmup_steps, max_train_steps))
         # accelerate steps the scheduler num_processes times per optimizer step (accelerate/scheduler.py:72-82)
         self.scheduler_steps_per_update = int(scheduler_steps_per_update)
@@ -66,8 +77,25 @@ class HipTrainer:
         """True when the LAST train_step call ended with an optimizer update (accelerator.sync_gradients)."""
         return self.micro_step == 0
 
+    def set_trainable(self, value):
+        """change the trainable set (the values of the constructor's `trainable`; None reads requires_grad again).  The moments
+        of a parameter that freezes stay as they are and are picked up again if it thaws.  Refused inside an accumulation window."""
+        if self.micro_step:
+            raise RuntimeError(f"set_trainable(): {self.micro_step} micro-batch(es) are pending; call it after an optimizer "
+                               "update or after flush()")
+        apply_trainable(self.vae, value)
+        self.optimizer.refresh_trainable()
+        self.vae.arena.attach_grads()   # a parameter that froze loses its .grad now, not at the next step
+        self.reducer = self._accum_reducer = None
+
+    @property
+    def trainable_ranges(self):
+        """merged [begin, end) arena ranges of the trainable parameters"""
+        return list(self.optimizer.ranges if self.optimizer.ranges is not None else self.optimizer.refresh_trainable())
+
     def _make_reducer(self, flat: torch.Tensor) -> GradBucketReducer:
-        return GradBucketReducer(flat, bucket_mb=self.bucket_mb, time_finish=self.time_comm, one_rank_exchange=self.one_rank_exchange)
+        return GradBucketReducer(flat, bucket_mb=self.bucket_mb, time_finish=self.time_comm, one_rank_exchange=self.one_rank_exchange,
+                                 span=span_of(self.trainable_ranges))
 
     def _accumulating_step(self, pixel_values, eps, end_of_dataloader: bool):
         """one micro-batch of an N-micro-batch update; returns (result, update_due).  The update is due on the N-th
@@ -158,7 +186,8 @@ class HipTrainer:
         grad = self.vae.arena.grad
         grad.copy_(self._accum)
         if self.exchanging:
-            allreduce_mean_(grad, one_rank_exchange=self.one_rank_exchange)
+            lo, hi = span_of(self.trainable_ranges)
+            allreduce_mean_(grad[lo:hi], one_rank_exchange=self.one_rank_exchange)
         self.micro_step = 0
         self._update()
 
@@ -177,12 +206,16 @@ class HipTrainer:
         if not opt.use_ema:
             raise RuntimeError("ema_weights(): this trainer was built with use_ema=False")
         flat = opt._ensure().flat
+        # a frozen element is its own average: only the trainable ranges change places, so a frozen weight that was nudged or
+        # re-loaded is seen as it is now
+        ranges = [(0, flat.numel())] if opt.all_trainable else opt.ranges
 
         def exchange():
             with torch.no_grad():
-                tmp = flat.clone()
-                flat.copy_(opt.ema)
-                opt.ema.copy_(tmp)
+                for b, e in ranges:
+                    tmp = flat[b:e].clone()
+                    flat[b:e].copy_(opt.ema[b:e])
+                    opt.ema[b:e].copy_(tmp)
         exchange()
         try:
             yield
@@ -195,11 +228,18 @@ class HipTrainer:
         sd = {"optimizer": self.optimizer.state_dict(), "lr_scheduler": self.lr_scheduler.state_dict(),
               "global_step": self.global_step, "micro_step": self.micro_step,
               "accum": self._accum.detach().cpu() if (self.micro_step > 0 and self._accum is not None) else None,
-              "generator": self.generator.get_state() if self.generator is not None else None}
+              "generator": self.generator.get_state() if self.generator is not None else None,
+              "trainable_ranges": [list(r) for r in self.trainable_ranges]}
         return sd
 
     def load_state_dict(self, sd: dict):
         """the weights must be in the arena already (an optimizer state without an average starts it from them)"""
+        mine = [list(r) for r in self.trainable_ranges]
+        theirs = sd.get("trainable_ranges")  # a state from before parameters could be frozen trained them all
+        theirs = [[0, self.vae.arena.total]] if theirs is None else [list(map(int, r)) for r in theirs]
+        if theirs != mine:
+            raise ValueError(f"trainer state was saved with the trainable arena ranges {_show(theirs)}, this trainer trains "
+                             f"{_show(mine)}: build it with the same trainable set")
         self.optimizer.load_state_dict(sd["optimizer"])
         self.lr_scheduler.load_state_dict(sd["lr_scheduler"])
         self.global_step = int(sd["global_step"])
