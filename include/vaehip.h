@@ -297,6 +297,37 @@ int vae_image_metrics_partial(const float* pred, int64_t psb, int64_t psc, int64
                               int64_t tsb, int64_t tsc, int64_t tsh, int64_t tsw, int32_t B, int32_t C, int32_t H, int32_t W,
                               double* ws, void* stream);
 int vae_image_metrics_final(const double* ws, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* stream);
+/* ---- logit lens (src/analysis/logit_lens.py; reference src/analysis/logit_lens.py: channel maps :132-164, mini-decoder
+ * :55-60 / :263-270 / :324-413), csrc/lens.hip ----
+ * x: an NHWC activation as the engine holds it, read in place: fp32 or bf16 storage (x_bf16), channels contiguous, pixel stride
+ * ld >= C elements (a channel-prefix view of a wider buffer: x4[..., :3] with ld = 4), B samples of H x W pixels.  The first
+ * S <= B samples are used, and the K channels named by `channels`, a DEVICE int32 list (any order, repeats allowed, C - 1
+ * included).  channels_host: the same list in host memory, or NULL; when given, an index outside [0, C) is VAE_EINVAL (the
+ * kernels read zeros for such an index and nothing outside x).  No planar or fp32 copy of x is made; every offset is 64-bit.
+ * Non-finite values in x are outside the contract.  Argument errors (null pointers, S > B, K < 1, H or W < 1, ld < C, a channel
+ * index the host can see outside [0, C)) return non-zero with vae_last_error() set before anything touches the GPU.
+ * Planes (two launches):
+ *   maps  [S][K][H][W] fp32: the raw planes (bf16 widened exactly)
+ *   range [S][K][2]:         min and max of each plane
+ *   norm  [S][K][H][W]:      (x - min) / (max - min), one IEEE subtraction and one IEEE division in fp32, where
+ *                            max - min > 1e-6f; exactly 0 on every other plane (logit_lens.py:143-148)
+ *   vae_lens_workspace: *nfloats = size of ws for this shape (exactly what the partial pass writes); needs no GPU.
+ *   partial: x -> maps, ws (min / max per wave); final: maps, ws -> range, norm.  min / max are order-free: bitwise repeatable.
+ * Projection (one launch): Sigmoid(ConvT2(ReLU(ConvT1(x)))), ConvT1 = ConvTranspose2d(Cin, 16, 3, stride 2, padding 1,
+ *   output_padding 1), ConvT2 = the same from 16 to 3 channels; w1 [Cin][16][3][3], b1 [16], w2 [16][3][3][3], b2 [3]: torch's
+ *   layout, fp32, device memory.  full_map = 0: Cin = 1, each listed channel on its own, out [S][K][4H][4W][3]; full_map != 0:
+ *   Cin = K, the listed channels in list order are the input, out [S][4H][4W][3].  out: fp32, HWC.  The 16-channel hidden image
+ *   stays in LDS; fp32 FMA accumulation.  vae_lens_tile: edge of the input tile a workgroup covers (tests sit on it). */
+int vae_lens_tile(void);
+int vae_lens_workspace(int32_t S, int32_t K, int32_t H, int32_t W, int64_t* nfloats);
+int vae_lens_planes_partial(const void* x, int32_t x_bf16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ld, int32_t S,
+                            const int32_t* channels, const int32_t* channels_host, int32_t K, float* maps, float* ws,
+                            void* stream);
+int vae_lens_planes_final(const float* maps, const float* ws, int32_t S, int32_t K, int32_t H, int32_t W, float* range,
+                          float* norm, void* stream);
+int vae_lens_project(const void* x, int32_t x_bf16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ld, int32_t S,
+                     const int32_t* channels, const int32_t* channels_host, int32_t K, int32_t full_map, const float* w1,
+                     const float* b1, const float* w2, const float* b2, float* out, void* stream);
 /* GroupNorm(+SiLU) backward.  g = dL/d(XF(gn(x))): fp32, or bf16 when g_bf16 != 0 (bf16 mode stores the dgrad outputs of
  * the halo-tile kernels as bf16, vae_igemm_args.out_bf16).
  * stage 1: ws [B][nchunk][C][2] partial sums of du and du*xhat                     */

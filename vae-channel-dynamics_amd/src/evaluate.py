@@ -7,9 +7,14 @@ images) and SSIM (11x11 gaussian, sigma 1.5; the reference needs torchmetrics) c
 kernel per batch (vaehip.ops.image_metrics, accumulated by vaehip.metrics.ImageMetrics), read straight from
 the engine's channels-last reconstruction; KL is summed on the device too, so the loop synchronises the host
 only to save the sample PNGs.  `to_unit`, `psnr_sums` and `ssim_per_image` below are the CPU definition the
-kernel is held to (tests/test_eval_metrics.py, tests/test_image_metrics_gpu.py).  Logit-lens visualisation is out of
-scope; `--enable_logit_lens` is accepted and captures the requested layers' activations through the
-hook protocol (as evaluate.py:207-211 does) so downstream tooling can use them.
+kernel is held to (tests/test_eval_metrics.py, tests/test_image_metrics_gpu.py).
+
+With `--enable_logit_lens` (on by default, as in the reference) the first batch's activations of `--logit_lens_layers` are
+captured on the device (SDXLVAEWrapper.add_device_captures) and analysis.logit_lens.VAELogitLens draws their channel maps
+and mini-decoder projections under `<output_dir>/<logit_lens.visualization_output_subdir>/step_0/<layer>/`; its arithmetic
+runs in csrc/lens.hip on the captured tensors, only the pictures' pixels come to the host.  `first_batch_activations.pt`
+(the captured tensors as logical (B, C, H, W) fp32 CPU tensors) is still written unless `--save_first_batch_activations
+false`, which spares the whole-tensor transfer.
 """
 import argparse
 import logging
@@ -45,6 +50,8 @@ def parse_args():
     p.add_argument("--logit_lens_projection_type", type=str, default="mini_decoder_single_channel",
                    choices=["mini_decoder_single_channel", "mini_decoder_full_map"])
     p.add_argument("--logit_lens_mini_decoder_input_channels", type=int, default=None)
+    # not a flag of the reference: first_batch_activations.pt is the one thing left that brings whole captured tensors to the host
+    p.add_argument("--save_first_batch_activations", default=True, type=lambda x: (str(x).lower() == "true"))
     # not a flag of the reference: evaluate <checkpoint_path>/vae_ema, the averaged weights train.py saves with training.use_ema
     # (`--use_ema` or `--use_ema true`; `--use_ema false` evaluates the raw weights and says so in eval_metrics.txt)
     p.add_argument("--use_ema", nargs="?", const=True, default=None, type=lambda x: (str(x).lower() == "true"))
@@ -98,9 +105,44 @@ def save_png(t: torch.Tensor, path: str):
     Image.fromarray(a).save(path)
 
 
+def lens_settings(args, config) -> dict:
+    """the analyzer's config as the reference builds it (evaluate.py:108-134); full-map projection without the decoder's
+    channel count ends the program with status 1"""
+    cin = args.logit_lens_mini_decoder_input_channels
+    if cin is None:
+        if args.logit_lens_projection_type == "mini_decoder_full_map":
+            logger.error("For 'mini_decoder_full_map', --logit_lens_mini_decoder_input_channels must be specified.")
+            sys.exit(1)
+        cin = 1
+    section = config.get("logit_lens", {}) or {}
+    return {"visualization_output_subdir": section.get("visualization_output_subdir", "logit_lens_visualizations_eval"),
+            "default_num_channels_to_viz": section.get("num_channels_to_viz", 4),
+            "default_num_batch_samples_to_viz": args.logit_lens_num_samples,
+            "mini_decoder_input_channels": cin,
+            "colormap": section.get("colormap", "viridis"),
+            "run_mini_decoder_projection": section.get("run_mini_decoder_projection", True)}
+
+
+def run_logit_lens(lens, args, acts: dict):
+    """channel maps and projections of the captured first batch (global step 0)"""
+    for layer in args.logit_lens_layers:
+        if layer in acts:
+            lens.visualize_channel_activation_maps(acts[layer], layer, 0, num_batch_samples_to_viz=args.logit_lens_num_samples,
+                                                   colormap=lens.config.get("colormap", "viridis"))
+    lens.run_logit_lens_with_activations(global_step=0, layers_to_analyze=args.logit_lens_layers,
+                                         num_batch_samples_to_viz=args.logit_lens_num_samples,
+                                         projection_type=args.logit_lens_projection_type, activations_to_process=acts)
+
+
+def host_activations(acts: dict) -> dict:
+    """captured activations as the hook path hands them out: logical (B, C, H, W) fp32 CPU tensors"""
+    return {k: (v.float().cpu().permute(0, 3, 1, 2) if v.is_cuda else v) for k, v in acts.items()}
+
+
 def main():
     args = parse_args()
     config = load_config(args.config_path)
+    lens_cfg = lens_settings(args, config) if args.enable_logit_lens else None  # (a bad flag combination ends here, before the GPU)
     if args.use_ema:  # a wrong checkpoint path is reported before anything else is touched
         model_directory(args.checkpoint_path, True)
     if not torch.cuda.is_available():
@@ -113,6 +155,11 @@ def main():
     model_path = model_directory(args.checkpoint_path, args.use_ema)
     w = SDXLVAEWrapper(pretrained_model_name_or_path=model_path, device=device)
     w.vae.eval()
+    lens = None
+    if lens_cfg is not None:
+        from analysis.logit_lens import VAELogitLens
+        logger.info("Logit Lens analysis enabled.")
+        lens = VAELogitLens(model_for_lens=w.vae, logit_lens_config=lens_cfg, main_experiment_output_dir=args.output_dir)
     data_cfg = config.get("data", {})
     bs = args.batch_size or data_cfg.get("validation_batch_size", data_cfg.get("batch_size", 4))
     ds = load_and_preprocess_dataset(
@@ -127,8 +174,8 @@ def main():
     n = saved = 0
     with torch.no_grad():
         for step, batch in enumerate(dl):
-            if step == 0 and args.enable_logit_lens:
-                w.add_hooks(args.logit_lens_layers)
+            if step == 0 and lens is not None:
+                w.add_device_captures(args.logit_lens_layers)
             pv = batch.get("pixel_values") if batch else None
             if pv is None:
                 continue
@@ -145,10 +192,14 @@ def main():
                 save_png(pv[i], os.path.join(args.output_dir, f"sample_{saved}_orig.png"))
                 save_png(rec[i], os.path.join(args.output_dir, f"sample_{saved}_recon.png"))
                 saved += 1
-            if step == 0 and args.enable_logit_lens:
+            if step == 0 and lens is not None:
                 acts = w.get_captured_activations()
-                torch.save({k: v for k, v in acts.items()}, os.path.join(args.output_dir, "first_batch_activations.pt"))
+                logger.info("Running LogitLens on first batch activations...")
+                run_logit_lens(lens, args, acts)
+                if args.save_first_batch_activations:
+                    torch.save(host_activations(acts), os.path.join(args.output_dir, "first_batch_activations.pt"))
                 w.remove_hooks()
+                logger.info("LogitLens hooks removed.")
     m = metrics.compute()
     avg_mse, psnr, ssim = m["avg_mse"], m["psnr"], m["ssim"]
     avg_kl = float(kl_sum) / n if n else 0

@@ -64,6 +64,28 @@ class SDXLVAEWrapper(torch.nn.Module):
         if not found and layer_names:
             logger.warning(f"No hooks registered. Ensure layer names {layer_names} are correct and exist in the VAE.")
 
+    def add_device_captures(self, layer_names: List[str]):
+        """add_hooks without the host copy: a layer the engine serves (Engine.metric_trackable) keeps the fp32 NHWC device
+        snapshot of its output under its name, any other layer gets the torch hook above"""
+        self.remove_hooks()
+        found = False
+        for name, module in self.vae.named_modules():
+            if name not in layer_names:
+                continue
+            found = True
+            engine = getattr(module, "_vae_engine", None)
+            engine = engine() if engine is not None else None
+            if engine is not None and engine.metric_trackable(module):
+                def sink(_moments, fmap, name=name):
+                    self._captured_activations[name] = fmap
+                self._hook_handles.append(engine.add_tracker(module, "output", sink, metrics=["full_activation_map"]))
+                logger.info(f"Registered device activation capture for VAE layer: '{name}'")
+            else:
+                self._hook_handles.append(module.register_forward_hook(self._capture(name)))
+                logger.info(f"Registered activation hook for VAE layer: '{name}'")
+        if not found and layer_names:
+            logger.warning(f"No hooks registered. Ensure layer names {layer_names} are correct and exist in the VAE.")
+
     def remove_hooks(self):
         if not self._hook_handles:
             return

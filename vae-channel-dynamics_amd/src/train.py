@@ -18,6 +18,8 @@ What differs from the reference, on purpose:
     so replicas stay identical (the reference nudges rank 0 only and never re-broadcasts).
   * wandb / tensorboard are optional: when unavailable, metrics go to <output_dir>/metrics.jsonl.
   * plots are not produced (reporting only); every CSV the plots were made from is still written.
+  * logit_lens.enabled draws (analysis/logit_lens.py, arithmetic in csrc/lens.hip): its layer entries may carry the
+    `.full_activation_map` suffix the reference's configs document but its loop never matched.
 """
 import argparse
 import csv
@@ -273,6 +275,38 @@ def resolve_resume(resume, output_dir: str, prefix: str = "chkpt"):
     return best
 
 
+def lens_activations(entries, step_data: dict) -> dict:
+    """the full activation maps a logit_lens layer list names, by monitor layer id.  An entry is a monitor layer id
+    (`vae.<module>.<input|output>`) or that id followed by `.full_activation_map`, the form the reference's base_config.yaml
+    documents and its own loop never matched; an entry without data for the step is reported and left out"""
+    acts = {}
+    for entry in entries:
+        layer_id = entry[:-len(".full_activation_map")] if entry.endswith(".full_activation_map") else entry
+        fmap = (step_data.get(layer_id) or {}).get("full_activation_map")
+        if fmap is None:
+            logger.warning(f"LogitLens: no full_activation_map for '{entry}' in the tracked data of this step. Skipping.")
+            continue
+        acts[layer_id] = fmap
+    return acts
+
+
+def run_logit_lens(lens, ll_cfg: dict, step_data: dict, global_step: int):
+    """channel maps (always) and mini-decoder projections (logit_lens.run_mini_decoder_projection) of the step's tracked maps"""
+    if not step_data:
+        logger.warning(f"LogitLens: No activation data for step {global_step}.")
+        return
+    entries = ll_cfg.get("layers_to_analyze_direct") or ll_cfg.get("target_tracked_metrics") or []
+    acts = lens_activations(entries, step_data)
+    n_samples = ll_cfg.get("num_batch_samples_to_viz", 1)
+    for layer_id, fmap in acts.items():
+        lens.visualize_channel_activation_maps(fmap, layer_id, global_step, num_channels_to_viz=ll_cfg.get("num_channels_to_viz"),
+                                               num_batch_samples_to_viz=n_samples, colormap=ll_cfg.get("colormap", "viridis"))
+    if acts and ll_cfg.get("run_mini_decoder_projection", True):
+        lens.run_logit_lens_with_activations(global_step=global_step, layers_to_analyze=list(acts), num_batch_samples_to_viz=n_samples,
+                                             projection_type=ll_cfg.get("projection_type", "mini_decoder_single_channel"),
+                                             activations_to_process=acts)
+
+
 def run_validation(trainer: HipTrainer, val_dataloader, kl_weight: float, global_step: int, mlog: MetricLogger, device, world: int):
     """train.py:53-97: eval forward with mode(), SUM-reduced MSE and kl().sum(), per-sample averages.
     Hooks/trackers stay attached, so validation forwards enter the monitor buffer exactly as in the reference.
@@ -426,9 +460,13 @@ def main():
     classifier = RegionClassifier(model=core_vae, config=cls_cfg) if cls_cfg.get("enabled", False) else None
     int_cfg = config.get("intervention", {})
     intervention = InterventionHandler(model=core_vae, config=int_cfg) if int_cfg.get("enabled", False) else None
-    if config.get("logit_lens", {}).get("enabled", False):
-        logger.info("logit_lens.enabled: visualisation is out of scope of this build (in the reference's train loop it "
-                    "never matches a layer key anyway, SURVEY.md 2a #10); skipped.")
+    ll_cfg = config.get("logit_lens", {}) or {}
+    lens = None
+    if ll_cfg.get("enabled", False) and is_main:
+        from analysis.logit_lens import VAELogitLens
+        lens = VAELogitLens(model_for_lens=core_vae, logit_lens_config=ll_cfg, main_experiment_output_dir=output_dir)
+    logger.info("VAELogitLens initialized for main process." if lens else "VAELogitLens disabled or not main process.")
+    lens_interval = int(ll_cfg.get("visualization_interval", 1000)) if lens else -1
 
     log_interval = int(logging_cfg.get("log_interval", 10))
     save_interval = int(config.get("saving", {}).get("save_interval_steps", 500))
@@ -487,6 +525,8 @@ def main():
                     classification = classifier.classify(tracked, global_step)
                 if not classification:
                     logger.info(f"Step {global_step}: Classifier found no inactive channels.")
+            if lens and global_step % lens_interval == 0:
+                run_logit_lens(lens, ll_cfg, monitor.get_data_for_step(global_step) if monitor else {}, global_step)
             if intervention and global_step % int_cfg.get("intervention_interval", 200) == 0:
                 if classification:
                     intervention.intervene(classification, global_step)

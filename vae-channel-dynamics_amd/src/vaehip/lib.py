@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 16  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 17  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -90,6 +90,11 @@ SIGNATURES = {
     "vae_image_metrics_workspace": [i32, i32, i32, i32, C.POINTER(i64)],
     "vae_image_metrics_partial": [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp],
     "vae_image_metrics_final": [vp, i32, i32, i32, i32, vp, vp],
+    "vae_lens_tile": [],
+    "vae_lens_workspace": [i32, i32, i32, i32, C.POINTER(i64)],
+    "vae_lens_planes_partial": [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(i32), i32, vp, vp, vp],
+    "vae_lens_planes_final": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "vae_lens_project": [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(i32), i32, i32, vp, vp, vp, vp, vp, vp],
     "vae_gn_bwd_partial": [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "vae_gn_bwd_final": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "vae_gn_bwd_apply": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],

@@ -944,6 +944,71 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _lens_operands(who: str, x: torch.Tensor, samples: int, channels: torch.Tensor, channels_host):
+    """shape / stride checks shared by the logit-lens wrappers -> the leading arguments of their entry points, K, and the
+    host list (kept alive by the caller until the call returns)"""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"{who}: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    if not (isinstance(channels, torch.Tensor) and channels.dim() == 1 and channels.dtype == torch.int32 and channels.is_contiguous()
+            and channels.device == x.device):
+        raise ValueError(f"{who}: channels must be a contiguous 1-D int32 tensor on {x.device}")
+    K = channels.numel()
+    samples = int(samples)
+    if B < 1 or H < 1 or W < 1 or Cc < 1 or K < 1 or not 1 <= samples <= B:
+        raise ValueError(f"{who}: {tuple(x.shape)} with {samples} samples and {K} channels: needs 1 <= samples <= B, at least one "
+                         f"channel and a non-empty map")
+    host = None
+    if channels_host is not None:
+        idx = [int(c) for c in channels_host]
+        if len(idx) != K:
+            raise ValueError(f"{who}: channels_host has {len(idx)} entries, channels {K}")
+        if any(not 0 <= c < Cc for c in idx):
+            raise ValueError(f"{who}: channel indices {idx} are not all inside [0, {Cc})")
+        host = (C.c_int32 * K)(*idx)
+    return (_p(x), _b16(x), B, H, W, Cc, ld, samples, _p(channels), host, K), (B, H, W, K, samples)
+
+
+def lens_planes(x: torch.Tensor, samples: int, channels: torch.Tensor, channels_host=None):
+    """the logit lens's channel maps of the first `samples` samples of x and the channels a device int32 list names, read in
+    place: (maps [S, K, H, W] fp32 -- bf16 storage widened exactly --, range [S, K, 2] = per-plane min and max, norm
+    [S, K, H, W] = (x - min) / (max - min), or 0 on a plane with max - min <= 1e-6).  x: NHWC, fp32 or bf16 storage, channels
+    contiguous; a channel-prefix view of a wider buffer is read in place.  channels_host: the same indices as a host sequence,
+    for the range check a device list cannot get (an index outside [0, C) reads zeros otherwise).  Non-finite values are
+    outside the contract.  Nothing synchronises the host."""
+    args, (B, H, W, K, S) = _lens_operands("lens_planes", x, samples, channels, channels_host)
+    n = C.c_int64(0)
+    lib.call("vae_lens_workspace", S, K, H, W, C.byref(n))
+    dev = x.device
+    ws = torch.empty((n.value,), device=dev, dtype=torch.float32)
+    maps = torch.empty((S, K, H, W), device=dev, dtype=torch.float32)
+    rng = torch.empty((S, K, 2), device=dev, dtype=torch.float32)
+    norm = torch.empty((S, K, H, W), device=dev, dtype=torch.float32)
+    lib.call("vae_lens_planes_partial", *args, _p(maps), _p(ws), _stream())
+    lib.call("vae_lens_planes_final", _p(maps), _p(ws), S, K, H, W, _p(rng), _p(norm), _stream())
+    return maps, rng, norm
+
+
+def lens_project(x: torch.Tensor, samples: int, channels: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                 b2: torch.Tensor, full_map: bool, channels_host=None) -> torch.Tensor:
+    """the logit lens's mini-decoder Sigmoid(ConvT2(ReLU(ConvT1(.)))) (ConvTranspose2d k 3, stride 2, padding 1, output_padding 1;
+    Cin -> 16 -> 3) on the same operand as lens_planes, in one launch with the hidden image in LDS: full_map False projects
+    each listed channel on its own (w1 [1, 16, 3, 3]) -> [S, K, 4H, 4W, 3]; full_map True takes the listed channels as the input
+    (w1 [K, 16, 3, 3]) -> [S, 4H, 4W, 3].  fp32, HWC.  Weights: torch's ConvTranspose2d layout, contiguous fp32 on x's device."""
+    args, (B, H, W, K, S) = _lens_operands("lens_project", x, samples, channels, channels_host)
+    cin = K if full_map else 1
+    for t, shape, name in ((w1, (cin, 16, 3, 3), "w1"), (b1, (16,), "b1"), (w2, (16, 3, 3, 3), "w2"), (b2, (3,), "b2")):
+        if not (t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"lens_project: {name} must be a contiguous float32 tensor of shape {shape} on {x.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    out = torch.empty((S, 4 * H, 4 * W, 3) if full_map else (S, K, 4 * H, 4 * W, 3), device=x.device, dtype=torch.float32)
+    lib.call("vae_lens_project", *args, int(bool(full_map)), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), _stream())
+    return out
+
+
 def map_snapshot(t: torch.Tensor) -> torch.Tensor:
     """fp32 NHWC device copy of an activation (full_activation_map): bf16 storage widened by vae_unpack_bf16"""
     if t.dtype == torch.bfloat16:
