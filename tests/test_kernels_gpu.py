@@ -3,7 +3,9 @@ CPU reference of the same op, on seeded inputs.  Tolerances: fp32 MFMA is an exa
 fp32 fmaf chain, so differences are summation-order only (1e-5 relative to the operand scale).
 
 The GroupNorm, tracker and dead-weight kernels at their edge shapes and values, against float64: tests/test_norm_edges_gpu.py
-(references and builders in tests/norm_refs.py, proved on the CPU by tests/test_norm_edges_host.py)."""
+(references and builders in tests/norm_refs.py, proved on the CPU by tests/test_norm_edges_host.py).
+The <= 4-channel convolution kernels (skinny.hip, conv_thin_bf16.hip, wgrad_thin_bf16.hip) at their tile loops and tails, against
+float64: tests/test_thin_edges_gpu.py (cases and references in tests/thin_refs.py, proved on the CPU by tests/test_thin_edges_host.py)."""
 import math
 import os
 
