@@ -1,5 +1,5 @@
 """Per-launch table of one train step: kernel, GEMM shape, milliseconds, TFLOP/s -- which LAUNCHES an instantiation's total hides
-(the bench's kernel table sums per instantiation).  usage: python tools/launch_shapes.py [--dtype bf16] [--batch 32] [--res 256] [--match igemm_rows_bf16]"""
+(the bench's kernel table sums per instantiation).  usage: python tools/launch_shapes.py [--dtype bf16] [--batch 32] [--res 256] [--match igemm_rows_bf16] [--flags]"""
 import argparse
 import os
 import sys
@@ -17,6 +17,7 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--match", default="", help="only kernels whose name contains this")
 ap.add_argument("--min-ms", type=float, default=0.0)
+ap.add_argument("--flags", action="store_true", help="also the source map, the transform, the storage flags and which optional buffers the launch has")
 args = ap.parse_args()
 
 _name = ops._kernel_name
@@ -27,9 +28,11 @@ def _name_with_shape(fn, a):
     g = a.g
     if hasattr(a, "K"):
         extra = f" M{a.M} N{a.N} K{a.K} taps{g.taps} s{g.stride} mode{g.mode} batch{a.batch}"
+        flags = f" B{g.B} Hs{g.Hs} Ws{g.Ws} Cs{g.Cs} xf{a.xf} a16:{a.a_bf16} out16:{a.out_bf16} bias:{int(bool(a.bias))} track:{int(bool(a.track))}"
     else:  # weight gradient: [M = Cout] x [N = Cin] per tap over npix pixels
         extra = f" Cout{a.M} Cin{a.N} npix{a.npix} taps{g.taps} s{g.stride} mode{g.mode} batch{a.batch} nsplit{a.nsplit}"
-    return s + extra
+        flags = f" B{g.B} Hs{g.Hs} Ws{g.Ws} Cs{g.Cs} xf{a.xf} x16:{a.x_bf16} y16:{a.y_bf16} bias:{int(bool(a.bias_partial))}"
+    return s + extra + (flags if args.flags else "")
 
 
 ops._kernel_name = _name_with_shape

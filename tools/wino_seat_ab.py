@@ -25,7 +25,14 @@ the case fixes one): outputs, `gstat` workspaces, slabs and bias partials bit fo
 shared header csrc/bf16_tile_common.h owns), which together must launch every instantiation the dispatcher can reach (exit status
 1 otherwise); timed on the 3x3 layers of the bf16 step at 256^2, batch 32 (BF16_STEP).
 
-usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16]"""
+`--only thin`: the six kernels of the <= 4-channel convolutions (csrc/skinny.hip, conv_thin_bf16.hip, wgrad_thin_bf16.hip; what they
+share is csrc/thin_common.h).  The small cases are the tables of tests/thin_refs.py (ROWS_CASES, THIN_LARGE, WG_CASES: operands, argument
+blocks and split counts as the tests build them): outputs, tracker buffers, slabs (the output itself with one split) and bias
+partials bit for bit; together they must launch all 16 instantiations (exit status 1 otherwise).  Timed: every launch of one fp32
+step (256^2, batch 16) and one bf16 step (256^2, batch 32) that one of these kernels serves (THIN_STEP, copied from the output of
+tools/launch_shapes.py --flags).
+
+usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16|thin]"""
 import argparse
 import ctypes as C
 import json
@@ -98,6 +105,36 @@ BF16_NAMES = ({f"conv3_tile_bf16_kernel<{TF[dg]},{TF[up]},{xf},{TF[i]}>" for dg,
               | {f"conv3_wide_bf16_kernel<{TF[dg]},{ks}>" for dg in (0, 1) for ks in (2, 3)}
               | {f"wgrad3_tile_bf16_kernel<{TF[up]},{xf},{TF[x]},{TF[y]}>" for up in (0, 1) for xf, x in ((0, 0), (0, 1), (1, 0), (2, 0)) for y in (0, 1)}
               | {"wgrad3_dma_bf16_kernel<false,1>", "wgrad3_dma_bf16_kernel<false,2>", "wgrad3_dma_bf16_kernel<true,1>"})
+
+
+def thin_cases():
+    """-> (thin_refs, [("thin", id, B, H, W, Ci, Co, case, timed)]): the tables of tests/thin_refs.py, then the launches of the two
+    steps as rows of the same tables.  One line of `launch_shapes.py --dtype no --batch 16 --flags` / `--dtype bf16 --batch 32
+    --flags` each: the layer, the map, the channel counts and storage, the transform, bias on or off and the split count are
+    the ones printed there (bf16: a wide operand the step hands over as a bf16 image is, after the dispatcher's canonical
+    form, the same operand stored as bf16 -- out16 / a16 / wide16 here)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import thin_refs as T
+    R, G = T.Rows, T.Wg
+    step = []
+    for tag, B, bf in (("f32", 16, False), ("bf16", 32, True)):
+        big, lat = (B, 256, 256), (B, 32, 32)
+        sk, wk = ("conv_thin_bf16_kernel", "wgrad_thin_bf16_kernel") if bf else ("conv_smallk_kernel", "wgrad_smallk_kernel")
+        sn = "conv_thinn_bf16_kernel<2>" if bf else "conv_smalln_kernel<2>"
+        step += [
+            R(f"step-{tag}-conv_in", sk, "fwd", "c3", big, 4, 128, 3, bf16=bf, out16=bf),
+            R(f"step-{tag}-post_quant", "conv_smallk_kernel", "fwd", "c1", lat, 4, 4, 4, bf16=bf),
+            R(f"step-{tag}-decoder_conv_in", sk, "fwd", "c3", lat, 4, 512, 4, bf16=bf, out16=bf),
+            R(f"step-{tag}-conv_out", sn, "fwd", "c3", big, 128, 3, 128, xf=T.XF_AFFINE_SILU, bf16=bf, a16=bf),
+            G(f"step-{tag}-conv_out-wgrad", wk + "<false,2>", 2, "c3", big, 128, 3, 128, 1024, xf=T.XF_AFFINE_SILU, bf16=bf, wide16=bf),
+            R(f"step-{tag}-conv_out-dgrad", sk, "dgrad", "c3", big, 3, 3, 128, bias=False, bf16=bf, out16=bf),
+            G(f"step-{tag}-decoder_conv_in-wgrad", wk + "<true,0>", 1, "c3", lat, 4, 512, 4, 8 * B, bf16=bf, wide16=bf),
+            G(f"step-{tag}-post_quant-wgrad", "wgrad_smallk_kernel<true,0>", 1, "c1", lat, 4, 4, 4, 8 * B, bf16=bf),
+            R(f"step-{tag}-post_quant-dgrad", "conv_smallk_kernel", "dgrad", "c1", lat, 4, 4, 4, bias=False, bf16=bf),
+            G(f"step-{tag}-conv_in-wgrad", wk + "<true,0>", 1, "c3", big, 4, 128, 3, 1024, bf16=bf, wide16=bf),
+        ]
+    small = list(T.ROWS_CASES) + [T.THIN_LARGE] + list(T.WG_CASES)
+    return T, [("thin", c.id, *c.shape, c.Ci, c.Co, c, timed) for cs, timed in ((small, False), (step, True)) for c in cs]
 
 
 def _p(t):
@@ -295,12 +332,67 @@ class Bf16Case:
         return launch, outs, (a, wh)
 
 
+class ThinCase:
+    """one row of the tables of tests/thin_refs.py (T): a small case with the operands the tests use, or a launch of the step with
+    operands drawn on the device; arm(dll) -> (launch function, outputs of that arm)"""
+    T = None
+
+    def __init__(self, dev, kind, cid, B, H, W, Ci, Co, c):
+        T = self.T
+        self.dev, self.c, self.rows = dev, c, isinstance(c, T.Rows)
+        self.opts = {"no_thin_mfma": 1} if c.no_thin else {}
+        if not cid.startswith("step-"):
+            o = T.rows_operands(c) if self.rows else T.wg_operands(c)
+            self.ops = {k: (None if v is None else v.to(dev)) for k, v in o._asdict().items()}
+            return
+        g = torch.Generator(device=dev).manual_seed(T._seed(cid))
+        rnd = lambda *s: torch.randn(s, device=dev, generator=g)  # noqa: E731
+        Hy, Wy = T.out_hw(c.kind, H, W)
+        self.ops = {"scale": torch.rand((B, c.Cs), device=dev, generator=g) + 0.5, "shift": rnd(B, c.Cs) * 0.5}
+        if self.rows:
+            src = rnd(B, H, W, c.Cs) if c.form == "fwd" else rnd(B, Hy, Wy, Co)
+            self.ops.update(src=src.bfloat16() if c.a16 else src, w=rnd(Co, T.taps_of(c.kind), Ci) * 0.2, bias=rnd(T.rows_dims(c)[1]) * 0.5)
+        else:
+            x, dy = rnd(B, H, W, c.Cs), rnd(B, Hy, Wy, Co)
+            self.ops.update(x=x.bfloat16() if (c.wide16 and c.side == 2) else x, dy=dy.bfloat16() if (c.wide16 and c.side == 1) else dy)
+
+    def arm(self, dll, st):
+        T, c, o, dev, nan = self.T, self.c, self.ops, self.dev, float("nan")
+        xf = c.xf != T.XF_NONE
+        if self.rows:
+            a = T.rows_block(c, ops)
+            M, N, _, _ = T.rows_dims(c)
+            outs = {"out": torch.full((M, N), nan, device=dev, dtype=torch.bfloat16 if c.out16 else torch.float32)}
+            if c.track:
+                outs["track"] = torch.full(((M + T.TP - 1) // T.TP, N), nan, device=dev)
+            a.A, a.W, a.C, a.bias, a.track = _p(o["src"]), _p(o["w"]), _p(outs["out"]), _p(o["bias"]) if c.bias else None, _p(outs.get("track"))
+            name, fn = dll.vae_igemm_kernel_name, dll.vae_igemm_rows
+        else:
+            a = T.wg_block(c, ops)
+            outs = {"slab": torch.full((c.ns, c.Co * T.taps_of(c.kind) * c.Ci), nan, device=dev)}
+            if c.bias:
+                outs["bias_partial"] = torch.full((c.ns, c.Co), nan, device=dev)
+            a.dY, a.X, a.bias_partial = _p(o["dy"]), _p(o["x"]), _p(outs.get("bias_partial"))
+            a.out, a.partial = (_p(outs["slab"]), None) if c.ns == 1 else (None, _p(outs["slab"]))
+            name, fn = dll.vae_wgrad_kernel_name, dll.vae_wgrad
+        a.scale, a.shift = (_p(o["scale"]), _p(o["shift"])) if xf else (None, None)
+        buf = C.create_string_buffer(128)
+        name(C.byref(a), buf, 128)
+        self.kernel = buf.value.decode()
+        assert self.kernel == c.kernel, (c.id, self.kernel, c.kernel)
+
+        def launch():
+            rc = fn(C.byref(a), st)
+            assert rc == 0, rc
+        return launch, outs, (a,)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs="+", help="NEW.so PARENT.so [name=OTHER.so ...]")
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16"])
+    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16", "thin"])
     arg = ap.parse_args()
     assert len(arg.libs) >= 2, "two libraries: this build and the parent's"
     names = ["new", "parent"] + [s.split("=", 1)[0] for s in arg.libs[2:]]
@@ -310,11 +402,13 @@ def main():
     cases = WINO2 if arg.only == "wino2" else (STEP + SMALL if arg.only != "up" else []) + (UP if arg.only != "wino4" else [])
     if arg.only == "bf16":
         cases = BF16_SMALL + BF16_STEP
+    if arg.only == "thin":
+        ThinCase.T, cases = thin_cases()
     for d in dlls:  # (an option of the library, so of every copy)
         d.vae_set_option(b"no_wino4", 1 if arg.only == "wino2" else 0)
     rows, all_equal = [], True
     for kind, mode, B, H, W, Ci, Co, epi, timed in cases:
-        c = (Bf16Case if kind == "bf16" else Case)(dev, kind, mode, B, H, W, Ci, Co, epi)
+        c = {"bf16": Bf16Case, "thin": ThinCase}.get(kind, Case)(dev, kind, mode, B, H, W, Ci, Co, epi)
         first, eq, launches, keep = None, {}, [], []
         for i, d in enumerate(dlls):  # one arm's outputs at a time beside the first's
             for o, v in getattr(c, "opts", {}).items():  # (a library option the case runs under: set on every copy, cleared below)
@@ -376,8 +470,9 @@ def main():
     timed_rows = [r for r in rows if "parent" in r and "wino4" in r["kernel"]]
     if timed_rows:  # the step's F(4x4) launches, one of each: sum of the medians per arm
         res["wino4_sum_of_medians_ms"] = {nm: round(sum(r[nm]["median_ms"] for r in timed_rows), 4) for nm in names}
-    if arg.only == "bf16":  # the small cases together reach every instantiation the dispatcher selects
-        res["instantiations_not_launched"] = sorted(BF16_NAMES - {r["kernel"] for r in rows if "parent" not in r})
+    if arg.only in ("bf16", "thin"):  # the small cases together reach every instantiation the dispatcher selects
+        every = BF16_NAMES if arg.only == "bf16" else set(ThinCase.T.INSTANTIATIONS)
+        res["instantiations_not_launched"] = sorted(every - {r["kernel"] for r in rows if "parent" not in r})
         print("instantiations not launched:", res["instantiations_not_launched"])
         all_equal = all_equal and not res["instantiations_not_launched"]
     if arg.out:

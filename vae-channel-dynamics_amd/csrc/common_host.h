@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 #include <hip/hip_runtime_api.h>
 #include "../../include/vaehip.h"
 
@@ -25,6 +26,25 @@ void vae_set_error(const char* fmt, ...);
   } while (0)
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// THE xf switch: launch(int_c<xf>) for a valid xf, false for any other value
+template <class Launch>
+bool dispatch_xf(int xf, Launch launch) {
+  switch (xf) {
+    case VAE_XF_NONE: launch(int_c<VAE_XF_NONE>{}); return true;
+    case VAE_XF_AFFINE: launch(int_c<VAE_XF_AFFINE>{}); return true;
+    case VAE_XF_AFFINE_SILU: launch(int_c<VAE_XF_AFFINE_SILU>{}); return true;
+    default: return false;
+  }
+}
+// The kernel files behind dispatch.cpp (which checks the operands of a transform, not the value of xf) have always run any
+// other value as AFFINE_SILU: their launchers keep that.
+template <class Launch>
+void dispatch_xf_or_silu(int xf, Launch launch) {
+  if (!dispatch_xf(xf, launch)) launch(int_c<VAE_XF_AFFINE_SILU>{});
+}
 
 constexpr int SS_HALF = 512;             // floats of GroupNorm scale (and of shift) kept in LDS per workgroup
 constexpr size_t BUF_MAX = 0xFFFFFFF0u;  // bytes one buffer descriptor can cover

@@ -280,11 +280,7 @@ __global__ __launch_bounds__(NT) void conv3_tile_kernel(vae_igemm_args p, int ti
 
 template <bool BKM, bool DG, bool UP>
 void launch_xf(const vae_igemm_args& a, dim3 grid, int tx, int ty, hipStream_t st) {
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((conv3_tile_kernel<BKM, DG, UP, VAE_XF_NONE>), grid, dim3(NT), 0, st, a, tx, ty); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((conv3_tile_kernel<BKM, DG, UP, VAE_XF_AFFINE>), grid, dim3(NT), 0, st, a, tx, ty); break;
-    default: hipLaunchKernelGGL((conv3_tile_kernel<BKM, DG, UP, VAE_XF_AFFINE_SILU>), grid, dim3(NT), 0, st, a, tx, ty); break;
-  }
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((conv3_tile_kernel<BKM, DG, UP, decltype(xf)::value>), grid, dim3(NT), 0, st, a, tx, ty); });
 }
 
 }  // namespace

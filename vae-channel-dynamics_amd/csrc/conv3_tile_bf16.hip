@@ -400,11 +400,7 @@ void launch_xf(const vae_igemm_args& a, dim3 grid, int tx, int ty, int nt, hipSt
     hipLaunchKernelGGL((conv3_tile_bf16_kernel<DG, UP, VAE_XF_NONE, true>), grid, dim3(NT), 0, st, a, tx, ty, nt);
     return;
   }
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((conv3_tile_bf16_kernel<DG, UP, VAE_XF_NONE, false>), grid, dim3(NT), 0, st, a, tx, ty, nt); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((conv3_tile_bf16_kernel<DG, UP, VAE_XF_AFFINE, false>), grid, dim3(NT), 0, st, a, tx, ty, nt); break;
-    default: hipLaunchKernelGGL((conv3_tile_bf16_kernel<DG, UP, VAE_XF_AFFINE_SILU, false>), grid, dim3(NT), 0, st, a, tx, ty, nt); break;
-  }
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((conv3_tile_bf16_kernel<DG, UP, decltype(xf)::value, false>), grid, dim3(NT), 0, st, a, tx, ty, nt); });
 }
 
 }  // namespace

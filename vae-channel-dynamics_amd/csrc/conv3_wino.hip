@@ -435,7 +435,7 @@ static int launch_wino_t(const vae_igemm_args& a, const float* U, hipStream_t st
 }
 
 int launch_conv3_wino(const vae_igemm_args& a, const float* U, hipStream_t st) {
-  if (a.xf == VAE_XF_NONE) return launch_wino_t<VAE_XF_NONE, CONV3_WINO_NB>(a, U, st);
-  if (a.xf == VAE_XF_AFFINE) return launch_wino_t<VAE_XF_AFFINE, CONV3_WINO_NB>(a, U, st);
-  return launch_wino_t<VAE_XF_AFFINE_SILU, CONV3_WINO_NB>(a, U, st);
+  int rc = 0;
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { rc = launch_wino_t<decltype(xf)::value, CONV3_WINO_NB>(a, U, st); });
+  return rc;
 }

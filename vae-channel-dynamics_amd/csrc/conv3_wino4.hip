@@ -580,7 +580,7 @@ static int launch_wino4_t(const vae_igemm_args& a, const float* U, hipStream_t s
 }
 
 int launch_conv3_wino4(const vae_igemm_args& a, const float* U, hipStream_t st) {
-  if (a.xf == VAE_XF_NONE) return launch_wino4_t<VAE_XF_NONE>(a, U, st);
-  if (a.xf == VAE_XF_AFFINE) return launch_wino4_t<VAE_XF_AFFINE>(a, U, st);
-  return launch_wino4_t<VAE_XF_AFFINE_SILU>(a, U, st);
+  int rc = 0;
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { rc = launch_wino4_t<decltype(xf)::value>(a, U, st); });
+  return rc;
 }

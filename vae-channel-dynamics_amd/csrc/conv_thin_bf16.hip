@@ -7,12 +7,14 @@
 // per workgroup and stay in registers as B operands (12 fragments), v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  The output
 // tile goes through LDS and leaves as whole 256-byte rows (16 bytes per lane).  The tracker sums (|value as stored| per channel
 // and 128-row tile, the layout of conv_smallk_kernel) come from the accumulators.
-#include "bf16_frag.h"
-#include <algorithm>
+// The tile shapes, the gather of the narrow tensor, the tile range of a workgroup, the octet transform of the halo and the host
+// predicates are in thin_common.h, shared with skinny.hip and wgrad_thin_bf16.hip.
+#include "thin_common.h"
+#include "launchers.h"
 
 namespace {
 
-constexpr int CT_TP = 128, CT_NT = 256;
+constexpr int CT_TP = thin::TP, CT_NT = 256;
 constexpr int CT_LDK = 48 + 8;         // im2col row stride (u16): 112 B
 constexpr int CT_LDO = 128 + 8;        // output tile row stride (u16): 272 B
 constexpr int CT_ITEMS = (CT_TP * 9 + CT_NT - 1) / CT_NT;  // (pixel, tap) gathers per thread and tile: 5
@@ -26,8 +28,7 @@ __global__ __launch_bounds__(CT_NT, 2) void conv_thin_bf16_kernel(vae_igemm_args
   const int lr = lane & 31, lh = lane >> 5;
   const int n0 = blockIdx.y * 128;
   const int hw = g.Ho * g.Wo;
-  const size_t sbytes = (size_t)g.B * g.Hs * g.Ws * g.Cs * 4u;
-  const auto rsS = VAE_BUF_RSRC(p.A, sbytes);
+  const auto rsS = thin::narrow_rsrc(p.A, g, g.Cs);
   const auto rsC = VAE_BUF_RSRC(p.C, (size_t)p.M * p.ldc * 2u);
 
   // weights -> bf16 [n][k = tap * 4 + s] in LDS (over sO), then into registers: B fragment of (k-step ks, channel block nb) =
@@ -49,29 +50,19 @@ __global__ __launch_bounds__(CT_NT, 2) void conv_thin_bf16_kernel(vae_igemm_args
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) bv[nb] = p.bias ? p.bias[n0 + nb * 32 + lr] : 0.f;
 
-  f32x4 rt[CT_ITEMS];
+  f32x4 rt[CT_ITEMS];  // the next tile's gathers: in registers while this tile is multiplied
   auto gather = [&](int tile, bool valid) {
     const int m0 = tile * CT_TP;
 #pragma unroll
     for (int i = 0; i < CT_ITEMS; ++i) {
       const int e = tid + CT_NT * i;
       const int row = e / 9, tap = e - row * 9;
-      const int m = m0 + row;
-      const int b = m / hw, rem = m - b * hw;
-      const int y = rem / g.Wo, x = rem - y * g.Wo;
-      const int kh = tap / 3, kw = tap - kh * 3;
-      int sy = 0, sx = 0;
-      const bool ok = valid && e < CT_TP * 9 && src_pixel(g, y, x, kh, kw, sy, sx);
-      const unsigned base = oob_unless(ok, (unsigned)(((b * g.Hs + sy) * g.Ws + sx) * g.Cs) * 4u);
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        if (s < p.K) v[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsS, base, 4u * s, 0));
-      rt[i] = v;
+      rt[i] = thin::gather4(g, rsS, g.Cs, p.K, hw, m0 + row, tap, valid && e < CT_TP * 9);
     }
   };
 
-  const int tbeg = blockIdx.x * tiles_per_wg, tend = min(ntiles, tbeg + tiles_per_wg);
+  const thin::TileRange tr = thin::tile_range(blockIdx.x, tiles_per_wg, ntiles);
+  const int tbeg = tr.beg, tend = tr.end;
   if (tbeg < tend) gather(tbeg, true);
   for (int tile = tbeg; tile < tend; ++tile) {
     __syncthreads();  // the previous tile's reads of sA / sO are done (first time: the weight fragments are in registers)
@@ -141,7 +132,7 @@ __global__ __launch_bounds__(CT_NT, 2) void conv_thin_bf16_kernel(vae_igemm_args
 // a tile row x 32 channels of one tap) is one ds_read_b128; the weights W[s][tap][c] are k-contiguous as stored and sit in LDS
 // as bf16 rows (the 13 unused output columns read a zero row).  Wave w = tile row w: 2 x 36 MFMAs.
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int CN_TH = 4, CN_TW = 32, CN_HW = CN_TW + 2, CN_HP = (CN_TH + 2) * CN_HW;  // 204 halo pixels
+constexpr int CN_TH = thin::TH, CN_TW = thin::TW, CN_HW = thin::HW, CN_HP = thin::HP;  // 204 halo pixels
 constexpr int CN_KMAX = 128, CN_LDH = CN_KMAX + 8;                                      // halo row stride (u16): 272 B
 constexpr int CN_LDWT = 9 * CN_KMAX + 8;                                               // weight row stride (u16)
 
@@ -152,11 +143,8 @@ __global__ __launch_bounds__(256, 2) void conv_thinn_bf16_kernel(vae_igemm_args 
   const vae_conv_geom g = p.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l16 = lane & 15, kq = lane >> 4;
-  int t = blockIdx.x;
-  const int tx = t % tiles_x; t /= tiles_x;
-  const int ty = t % tiles_y;
-  const int b = t / tiles_y;
-  const int y0 = ty * CN_TH, x0 = tx * CN_TW;
+  const thin::Tile tl = thin::decode(blockIdx.x, tiles_x, tiles_y);
+  const int b = tl.b, y0 = tl.y0, x0 = tl.x0;
   const int K = p.K, nq = K / 8;  // channel octets per pixel
   const auto rsA = VAE_BUF_RSRC(reinterpret_cast<const u16*>(p.A) + (int64_t)b * g.Hs * g.Ws * g.Cs, (size_t)g.Hs * g.Ws * g.Cs * 2u);
 
@@ -186,31 +174,13 @@ __global__ __launch_bounds__(256, 2) void conv_thinn_bf16_kernel(vae_igemm_args 
       const int ir = pp / CN_HW, jc = pp - ir * CN_HW;
       const int hy = y0 - 1 + ir, hx = x0 - 1 + jc;
       ok[i] = q < nchunks && ((unsigned)hy < (unsigned)g.Hs) && ((unsigned)hx < (unsigned)g.Ws);
-      r[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, oob_unless(ok[i], (unsigned)(((hy * g.Ws + hx) * g.Cs + oct * 8) * 2)), 0, 0));
+      r[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, oob_unless(ok[i], (unsigned)((hy * g.Ws + hx) * g.Cs + oct * 8) * 2u), 0, 0));
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int q = q0 + tid + 256 * i;
-      if (q < nchunks) {
-        uint4 v = r[i];
-        if (XF != VAE_XF_NONE) {
-          const f32x4 lo = unpack4(uint2{v.x, v.y}), hi = unpack4(uint2{v.z, v.w});
-          f32x4 a, c;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float u = lo[e] * sc[e] + sh[e], w = hi[e] * sc[4 + e] + sh[4 + e];
-            if (XF == VAE_XF_AFFINE_SILU) {
-              u = silu_f(u);
-              w = silu_f(w);
-            }
-            a[e] = ok[i] ? u : 0.f;  // padding stays zero AFTER the transform
-            c[e] = ok[i] ? w : 0.f;
-          }
-          const uint2 pa = pack4(a), pc = pack4(c);
-          v = uint4{pa.x, pa.y, pc.x, pc.y};
-        }
-        *reinterpret_cast<uint4*>(&sH[(q / nq) * CN_LDH + oct * 8]) = v;
-      }
+      if (q < nchunks)  // (padding stays zero AFTER the transform)
+        *reinterpret_cast<uint4*>(&sH[(q / nq) * CN_LDH + oct * 8]) = thin::xform8_bf16<XF>(r[i], sc, sh, ok[i]);
     }
   }
   __syncthreads();
@@ -249,17 +219,16 @@ __global__ __launch_bounds__(256, 2) void conv_thinn_bf16_kernel(vae_igemm_args 
 bool conv_thin_bf16_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
   if (a.prec != VAE_PREC_BF16 || !a.out_bf16 || a.a_bf16 || a.A16 != nullptr || a.res != nullptr || a.xf != VAE_XF_NONE) return false;
-  if (a.K > 4 || a.batch != 1 || a.alpha != 1.0f || g.taps != 9 || g.stride != 1 || a.gstat || a.gnb_ws) return false;
-  if (!(g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_DGRAD) || g.Ho != g.Hs || g.Wo != g.Ws) return false;
+  if (a.K > 4 || a.batch != 1 || a.alpha != 1.0f || g.taps != 9 || !thin::same_map(g) || a.gstat || a.gnb_ws) return false;
+  if (!(g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_DGRAD)) return false;
   if (a.N % 128 != 0 || a.ldc % 8 != 0 || a.M % CT_TP != 0 || !aligned16(a.C)) return false;
-  if ((size_t)a.M * a.ldc * 2u >= BUF_MAX || (size_t)g.B * g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX) return false;
-  return true;
+  return thin::desc_fits((size_t)a.M * a.ldc, 2u) && thin::narrow_fits(g);
 }
 
 int launch_conv_thin_bf16(const vae_igemm_args& a, hipStream_t st) {
   const int ntiles = a.M / CT_TP;
   const int per = std::max(1, std::min(8, ntiles / 1024));  // a few tiles per workgroup: the weight fragments are built once
-  dim3 grid((unsigned)((ntiles + per - 1) / per), (unsigned)(a.N / 128));
+  dim3 grid((unsigned)thin::tiles_per_part(ntiles, per), (unsigned)(a.N / 128));
   hipLaunchKernelGGL(conv_thin_bf16_kernel, grid, dim3(CT_NT), 0, st, a, ntiles, per);
   return 0;
 }
@@ -269,19 +238,14 @@ bool conv_thinn_bf16_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
   if (a.prec != VAE_PREC_BF16 || !a.a_bf16 || a.out_bf16 || a.A16 != nullptr || a.res != nullptr || a.track != nullptr) return false;
   if (a.N > 4 || a.K % 32 != 0 || a.K > CN_KMAX || (256 % (a.K / 8)) != 0 || a.batch != 1 || a.alpha != 1.0f || a.sk != 1) return false;
-  if (g.mode != VAE_MODE_FWD || g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.Ho != g.Hs || g.Wo != g.Ws) return false;
+  if (!thin::fwd_same_3x3(g)) return false;
   if (g.Wo % CN_TW != 0 || g.Ho % CN_TH != 0 || g.Cs % 8 != 0 || !aligned16(a.A) || a.gstat || a.gnb_ws) return false;
-  if ((size_t)g.Hs * g.Ws * g.Cs * 2u >= BUF_MAX) return false;
-  return true;
+  return thin::desc_fits(thin::image_elems(g), 2u);
 }
 
 int launch_conv_thinn_bf16(const vae_igemm_args& a, hipStream_t st) {
-  const int tx = a.g.Wo / CN_TW, ty = a.g.Ho / CN_TH;
-  dim3 grid((unsigned)((int64_t)tx * ty * a.g.B));
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((conv_thinn_bf16_kernel<VAE_XF_NONE>), grid, dim3(256), 0, st, a, tx, ty); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((conv_thinn_bf16_kernel<VAE_XF_AFFINE>), grid, dim3(256), 0, st, a, tx, ty); break;
-    default: hipLaunchKernelGGL((conv_thinn_bf16_kernel<VAE_XF_AFFINE_SILU>), grid, dim3(256), 0, st, a, tx, ty); break;
-  }
+  int tx, ty;
+  const dim3 grid = thin::tile_grid(a.g, tx, ty);
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((conv_thinn_bf16_kernel<decltype(xf)::value>), grid, dim3(256), 0, st, a, tx, ty); });
   return 0;
 }

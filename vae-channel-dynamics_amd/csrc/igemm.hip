@@ -903,21 +903,8 @@ __global__ __launch_bounds__(256) void wgrad_wino_reduce_kernel(const float* __r
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-template <int V>
-using int_c = std::integral_constant<int, V>;
-using std::false_type;
+using std::false_type;  // (int_c and dispatch_xf, THE xf switch: common_host.h)
 using std::true_type;
-
-// THE xf switch: launch(int_c<xf>) for a valid xf, false for any other value
-template <class Launch>
-bool dispatch_xf(int xf, Launch launch) {
-  switch (xf) {
-    case VAE_XF_NONE: launch(int_c<VAE_XF_NONE>{}); return true;
-    case VAE_XF_AFFINE: launch(int_c<VAE_XF_AFFINE>{}); return true;
-    case VAE_XF_AFFINE_SILU: launch(int_c<VAE_XF_AFFINE_SILU>{}); return true;
-    default: return false;
-  }
-}
 
 // BF: the bf16 policy (vectorised shapes only: the caller checked, `vec` is not read)
 template <bool BF, int BM, int BN, int WM, int WN>

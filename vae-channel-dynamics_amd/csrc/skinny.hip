@@ -11,16 +11,22 @@
 // The WIDE side may be stored as bf16 (bf16 mode keeps the 128-channel activations / gradients as bf16): out_bf16 for
 // conv_smallk's output, y_bf16 / x_bf16 for wgrad_smallk's V, a_bf16 for conv_smalln's input; the narrow side, the weights
 // and the arithmetic are fp32.
-#include "bf16_frag.h"
-#include <algorithm>
+// The tile shapes, the tile range of a split, the per-element transform, the slab protocol of the weight gradient and the host
+// predicates are in thin_common.h, shared with the matrix-pipe kernels of the same launches (conv_thin_bf16.hip,
+// wgrad_thin_bf16.hip).
+#include "thin_common.h"
+#include "launchers.h"
 
 namespace {
 
-constexpr int TP = 128;   // pixels per tile
+using thin::TP;
+using thin::TAPS_MAX;
 constexpr int NT = 256;   // 2 pixel streams x 128 channel lanes
-constexpr int TAPS_MAX = 9;
 
-// stage S[src(row, tap)][0..3] for the TP rows of tile `m0` (row = linear pixel of the row grid of `g`)
+// stage S[src(row, tap)][0..3] for the TP rows of tile `m0` (row = linear pixel of the row grid of `g`), straight into LDS.
+// (Spelt out, not thin::gather4: this gather also serves 1x1 layers, and through the shared function -- whole, or only its
+// pixel mapping -- the two kernels below moved: wgrad_smallk_kernel<false,*> one scalar spill fewer (20 / 24 / 24 for
+// 21 / 25 / 25), wgrad_smallk_kernel<true,0> 77 VGPRs for 79.)
 __device__ __forceinline__ void stage_small(const vae_conv_geom& g, const float* __restrict__ S, int Cs_small, int K, int m0,
                                             int mrows, f32x4* __restrict__ sI) {
   const int hw = g.Ho * g.Wo;
@@ -122,9 +128,8 @@ __global__ __launch_bounds__(NT) void wgrad_smallk_kernel(vae_wgrad_args p, vae_
   int xb = -1;
   float xsc = 1.f, xsh = 0.f;
 
-  const int per = (ntiles + p.nsplit - 1) / p.nsplit;
-  const int tbeg = split * per, tend = min(ntiles, tbeg + per);
-  for (int tile = tbeg; tile < tend; ++tile) {
+  const thin::TileRange tr = thin::tile_range(split, thin::tiles_per_part(ntiles, p.nsplit), ntiles);
+  for (int tile = tr.beg; tile < tr.end; ++tile) {
     const int m0 = tile * TP;
     __syncthreads();  // the previous tile's reads of sI are done
     stage_small(gs, S, lds_, narrow, m0, npixv, sI);
@@ -142,9 +147,7 @@ __global__ __launch_bounds__(NT) void wgrad_smallk_kernel(vae_wgrad_args p, vae_
           xsc = chok ? p.scale[(int64_t)b * p.g.Cs + ch] : 0.f;
           xsh = chok ? p.shift[(int64_t)b * p.g.Cs + ch] : 0.f;
         }
-        float u = v * xsc + xsh;
-        if (XF == VAE_XF_AFFINE_SILU) u = silu_f(u);
-        v = ok ? u : 0.f;
+        v = thin::xform1<XF>(v, xsc, xsh, ok);
       }
       if (SMALL_X) vsum += v;
 #pragma unroll
@@ -175,24 +178,19 @@ __global__ __launch_bounds__(NT) void wgrad_smallk_kernel(vae_wgrad_args p, vae_
   }
   __syncthreads();
   if (half == 0) {
-    const int64_t ld = (int64_t)gs.taps * p.N;
-    float* __restrict__ O = (p.nsplit == 1 ? p.out : p.partial + (int64_t)split * p.M * ld);
+    const thin::Slab sl = thin::slab_of(p, split, gs.taps);
     if (chok) {
 #pragma unroll
       for (int t = 0; t < TAPS_MAX; ++t)
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-          if (t < gs.taps && s < narrow) {
-            const float r = acc[t][s] + red[lane * 36 + t * 4 + s];
-            if (SMALL_X) O[(int64_t)ch * ld + (int64_t)t * p.N + s] = p.alpha * r;
-            else O[(int64_t)s * ld + (int64_t)t * p.N + ch] = p.alpha * r;
-          }
+          if (t < gs.taps && s < narrow) thin::slab_store<SMALL_X>(sl, ch, t, s, acc[t][s] + red[lane * 36 + t * 4 + s]);
     }
     if (p.bias_partial) {
       if (SMALL_X) {  // every channel block owns its channels' sums of dY
-        if (chok) p.bias_partial[(int64_t)split * p.M + ch] = vsum + red[128 * 36 + lane];
+        if (chok) thin::bias_partial_row(p, split)[ch] = vsum + red[128 * 36 + lane];
       } else if (blockIdx.y == 0 && lane < p.M) {
-        p.bias_partial[(int64_t)split * p.M + lane] = ssum[lane] + red[128 * 36 + lane];
+        thin::bias_partial_row(p, split)[lane] = ssum[lane] + red[128 * 36 + lane];
       }
     }
   }
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(NT) void wgrad_smallk_kernel(vae_wgrad_args p, vae_
 bool conv_smallk_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
   return a.K <= 4 && a.batch == 1 && a.xf == VAE_XF_NONE && a.res == nullptr && a.alpha == 1.0f && g.taps <= TAPS_MAX &&
-         g.mode != VAE_MODE_DGRAD_S2 && (size_t)a.M * a.ldc * 4u < BUF_MAX && (size_t)g.B * g.Hs * g.Ws * g.Cs * 4u < BUF_MAX;
+         g.mode != VAE_MODE_DGRAD_S2 && thin::desc_fits((size_t)a.M * a.ldc, 4u) && thin::narrow_fits(g);
 }
 int launch_conv_smallk(const vae_igemm_args& a, hipStream_t st) {
   dim3 grid((unsigned)((a.M + TP - 1) / TP), (unsigned)((a.N + 127) / 128));
@@ -211,46 +209,15 @@ int launch_conv_smallk(const vae_igemm_args& a, hipStream_t st) {
   return 0;
 }
 
-// 0 = not served here, 1 = the narrow side is X (N <= 4), 2 = the narrow side is dY (M <= 4)
-int wgrad_smallk_kind(const vae_wgrad_args& a) {
-  const vae_conv_geom& g = a.g;
-  if (a.batch != 1 || g.taps > TAPS_MAX) return 0;
-  if ((size_t)a.npix * a.ldy * 4u >= BUF_MAX || (size_t)g.B * g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX) return 0;
-  if (a.N <= 4 && a.xf == VAE_XF_NONE && (g.mode == VAE_MODE_FWD || g.mode == VAE_MODE_UP2X)) return 1;
-  // transposed gather: plain stride-1 'same' geometry only (every input pixel is the centre tap of one output pixel)
-  if (a.M <= 4 && g.mode == VAE_MODE_FWD && g.stride == 1 && g.Ho == g.Hs && g.Wo == g.Ws &&
-      ((g.taps == 9 && g.pad_t == 1 && g.pad_l == 1) || (g.taps == 1 && g.pad_t == 0 && g.pad_l == 0)))
-    return 2;
-  return 0;
-}
-int wgrad_smallk_tiles(const vae_wgrad_args& a) { return (int)(((int64_t)a.g.B * a.g.Ho * a.g.Wo + TP - 1) / TP); }
-// how a pixel of V and a tap map to a pixel of S
-static vae_conv_geom wgrad_smallk_geom(const vae_wgrad_args& a, int kind) {
-  vae_conv_geom gs = a.g;
-  if (kind == 2) {  // V = X over input pixels; S = dY at (y + pad - kh, x + pad - kw)
-    gs.mode = VAE_MODE_DGRAD;
-    gs.Cs = a.ldy;
-  }
-  return gs;
-}
-int launch_wgrad_thin_bf16(const vae_wgrad_args& a, int kind, const vae_conv_geom& gs, int ntiles, hipStream_t st);  // wgrad_thin_bf16.hip
-int launch_wgrad_thin(const vae_wgrad_args& a, hipStream_t st) {  // bf16 mode, wide side stored as bf16: the same launch on the matrix pipe
-  const int kind = wgrad_smallk_kind(a);
-  return launch_wgrad_thin_bf16(a, kind, wgrad_smallk_geom(a, kind), wgrad_smallk_tiles(a), st);
-}
+int wgrad_smallk_kind(const vae_wgrad_args& a) { return thin::wgrad_kind(a); }
+int wgrad_smallk_tiles(const vae_wgrad_args& a) { return thin::wgrad_tiles(a); }
 
 int launch_wgrad_smallk(const vae_wgrad_args& a, hipStream_t st) {
-  const int kind = wgrad_smallk_kind(a);
-  const int ntiles = wgrad_smallk_tiles(a);
-  const vae_conv_geom gs = wgrad_smallk_geom(a, kind);
-  const int wide = kind == 1 ? a.M : a.N;
-  dim3 grid((unsigned)a.nsplit, (unsigned)((wide + 127) / 128));
-#define WSK(SX, XFV) hipLaunchKernelGGL((wgrad_smallk_kernel<SX, XFV>), grid, dim3(NT), 0, st, a, gs, ntiles)
-  if (kind == 1) WSK(true, VAE_XF_NONE);
-  else if (a.xf == VAE_XF_NONE) WSK(false, VAE_XF_NONE);
-  else if (a.xf == VAE_XF_AFFINE) WSK(false, VAE_XF_AFFINE);
-  else WSK(false, VAE_XF_AFFINE_SILU);
-#undef WSK
+  const int kind = thin::wgrad_kind(a), ntiles = thin::wgrad_tiles(a);
+  const vae_conv_geom gs = thin::wgrad_geom(a, kind);
+  const dim3 grid = thin::wgrad_grid(a, kind);
+  if (kind == 1) hipLaunchKernelGGL((wgrad_smallk_kernel<true, VAE_XF_NONE>), grid, dim3(NT), 0, st, a, gs, ntiles);
+  else dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((wgrad_smallk_kernel<false, decltype(xf)::value>), grid, dim3(NT), 0, st, a, gs, ntiles); });
   return 0;
 }
 
@@ -263,7 +230,7 @@ int launch_wgrad_smallk(const vae_wgrad_args& a, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int NTH = 4, NTW = 32, NHW = NTW + 2, NHP = (NTH + 2) * NHW;  // 4x32 tile, 204 halo pixels
+constexpr int NTH = thin::TH, NTW = thin::TW, NHW = thin::HW, NHP = thin::HP;  // 4x32 tile, 204 halo pixels
 constexpr int NBK = 32, NLD = NBK + 4, NNT = 128;
 constexpr int NHQ = NHP * (NBK / 4), NHI = (NHQ + NNT - 1) / NNT;       // 1632 float4 slots, 13 per thread
 
@@ -272,11 +239,8 @@ __global__ __launch_bounds__(NNT) void conv_smalln_kernel(vae_igemm_args p, int 
   __shared__ __attribute__((aligned(16))) float sH[NHP * NLD];
   const vae_conv_geom g = p.g;
   const int tid = threadIdx.x;
-  int t = blockIdx.x;
-  const int tx = t % tiles_x; t /= tiles_x;
-  const int ty = t % tiles_y;
-  const int b = t / tiles_y;
-  const int y0 = ty * NTH, x0 = tx * NTW;
+  const thin::Tile tl = thin::decode(blockIdx.x, tiles_x, tiles_y);
+  const int b = tl.b, y0 = tl.y0, x0 = tl.x0;
   const int pr = tid >> 5, px = tid & 31;  // this lane's pixel of the tile
   const bool abf = p.a_bf16 != 0;
   const unsigned esA = abf ? 2u : 4u;
@@ -313,15 +277,8 @@ __global__ __launch_bounds__(NNT) void conv_smalln_kernel(vae_igemm_args p, int 
       const int q = tid + NNT * i;
       if (q < NHQ) {
         f32x4 v = raw4_to_f32(rh[i], abf);
-        if (XF != VAE_XF_NONE) {  // padding must stay zero after the transform
-          const bool ok = (hmask >> i) & 1;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float u = v[e] * rsc[e] + rsh[e];
-            if (XF == VAE_XF_AFFINE_SILU) u = silu_f(u);
-            v[e] = ok ? u : 0.f;
-          }
-        }
+        for (int e = 0; e < 4; ++e) v[e] = thin::xform1<XF>(v[e], rsc[e], rsh[e], (hmask >> i) & 1);  // padding stays zero after the transform
         *reinterpret_cast<f32x4*>(&sH[(q >> 3) * NLD + hk4 * 4]) = v;
       }
     }
@@ -362,7 +319,7 @@ __global__ __launch_bounds__(NNT) void conv_smalln_kernel(vae_igemm_args p, int 
     if (s < p.N) {
       const float v = acc[s] + (p.bias ? p.bias[s] : 0.f);
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC,
-                                            (oy < g.Ho && ox < g.Wo) ? (unsigned)(((oy * g.Wo + ox) * p.ldc + s) * 4) : BUF_OOB, 0, 0);
+                                            (oy < g.Ho && ox < g.Wo) ? (unsigned)((oy * g.Wo + ox) * p.ldc + s) * 4u : BUF_OOB, 0, 0);
     }
 }
 
@@ -371,18 +328,13 @@ __global__ __launch_bounds__(NNT) void conv_smalln_kernel(vae_igemm_args p, int 
 bool conv_smalln_eligible(const vae_igemm_args& a) {
   const vae_conv_geom& g = a.g;
   return a.N <= 4 && a.K >= NBK && a.K % NBK == 0 && a.sn % 4 == 0 && a.st % 4 == 0 && aligned16(a.W) && a.batch == 1 && a.res == nullptr && a.track == nullptr && a.alpha == 1.0f &&
-         a.A16 == nullptr && g.mode == VAE_MODE_FWD && g.taps == 9 && g.stride == 1 && g.pad_t == 1 && g.pad_l == 1 &&
-         g.Ho == g.Hs && g.Wo == g.Ws && g.Wo % NTW == 0 && g.Ho % NTH == 0 && a.sk == 1 && g.Cs % 4 == 0 && aligned16(a.A) &&
+         a.A16 == nullptr && thin::fwd_same_3x3(g) && g.Wo % NTW == 0 && g.Ho % NTH == 0 && a.sk == 1 && g.Cs % 4 == 0 && aligned16(a.A) &&
          (a.xf == VAE_XF_NONE || (aligned16(a.scale) && aligned16(a.shift))) &&
-         (size_t)g.Hs * g.Ws * g.Cs * 4u < BUF_MAX && (size_t)g.Ho * g.Wo * a.ldc * 4u < BUF_MAX;
+         thin::desc_fits(thin::image_elems(g), 4u) && thin::desc_fits((size_t)g.Ho * g.Wo * a.ldc, 4u);
 }
 int launch_conv_smalln(const vae_igemm_args& a, hipStream_t st) {
-  const int tx = a.g.Wo / NTW, ty = a.g.Ho / NTH;
-  dim3 grid((unsigned)((int64_t)tx * ty * a.g.B));
-  switch (a.xf) {
-    case VAE_XF_NONE: hipLaunchKernelGGL((conv_smalln_kernel<VAE_XF_NONE>), grid, dim3(NNT), 0, st, a, tx, ty); break;
-    case VAE_XF_AFFINE: hipLaunchKernelGGL((conv_smalln_kernel<VAE_XF_AFFINE>), grid, dim3(NNT), 0, st, a, tx, ty); break;
-    default: hipLaunchKernelGGL((conv_smalln_kernel<VAE_XF_AFFINE_SILU>), grid, dim3(NNT), 0, st, a, tx, ty); break;
-  }
+  int tx, ty;
+  const dim3 grid = thin::tile_grid(a.g, tx, ty);
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((conv_smalln_kernel<decltype(xf)::value>), grid, dim3(NNT), 0, st, a, tx, ty); });
   return 0;
 }

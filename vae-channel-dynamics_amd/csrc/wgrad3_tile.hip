@@ -233,12 +233,9 @@ int launch_wgrad3_tile(const vae_wgrad_args& a, hipStream_t st) {
   const int64_t nunits = wgrad3_tile_units(g);
   dim3 grid((unsigned)(((a.M + BMT - 1) / BMT) * (a.N / BNT)), (unsigned)a.nsplit, 1);
   const bool up = g.mode == VAE_MODE_UP2X;
-#define WG3(UPV, XFV) hipLaunchKernelGGL((wgrad3_tile_kernel<UPV, XFV>), grid, dim3(NT), 0, st, a, xblocks, nunits)
-  switch (a.xf) {
-    case VAE_XF_NONE: if (up) WG3(true, VAE_XF_NONE); else WG3(false, VAE_XF_NONE); break;
-    case VAE_XF_AFFINE: if (up) WG3(true, VAE_XF_AFFINE); else WG3(false, VAE_XF_AFFINE); break;
-    default: if (up) WG3(true, VAE_XF_AFFINE_SILU); else WG3(false, VAE_XF_AFFINE_SILU); break;
-  }
-#undef WG3
+  dispatch_xf_or_silu(a.xf, [&](auto xf) {
+    if (up) hipLaunchKernelGGL((wgrad3_tile_kernel<true, decltype(xf)::value>), grid, dim3(NT), 0, st, a, xblocks, nunits);
+    else hipLaunchKernelGGL((wgrad3_tile_kernel<false, decltype(xf)::value>), grid, dim3(NT), 0, st, a, xblocks, nunits);
+  });
   return 0;
 }

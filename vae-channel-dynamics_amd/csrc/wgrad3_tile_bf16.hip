@@ -498,11 +498,9 @@ int launch_wgrad3_tile_bf16(const vae_wgrad_args& a, hipStream_t st) {
     if (up) WG3(true, VAE_XF_NONE, true); else WG3(false, VAE_XF_NONE, true);
     return 0;
   }
-  switch (a.xf) {
-    case VAE_XF_NONE: if (up) WG3(true, VAE_XF_NONE, false); else WG3(false, VAE_XF_NONE, false); break;
-    case VAE_XF_AFFINE: if (up) WG3(true, VAE_XF_AFFINE, false); else WG3(false, VAE_XF_AFFINE, false); break;
-    default: if (up) WG3(true, VAE_XF_AFFINE_SILU, false); else WG3(false, VAE_XF_AFFINE_SILU, false); break;
-  }
+  dispatch_xf_or_silu(a.xf, [&](auto xf) {
+    if (up) WG3(true, decltype(xf)::value, false); else WG3(false, decltype(xf)::value, false);
+  });
 #undef WG3
   return 0;
 }

@@ -375,8 +375,6 @@ int launch_wgrad3_wino(const vae_wgrad_args& a, hipStream_t st) {
   const int64_t nunits = wgrad3_wino_units(g);
   dim3 grid((unsigned)((a.M / GCO) * (a.N / GCI) * a.nsplit), 1, 1);
   const int strips = g.Wo / 16;
-  if (a.xf == VAE_XF_NONE) hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_NONE>, grid, dim3(GNT), 0, st, a, strips, nunits);
-  else if (a.xf == VAE_XF_AFFINE) hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_AFFINE>, grid, dim3(GNT), 0, st, a, strips, nunits);
-  else hipLaunchKernelGGL(wgrad3_wino_kernel<VAE_XF_AFFINE_SILU>, grid, dim3(GNT), 0, st, a, strips, nunits);
+  dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL(wgrad3_wino_kernel<decltype(xf)::value>, grid, dim3(GNT), 0, st, a, strips, nunits); });
   return 0;
 }

@@ -14,12 +14,14 @@
 // Same slab protocol as wgrad_smallk_kernel (grid = splits x 128-channel blocks, tiles of 128 linear pixels dealt in ranges,
 // fixed order: deterministic), so vae_wgrad_plan / vae_reduce_splits are unchanged.  Workgroup = 4 waves, wave w owns wide
 // channels 32w..32w+31 (two accumulators); two workgroups per CU cover each other's staging.
-#include "bf16_frag.h"
-#include <algorithm>
+// The gather of the narrow tensor, the tile range of a split, the octet transform of the wide tensor, the slab protocol and the
+// host predicates (kind, tiles, gather geometry) are in thin_common.h, shared with skinny.hip and conv_thin_bf16.hip.
+#include "thin_common.h"
+#include "launchers.h"
 
 namespace {
 
-constexpr int WT_TP = 128;            // pixels per tile (the contraction length of a tile)
+constexpr int WT_TP = thin::TP;       // pixels per tile (the contraction length of a tile)
 constexpr int WT_NT = 256;
 constexpr int WT_LDW = 128 + 32;      // wide image row stride (u16): 320 B, transposing reads conflict-free (bf16_frag.h)
 constexpr int WT_LDT = WT_TP + 8;     // thin plane row stride (u16): 272 B
@@ -42,8 +44,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
   const int ldv = SMALL_X ? p.ldy : p.g.Cs, lds_ = SMALL_X ? p.g.Cs : p.ldy;
   const int npix = gs.B * gs.Ho * gs.Wo, hw = gs.Ho * gs.Wo;
   const auto rsV = VAE_BUF_RSRC(V, (size_t)npix * ldv * 2u);
-  const size_t sbytes = (size_t)gs.B * gs.Hs * gs.Ws * lds_ * 4u;
-  const auto rsS = VAE_BUF_RSRC(S, sbytes);
+  const auto rsS = thin::narrow_rsrc(S, gs, lds_);
 
   // rows 36..63 of T never change: zeros, and (SMALL_X) row 36 = ones -> out row 36 = column sums of dY = the bias gradient
   for (int i = tid; i < (WT_MR - 36) * WT_LDT; i += WT_NT) {
@@ -78,18 +79,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
     for (int i = 0; i < WT_ITEMS; ++i) {
       const int e = tid + WT_NT * i;
       const int row = e / 9, tap = e - row * 9;
-      const int m = m0 + row;
-      const int b = m / hw, rem = m - b * hw;
-      const int y = rem / gs.Wo, x = rem - y * gs.Wo;
-      const int kh = tap / 3, kw = tap - kh * 3;
-      int sy = 0, sx = 0;
-      const bool ok = valid && e < WT_TP * 9 && src_pixel(gs, y, x, kh, kw, sy, sx);
-      const unsigned base = oob_unless(ok, (unsigned)(((b * gs.Hs + sy) * gs.Ws + sx) * lds_) * 4u);
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        if (s < narrow) v[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsS, base, 4u * s, 0));
-      rt[i] = v;
+      rt[i] = thin::gather4(gs, rsS, lds_, narrow, hw, m0 + row, tap, valid && e < WT_TP * 9);
     }
   };
   auto store_tile = [&](int tile) {
@@ -105,26 +95,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
       }
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      uint4 r = rw[i];
-      if (XF != VAE_XF_NONE) {
-        const f32x4 lo = unpack4(uint2{r.x, r.y}), hi = unpack4(uint2{r.z, r.w});
-        f32x4 a, bq;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float u = lo[e] * sc[e] + sh[e], w = hi[e] * sc[4 + e] + sh[4 + e];
-          if (XF == VAE_XF_AFFINE_SILU) {
-            u = silu_f(u);
-            w = silu_f(w);
-          }
-          a[e] = u;
-          bq[e] = w;
-        }
-        const uint2 pa = pack4(a), pb = pack4(bq);
-        r = uint4{pa.x, pa.y, pb.x, pb.y};
-      }
-      *reinterpret_cast<uint4*>(&sW[((tid >> 4) + 16 * i) * WT_LDW + oct * 8]) = r;
-    }
+    for (int i = 0; i < 8; ++i)  // (whole tiles only: no pixel of the wide tensor is padding)
+      *reinterpret_cast<uint4*>(&sW[((tid >> 4) + 16 * i) * WT_LDW + oct * 8]) = thin::xform8_bf16<XF>(rw[i], sc, sh, true);
 #pragma unroll
     for (int i = 0; i < WT_ITEMS; ++i) {
       const int e = tid + WT_NT * i;
@@ -138,8 +110,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
     }
   };
 
-  const int per = (ntiles + p.nsplit - 1) / p.nsplit;
-  const int tbeg = split * per, tend = min(ntiles, tbeg + per);
+  const thin::TileRange tr = thin::tile_range(split, thin::tiles_per_part(ntiles, p.nsplit), ntiles);
+  const int tbeg = tr.beg, tend = tr.end;
   const int aoff = lr * WT_LDT + 8 * lh;                                              // + 32 mt rows, + 16 ks pixels
   const int boff = (lh * 8 + trq) * WT_LDW + wave * 32 + trh * 16 + trp * 4;           // + 16 ks pixel rows
   if (tbeg < tend) load_tile(tbeg, true);
@@ -160,8 +132,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
   }
 
   // slab of this split: row m = (tap, s) of the product, column = wide channel (lane lr of wave w: c0 + 32 w + lr)
-  const int64_t ld = (int64_t)9 * p.N;
-  float* __restrict__ O = (p.nsplit == 1 ? p.out : p.partial + (int64_t)split * p.M * ld);
+  const thin::Slab sl = thin::slab_of(p, split, 9);
   const int ch = c0 + wave * 32 + lr;
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
@@ -169,11 +140,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
     for (int r = 0; r < 16; ++r) {
       const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
       const int t = m >> 2, s = m & 3;
-      if (m < 36 && s < narrow) {
-        if (SMALL_X) O[(int64_t)ch * ld + (int64_t)t * p.N + s] = p.alpha * acc[mt][r];
-        else O[(int64_t)s * ld + (int64_t)t * p.N + ch] = p.alpha * acc[mt][r];
-      }
-      if (SMALL_X && m == 36 && p.bias_partial) p.bias_partial[(int64_t)split * p.M + ch] = acc[mt][r];
+      if (m < 36 && s < narrow) thin::slab_store<SMALL_X>(sl, ch, t, s, acc[mt][r]);
+      if (SMALL_X && m == 36 && p.bias_partial) thin::bias_partial_row(p, split)[ch] = acc[mt][r];
     }
   if (!SMALL_X && p.bias_partial && blockIdx.y == 0) {  // sums of dY: 256 threads' shares, fixed order
     __syncthreads();
@@ -183,7 +151,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
     if (tid < p.M) {
       float t = 0.f;
       for (int i = 0; i < WT_NT; ++i) t += sB[tid * WT_NT + i];
-      p.bias_partial[(int64_t)split * p.M + tid] = t;
+      thin::bias_partial_row(p, split)[tid] = t;
     }
   }
 }
@@ -194,26 +162,22 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_thin_bf16_kernel(vae_wgrad_arg
 bool wgrad_thin_bf16_eligible(const vae_wgrad_args& a, int kind) {
   const vae_conv_geom& g = a.g;
   if (a.prec != VAE_PREC_BF16 || kind == 0 || a.batch != 1 || a.X16 != nullptr || a.dY16 != nullptr) return false;
-  if (g.mode != VAE_MODE_FWD || g.taps != 9 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.Ho != g.Hs || g.Wo != g.Ws) return false;
+  if (!thin::fwd_same_3x3(g)) return false;
   if (((int64_t)g.Ho * g.Wo) % WT_TP != 0) return false;  // whole 128-pixel tiles, each inside one image
   if (kind == 1) {
     if (!a.y_bf16 || a.x_bf16 || a.xf != VAE_XF_NONE || a.M % 128 != 0 || a.ldy % 8 != 0 || !aligned16(a.dY)) return false;
-    if ((size_t)a.npix * a.ldy * 2u >= BUF_MAX || (size_t)g.B * g.Hs * g.Ws * g.Cs * 4u >= BUF_MAX) return false;
-  } else {
-    if (!a.x_bf16 || a.y_bf16 || a.N % 128 != 0 || g.Cs % 8 != 0 || !aligned16(a.X)) return false;
-    if ((size_t)a.npix * g.Cs * 2u >= BUF_MAX || (size_t)a.npix * a.ldy * 4u >= BUF_MAX) return false;
+    return thin::desc_fits((size_t)a.npix * a.ldy, 2u) && thin::narrow_fits(g);
   }
-  return true;
+  if (!a.x_bf16 || a.y_bf16 || a.N % 128 != 0 || g.Cs % 8 != 0 || !aligned16(a.X)) return false;
+  return thin::desc_fits((size_t)a.npix * g.Cs, 2u) && thin::desc_fits((size_t)a.npix * a.ldy, 4u);
 }
 
-int launch_wgrad_thin_bf16(const vae_wgrad_args& a, int kind, const vae_conv_geom& gs, int ntiles, hipStream_t st) {
-  const int wide = kind == 1 ? a.M : a.N;
-  dim3 grid((unsigned)a.nsplit, (unsigned)(wide / 128));
-#define WTK(SX, XFV) hipLaunchKernelGGL((wgrad_thin_bf16_kernel<SX, XFV>), grid, dim3(WT_NT), 0, st, a, gs, ntiles)
-  if (kind == 1) WTK(true, VAE_XF_NONE);
-  else if (a.xf == VAE_XF_NONE) WTK(false, VAE_XF_NONE);
-  else if (a.xf == VAE_XF_AFFINE) WTK(false, VAE_XF_AFFINE);
-  else WTK(false, VAE_XF_AFFINE_SILU);
-#undef WTK
+// bf16 mode, wide side stored as bf16: the launch of launch_wgrad_smallk on the matrix pipe
+int launch_wgrad_thin(const vae_wgrad_args& a, hipStream_t st) {
+  const int kind = thin::wgrad_kind(a), ntiles = thin::wgrad_tiles(a);
+  const vae_conv_geom gs = thin::wgrad_geom(a, kind);
+  const dim3 grid = thin::wgrad_grid(a, kind);
+  if (kind == 1) hipLaunchKernelGGL((wgrad_thin_bf16_kernel<true, VAE_XF_NONE>), grid, dim3(WT_NT), 0, st, a, gs, ntiles);
+  else dispatch_xf_or_silu(a.xf, [&](auto xf) { hipLaunchKernelGGL((wgrad_thin_bf16_kernel<false, decltype(xf)::value>), grid, dim3(WT_NT), 0, st, a, gs, ntiles); });
   return 0;
 }
