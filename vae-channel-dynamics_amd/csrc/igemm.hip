@@ -7,9 +7,15 @@
 //     - weight tile n-contiguous ([BK][BN], BKM = true)  : conv/linear dgrad, P.V, dS.K
 //   wgrad  (contraction over pixels; both tiles pixel-major, [BK px][BM] and [BK px][BN]) : conv/linear wgrad, P^T.dO, dS^T.Q
 //
-// There is ONE rows body and ONE wgrad body.  Each is instantiated under two arithmetic policies:
-//   F32  (VAE_PREC_F32) : exact fp32 products, fp32 accumulate, on v_mfma_f32_32x32x2_f32.  Serves any shape: the
-//         unvectorised instantiations (VEC = false) load element by element.
+// There is ONE rows body and ONE wgrad body.  Each is instantiated under three arithmetic policies:
+//   F32  (VAE_PREC_F32): exact fp32 products, fp32 accumulate, on v_mfma_f32_32x32x2_f32.  Serves any shape: the unvectorised
+//         instantiations (VEC = false) load element by element.  Also the vectorised 4-wave skinny tiles (128 x 32, 32 x 128).
+//   F32X3 (VAE_PREC_F32, VEC = true, the 8-wave 128 x 128 tile): fp32 operands and results, but NOT exact fp32 products: every
+//         operand value is split into three bf16 planes while staged in LDS and a product is six bf16 plane products on
+//         v_mfma_f32_32x32x16_bf16, fp32 accumulate (<= 2^-25 of |a b| per product; the matrix pipe is busy 2.67 x shorter than
+//         with the fp32 MFMA).  A finite operand in the top 2^-8 of the fp32 range rounds to Inf in its first plane; Inf / NaN
+//         stay non-finite (see the policy).  -DVAE_FLAT_X3=0 puts these instantiations back on F32 (the A/B arm: the bits of
+//         exact fp32 products).
 //   BF16 (VAE_PREC_BF16): operands rounded to bf16 while staged in LDS, products on v_mfma_f32_32x32x16_bf16, fp32 accumulate.
 //         Every activation operand is stored as fp32 or as bf16, per tensor (a_bf16 / out_bf16 / res_bf16, x_bf16 / y_bf16:
 //         wave-uniform switches on the load / store instructions; the weights W are always the fp32 master copy).  Only the
@@ -53,18 +59,23 @@ struct F32 {
   static constexpr int PAD_K = 4, PAD_T = 4;
   static constexpr bool SETPRIO = true;  // s_setprio brackets the MFMA block
   static constexpr bool PAIR16 = false;
+  // An operand tile is PLANES images of the tile in LDS, a plane stride apart (the stride is the body's: one tile); the staging
+  // and fragment functions take that stride.  One plane here.  LDS_DYNAMIC: the stages are the kernel's dynamic LDS, which the
+  // launcher sizes (rows_lds_elems / wgrad_lds_elems) and reserves (VAE_RESERVE_LDS); else a static array of the body.
+  static constexpr int PLANES = 1;
+  static constexpr bool LDS_DYNAMIC = false;
   static constexpr bool flag(int32_t) { return false; }  // operands and results are fp32: no storage switch exists
 
   static __device__ __forceinline__ raw4 load4(__amdgpu_buffer_rsrc_t rs, unsigned, bool ok, int row, int ld, int c) {
     return VAE_BUF_LOAD4(rs, oob_unless(ok, ((unsigned)row * (unsigned)ld + (unsigned)c) * 4u));
   }
   static __device__ __forceinline__ f32x4 to_f32(raw4 r, bool) { return r; }
-  static __device__ __forceinline__ void put4(elem* d, f32x4 v) { *reinterpret_cast<f32x4*>(d) = v; }
-  static __device__ __forceinline__ void put4_stored(elem* d, raw4, f32x4 v, bool) { put4(d, v); }
+  static __device__ __forceinline__ void put4(elem* d, f32x4 v, int) { *reinterpret_cast<f32x4*>(d) = v; }
+  static __device__ __forceinline__ void put4_stored(elem* d, raw4, f32x4 v, bool, int) { put4(d, v, 0); }
   // 4 consecutive k at p (one ds_read_b128)
-  static __device__ __forceinline__ frag frag_k(const elem* p) { return *reinterpret_cast<const f32x4*>(p); }
+  static __device__ __forceinline__ frag frag_k(const elem* p, int) { return *reinterpret_cast<const f32x4*>(p); }
   // the same 4 k of k-group kg from a [k][col] tile: this lane's column of the 32 from col0
-  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0) {
+  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0, int) {
     frag v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = tile[(kg * 8 + l.lh * 4 + j) * ld + col0 + l.lr];
@@ -73,7 +84,8 @@ struct F32 {
   // both operands from [k][col] tiles (wgrad), MI / NI fragments from columns colA / colB on.  The a and b reads alternate
   // per k row: the compiler's pairing of the dword reads, and with it the register count, follows the source order.
   template <int MI, int NI>
-  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l) {
+  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l,
+                                                  int, int) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = kg * 8 + l.lh * 4 + j;
@@ -116,27 +128,30 @@ struct BF16 {
   static constexpr int PAD_K = 8, PAD_T = 32;
   static constexpr bool SETPRIO = false;
   static constexpr bool PAIR16 = true;  // the rows epilogue has the paired 4-byte bf16 store
+  static constexpr int PLANES = 1;
+  static constexpr bool LDS_DYNAMIC = false;
   static __device__ __forceinline__ bool flag(int32_t v) { return v != 0; }  // storage of an operand / result (uniform)
 
   static __device__ __forceinline__ raw4 load4(__amdgpu_buffer_rsrc_t rs, unsigned esize, bool ok, int row, int ld, int c) {
     return buf_load4_raw(rs, esize, neg_unless(ok, row * ld + c));
   }
   static __device__ __forceinline__ f32x4 to_f32(raw4 r, bool bf) { return raw4_to_f32(r, bf); }
-  static __device__ __forceinline__ void put4(elem* d, f32x4 v) { *reinterpret_cast<uint2*>(d) = pack4(v); }
+  static __device__ __forceinline__ void put4(elem* d, f32x4 v, int) { *reinterpret_cast<uint2*>(d) = pack4(v); }
   // an operand that is staged untransformed and already stored as bf16 goes to LDS as loaded
-  static __device__ __forceinline__ void put4_stored(elem* d, raw4 r, f32x4 v, bool bf) {
+  static __device__ __forceinline__ void put4_stored(elem* d, raw4 r, f32x4 v, bool bf, int) {
     *reinterpret_cast<uint2*>(d) = bf ? uint2{r.x, r.y} : pack4(v);
   }
-  static __device__ __forceinline__ frag frag_k(const elem* p) { return frag_direct(p); }
-  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0) {
+  static __device__ __forceinline__ frag frag_k(const elem* p, int) { return frag_direct(p); }
+  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0, int) {
     return frag_tr(tile + (kg * 16 + l.lh * 8 + l.trq) * ld + col0 + l.trh * 16 + l.trp * 4, ld);
   }
   template <int MI, int NI>
-  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l) {
+  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l,
+                                                  int, int) {
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) a[mi] = frag_t(sA, ldA, kg, l, colA + mi * 32);
+    for (int mi = 0; mi < MI; ++mi) a[mi] = frag_t(sA, ldA, kg, l, colA + mi * 32, 0);
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) b[ni] = frag_t(sB, ldB, kg, l, colB + ni * 32);
+    for (int ni = 0; ni < NI; ++ni) b[ni] = frag_t(sB, ldB, kg, l, colB + ni * 32, 0);
   }
   template <int MI, int NI>
   static __device__ __forceinline__ void mma(f32x16 (&acc)[MI][NI], const frag* a, const frag* b) {
@@ -197,6 +212,102 @@ struct BF16 {
   }
 };
 
+// F32X3: fp32 operands and results, products on the bf16 matrix pipe: each operand value a is staged as three bf16 planes
+//   hi = bf16(a), mid = bf16(a - hi), lo = bf16((a - hi) - mid)      (round to nearest even; both subtractions are exact in fp32)
+// so that hi + mid + lo = a up to 2^-26 |a|, and a.b is the sum of the six bf16 products that are not below 2^-24 |a.b|, added
+// into the fp32 accumulator smallest first.  Everything outside LDS (loads, descriptors, transform, epilogue) is F32's; the LDS
+// image and the fragment reads are BF16's, once per plane.  K step: at 32 the three planes of both 128-row tiles, double buffered,
+// are 120 KB, one 8-wave workgroup per CU, and the kernels gained 1.3 x over exact fp32; at 16 (one k-group per step and barrier)
+// they are 72 KB, TWO workgroups per CU as under F32, and the gain is 1.5 x (tools/flat_x3_ab.py, profiles/flat_x3_measured.json).
+// The stages are dynamic LDS (62-78 KB by instantiation).  8-wave tiles only (F32For): a 4-wave loader pass covers 32 k.
+// Non-finite and extreme operands: Inf and NaN stay non-finite (Inf - Inf makes the lower planes NaN, so a product that exact
+// fp32 gives as Inf may come out NaN); a finite value in the top 2^-8 of the fp32 range rounds to Inf in the hi plane and then
+// behaves like Inf; mid / lo planes that fall below the bf16 normal range may flush to zero, hi carries the value.
+#ifndef VAE_FLAT_X3
+#define VAE_FLAT_X3 1
+#endif
+struct F32X3 : F32 {
+  typedef u16 elem;
+  struct frag { bf16x8 p[3]; };  // 8 k per lane half of every plane
+  static constexpr int BK_ROWS = 16, BK_WGRAD = 16;  // one k-group per step
+  static constexpr int KG = 16;
+  // k-contiguous rows: 48 B row stride, 3 i mod 16: distinct 16-B slots for the 16 rows of a b128 lane group, conflict-free
+  // ds_read_b128.  [k][col] rows as BF16.
+  static constexpr int PAD_K = 8, PAD_T = 32;
+  static constexpr bool SETPRIO = false;
+  static constexpr int PLANES = 3;
+  static constexpr bool LDS_DYNAMIC = true;
+
+  static __device__ __forceinline__ void put4(elem* d, f32x4 v, int ps) {
+    const uint2 hi = pack4(v);
+    const f32x4 h = unpack4(hi);
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = v[e] - h[e];
+    const uint2 mid = pack4(r);
+    const f32x4 m = unpack4(mid);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = r[e] - m[e];
+    *reinterpret_cast<uint2*>(d) = hi;
+    *reinterpret_cast<uint2*>(d + ps) = mid;
+    *reinterpret_cast<uint2*>(d + 2 * ps) = pack4(r);
+  }
+  static __device__ __forceinline__ void put4_stored(elem* d, raw4, f32x4 v, bool, int ps) { put4(d, v, ps); }
+  static __device__ __forceinline__ frag frag_k(const elem* p, int ps) {
+    frag f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) f.p[q] = BF16::frag_k(p + q * ps, 0);
+    return f;
+  }
+  static __device__ __forceinline__ frag frag_t(const elem* tile, int ld, int kg, LanePos l, int col0, int ps) {
+    frag f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) f.p[q] = BF16::frag_t(tile + q * ps, ld, kg, l, col0, 0);
+    return f;
+  }
+  template <int MI, int NI>
+  static __device__ __forceinline__ void frags_tt(frag* a, frag* b, const elem* sA, int ldA, int colA, const elem* sB, int ldB, int colB, int kg, LanePos l,
+                                                  int psA, int psB) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) a[mi] = frag_t(sA, ldA, kg, l, colA + mi * 32, psA);
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) b[ni] = frag_t(sB, ldB, kg, l, colB + ni * 32, psB);
+  }
+  // term by term over the wave tile (the accumulators alternate), smallest terms first: hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi
+  template <int MI, int NI>
+  static __device__ __forceinline__ void mma(f32x16 (&acc)[MI][NI], const frag* a, const frag* b) {
+    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].p[PA[t]], b[ni].p[PB[t]], acc[mi][ni], 0, 0, 0);
+  }
+};
+
+// the policy of the fp32 instantiations: F32X3 for the vectorised 8-wave tile (128 x 128).  The 4-wave skinny tiles (128 x 32,
+// 32 x 128) keep exact fp32 products: measured under F32X3 they were no faster (rows 1.01-1.04 x the time) or slower (the weight
+// gradient behind a fused GroupNorm 1.32 x): profiles/flat_x3_measured.json.  VAE_FLAT_X3 = 0: exact fp32 products everywhere
+// (the A/B arm)
+template <bool VEC, int WAVES>
+using F32For = std::conditional_t<VEC && WAVES == 8 && (VAE_FLAT_X3 != 0), F32X3, F32>;
+
+// LDS elements of a body: two stages of PLANES x (A tile + B tile), and the GroupNorm scale / shift table behind them
+template <class P, int BM, int BN, bool BKM, int XF>
+constexpr int rows_lds_elems() {
+  constexpr int BK = P::BK_ROWS;
+  return 2 * P::PLANES * (BM * (BK + P::PAD_K) + (BKM ? BK * (BN + P::PAD_T) : BN * (BK + P::PAD_K))) +
+         ((XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(typename P::elem)) : 0);
+}
+template <class P, int BM, int BN, int XF>
+constexpr int wgrad_lds_elems() {
+  return 2 * P::PLANES * P::BK_WGRAD * (BM + P::PAD_T + BN + P::PAD_T) + ((XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(typename P::elem)) : 0);
+}
+// the stages' storage: static, or the kernel's dynamic LDS where the policy says so (the launcher passes *_lds_elems)
+extern __shared__ __attribute__((aligned(16))) unsigned char lds_dynamic[];
+
 template <int MI, int NI>
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NI]) {
 #pragma unroll
@@ -210,7 +321,7 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NI]) {
 // ---------------------------------------------------------------------------------------
 // rows body.  Pipeline: LDS is double buffered; the global loads of K-step s+2 are issued and the registers of step s+1 are
 // transformed + written to the other LDS stage in the MIDDLE of step s's MFMA block, so one workgroup barrier per K-step
-// suffices and the VALU/LDS-write work sits in the shadow of MFMAs already issued.  A step is NKG = 2 or 4 k-groups.  The
+// suffices and the VALU/LDS-write work sits in the shadow of MFMAs already issued.  A step is NKG = 1, 2 or 4 k-groups.  The
 // GroupNorm scale/shift rows the tile needs are staged in LDS once per workgroup (they used to be 8 dependent global loads
 // per thread per step).
 // (The pipeline driver -- compute and the step loop -- is written out in both bodies: behind a shared function hipcc's
@@ -227,14 +338,17 @@ __device__ __forceinline__ void rows_body(const vae_igemm_args& p) {
   constexpr int LDB = BKM ? (BN + P::PAD_T) : (BK + P::PAD_K);
   constexpr int SA = BM * LDA;
   constexpr int SB = BKM ? BK * LDB : BN * LDB;
-  constexpr int STAGE = SA + SB;  // elements
+  constexpr int PL = P::PLANES;   // planes of a tile, SA / SB apart
+  constexpr int STAGE = PL * (SA + SB);  // elements
   constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(elem)) : 0;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
   constexpr int AR = BM / RP;  // A rows per thread
   constexpr int NQ = BN / 4, KR = NT / NQ;  // n-contiguous weight tile: NQ float4 per k row, KR k rows per pass
   constexpr int BR = BKM ? (BK / KR) : (BN / RP);
-  static_assert(AR >= 1 && BR >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
-  __shared__ __attribute__((aligned(16))) elem smem[2 * STAGE + SS];
+  static_assert(AR >= 1 && BR >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 1 || BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
+  static_assert(2 * STAGE + SS == rows_lds_elems<P, BM, BN, BKM, XF>(), "the launcher reserves what the body lays out");
+  __shared__ __attribute__((aligned(16))) elem smem_static[P::LDS_DYNAMIC ? 1 : 2 * STAGE + SS];
+  elem* const smem = P::LDS_DYNAMIC ? reinterpret_cast<elem*>(lds_dynamic) : smem_static;
   float* sS = reinterpret_cast<float*>(smem + 2 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -374,23 +488,23 @@ __device__ __forceinline__ void rows_body(const vae_igemm_args& p) {
         const int o = ok ? (a_b[i] - b_lo) * p.K + c : 0;
         v = xform4_tab<XF>(v, sS + o, sS + SS_HALF + o, ok);
       }
-      P::put4(&sA[(r0 + RP * i) * LDA + k4 * 4], v);
+      P::put4(&sA[(r0 + RP * i) * LDA + k4 * 4], v, SA);
     }
 #pragma unroll
     for (int i = 0; i < BR; ++i) {
-      if (!BKM) P::put4(&sB[(r0 + RP * i) * LDB + k4 * 4], rw[i]);
-      else P::put4(&sB[(kq + KR * i) * LDB + n4 * 4], rw[i]);
+      if (!BKM) P::put4(&sB[(r0 + RP * i) * LDB + k4 * 4], rw[i], SB);
+      else P::put4(&sB[(kq + KR * i) * LDB + n4 * 4], rw[i], SB);
     }
   };
   // fragments of k-group kg+1 are requested before the MFMAs of kg are issued (pinned with sched_barrier)
   typename P::frag fa[2][MI], fb[2][NI];
   auto fetch = [&](const elem* sA, const elem* sB, int kg, typename P::frag* a, typename P::frag* b) {
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) a[mi] = P::frag_k(&sA[(wm * TM + mi * 32 + lr) * LDA + kg * P::KG + lh * (P::KG / 2)]);
+    for (int mi = 0; mi < MI; ++mi) a[mi] = P::frag_k(&sA[(wm * TM + mi * 32 + lr) * LDA + kg * P::KG + lh * (P::KG / 2)], SA);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      if (!BKM) b[ni] = P::frag_k(&sB[(wn * TN + ni * 32 + lr) * LDB + kg * P::KG + lh * (P::KG / 2)]);
-      else b[ni] = P::frag_t(sB, LDB, kg, lp, wn * TN + ni * 32);
+      if (!BKM) b[ni] = P::frag_k(&sB[(wn * TN + ni * 32 + lr) * LDB + kg * P::KG + lh * (P::KG / 2)], SB);
+      else b[ni] = P::frag_t(sB, LDB, kg, lp, wn * TN + ni * 32, SB);
     }
   };
   constexpr int NKG = BK / P::KG;
@@ -404,18 +518,18 @@ __device__ __forceinline__ void rows_body(const vae_igemm_args& p) {
   };
   load_regs(0);
   __syncthreads();  // scale/shift table visible
-  store_lds(smem, smem + SA);
+  store_lds(smem, smem + PL * SA);
   if (steps > 1) load_regs(1);
   __syncthreads();
   for (int s = 0; s < steps; ++s) {
     const elem* cA = smem + (s & 1) * STAGE;
-    const elem* cB = cA + SA;
+    const elem* cB = cA + PL * SA;
     fetch(cA, cB, 0, fa[0], fb[0]);
-    compute(cA, cB, 0);
+    if (NKG > 1) compute(cA, cB, 0);  // (a step of one k-group: its fragments are requested, then the staging, then its MFMAs)
     if (NKG == 4) compute(cA, cB, 1);
     if (s + 1 < steps) {  // staged in the shadow of the MFMAs already issued
       elem* nA = smem + ((s + 1) & 1) * STAGE;
-      store_lds(nA, nA + SA);
+      store_lds(nA, nA + PL * SA);
       if (s + 2 < steps) load_regs(s + 2);
     }
     compute(cA, cB, NKG / 2);
@@ -503,13 +617,16 @@ __device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
   constexpr int NT = 64 * WM * WN;
   constexpr int LDA = BM + P::PAD_T, LDB = BN + P::PAD_T;
   constexpr int SA = BK * LDA, SB = BK * LDB;
-  constexpr int STAGE = SA + SB;
+  constexpr int PL = P::PLANES;
+  constexpr int STAGE = PL * (SA + SB);
   constexpr int SS = (XF != VAE_XF_NONE) ? 2 * SS_HALF * (4 / (int)sizeof(elem)) : 0;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
   constexpr int AQ = BM / 4, AKR = NT / AQ, AI = BK / AKR;  // dY tile: AQ float4 per row
   constexpr int BQ = BN / 4, BKR = NT / BQ, BI = BK / BKR;
-  static_assert(AI >= 1 && BI >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
-  __shared__ __attribute__((aligned(16))) elem smem[2 * STAGE + SS];
+  static_assert(AI >= 1 && BI >= 1 && TM % 32 == 0 && TN % 32 == 0 && (BK / P::KG == 1 || BK / P::KG == 2 || BK / P::KG == 4), "tile/wave layout");
+  static_assert(2 * STAGE + SS == wgrad_lds_elems<P, BM, BN, XF>(), "the launcher reserves what the body lays out");
+  __shared__ __attribute__((aligned(16))) elem smem_static[P::LDS_DYNAMIC ? 1 : 2 * STAGE + SS];
+  elem* const smem = P::LDS_DYNAMIC ? reinterpret_cast<elem*>(lds_dynamic) : smem_static;
   float* sS = reinterpret_cast<float*>(smem + 2 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -592,7 +709,7 @@ __device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
       const f32x4 v = P::to_f32(ra[i], ybf);
-      P::put4_stored(&sA[(akq + AKR * i) * LDA + a4 * 4], ra[i], v, ybf);
+      P::put4_stored(&sA[(akq + AKR * i) * LDA + a4 * 4], ra[i], v, ybf, SA);
       if (do_bias) bsum += v;
     }
 #pragma unroll
@@ -603,12 +720,12 @@ __device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
         const int o = ok ? (xb[i] - b_lo) * BN + b4 * 4 : 0;
         v = xform4_tab<XF>(v, sS + o, sS + SS_HALF + o, ok);
       }
-      P::put4(&sB[(bkq + BKR * i) * LDB + b4 * 4], v);
+      P::put4(&sB[(bkq + BKR * i) * LDB + b4 * 4], v, SB);
     }
   };
   typename P::frag fa[2][MI], fb[2][NI];
   auto fetch = [&](const elem* sA, const elem* sB, int kg, typename P::frag* a, typename P::frag* b) {
-    P::template frags_tt<MI, NI>(a, b, sA, LDA, wm * TM, sB, LDB, wn * TN, kg, lp);
+    P::template frags_tt<MI, NI>(a, b, sA, LDA, wm * TM, sB, LDB, wn * TN, kg, lp, SA, SB);
   };
   constexpr int NKG = BK / P::KG;
   auto compute = [&](const elem* sA, const elem* sB, int kg) {  // fragments of kg already requested
@@ -622,18 +739,18 @@ __device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
   if (steps > 0) {
     load_regs(0);
     __syncthreads();  // scale/shift table visible
-    store_lds(smem, smem + SA);
+    store_lds(smem, smem + PL * SA);
     if (steps > 1) load_regs(1);
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
       const elem* cA = smem + (s & 1) * STAGE;
-      const elem* cB = cA + SA;
+      const elem* cB = cA + PL * SA;
       fetch(cA, cB, 0, fa[0], fb[0]);
-      compute(cA, cB, 0);
+      if (NKG > 1) compute(cA, cB, 0);
       if (NKG == 4) compute(cA, cB, 1);
       if (s + 1 < steps) {  // staged in the shadow of the MFMAs already issued
         elem* nA = smem + ((s + 1) & 1) * STAGE;
-        store_lds(nA, nA + SA);
+        store_lds(nA, nA + PL * SA);
         if (s + 2 < steps) load_regs(s + 2);
       }
       compute(cA, cB, NKG / 2);
@@ -674,9 +791,9 @@ __device__ __forceinline__ void wgrad_body(const vae_wgrad_args& p) {
 
 // entry points: a body under its policy
 template <int BM, int BN, int WM, int WN, bool BKM, bool VEC, int XF>
-__global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args p) { rows_body<F32, BM, BN, WM, WN, BKM, VEC, XF>(p); }
+__global__ __launch_bounds__(64 * WM * WN) void igemm_rows_kernel(vae_igemm_args p) { rows_body<F32For<VEC, WM * WN>, BM, BN, WM, WN, BKM, VEC, XF>(p); }
 template <int BM, int BN, int WM, int WN, bool VEC, int XF>
-__global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) { wgrad_body<F32, BM, BN, WM, WN, VEC, XF>(p); }
+__global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(vae_wgrad_args p) { wgrad_body<F32For<VEC, WM * WN>, BM, BN, WM, WN, VEC, XF>(p); }
 template <int BM, int BN, int WM, int WN, bool BKM, int XF>
 __global__ __launch_bounds__(64 * WM * WN) void igemm_rows_bf16_kernel(vae_igemm_args p) { rows_body<BF16, BM, BN, WM, WN, BKM, true, XF>(p); }
 template <int BM, int BN, int WM, int WN, int XF>
@@ -912,9 +1029,18 @@ int launch_rows_tile(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st
   const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), 1, (unsigned)a.batch), block(64 * WM * WN);
   auto go = [&](auto bkm_c, auto vec_c) {
     constexpr bool BKM = decltype(bkm_c)::value, VEC = decltype(vec_c)::value;
+    int rc = 0;  // of the LDS reservation
     auto launch = [&](auto xf) {
-      if constexpr (BF) hipLaunchKernelGGL((igemm_rows_bf16_kernel<BM, BN, WM, WN, BKM, decltype(xf)::value>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, decltype(xf)::value>), grid, block, 0, st, a);
+      constexpr int XF = decltype(xf)::value;
+      if constexpr (BF) {
+        hipLaunchKernelGGL((igemm_rows_bf16_kernel<BM, BN, WM, WN, BKM, XF>), grid, block, 0, st, a);
+      } else if constexpr (F32For<VEC, WM * WN>::LDS_DYNAMIC) {
+        constexpr int LDS = rows_lds_elems<F32For<VEC, WM * WN>, BM, BN, BKM, XF>() * (int)sizeof(typename F32For<VEC, WM * WN>::elem);
+        if (rc == 0) rc = [&]() -> int { VAE_RESERVE_LDS((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, XF>), LDS, "igemm_rows"); return 0; }();
+        if (rc == 0) hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, XF>), grid, block, LDS, st, a);
+      } else {
+        hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, BKM, VEC, XF>), grid, block, 0, st, a);
+      }
     };
     if constexpr (BKM) {  // the n-contiguous weight tile exists untransformed only
       if (a.xf != VAE_XF_NONE) { vae_set_error("igemm_rows: xf unsupported with n-contiguous weights"); return VAE_EINVAL; }
@@ -923,7 +1049,7 @@ int launch_rows_tile(const vae_igemm_args& a, bool bkm, bool vec, hipStream_t st
       vae_set_error("igemm_rows: bad xf %d", a.xf);
       return VAE_EINVAL;
     }
-    return 0;
+    return rc;
   };
   if (BF || vec) return bkm ? go(true_type{}, true_type{}) : go(false_type{}, true_type{});
   if constexpr (!BF) return bkm ? go(true_type{}, false_type{}) : go(false_type{}, false_type{});
@@ -938,11 +1064,21 @@ template <bool BF, int BM, int BN, int WM, int WN>
 int launch_wgrad_tile(const vae_wgrad_args& a, bool vec, hipStream_t st) {
   const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), (unsigned)(a.g.taps * a.nsplit), (unsigned)a.batch), block(64 * WM * WN);
   auto go = [&](auto vec_c) {
+    int rc = 0;  // of the LDS reservation
     auto launch = [&](auto xf) {
-      if constexpr (BF) hipLaunchKernelGGL((wgrad_bf16_kernel<BM, BN, WM, WN, decltype(xf)::value>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, decltype(vec_c)::value, decltype(xf)::value>), grid, block, 0, st, a);
+      constexpr bool VEC = decltype(vec_c)::value;
+      constexpr int XF = decltype(xf)::value;
+      if constexpr (BF) {
+        hipLaunchKernelGGL((wgrad_bf16_kernel<BM, BN, WM, WN, XF>), grid, block, 0, st, a);
+      } else if constexpr (F32For<VEC, WM * WN>::LDS_DYNAMIC) {
+        constexpr int LDS = wgrad_lds_elems<F32For<VEC, WM * WN>, BM, BN, XF>() * (int)sizeof(typename F32For<VEC, WM * WN>::elem);
+        if (rc == 0) rc = [&]() -> int { VAE_RESERVE_LDS((wgrad_kernel<BM, BN, WM, WN, VEC, XF>), LDS, "wgrad"); return 0; }();
+        if (rc == 0) hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, VEC, XF>), grid, block, LDS, st, a);
+      } else {
+        hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN, VEC, XF>), grid, block, 0, st, a);
+      }
     };
-    if (dispatch_xf(a.xf, launch)) return 0;
+    if (dispatch_xf(a.xf, launch)) return rc;
     vae_set_error("wgrad: bad xf %d", a.xf);
     return VAE_EINVAL;
   };
