@@ -28,7 +28,7 @@ KIND = "norm_edges/"
 
 # ---------------------------------------------------------------------------------------------------- host plans, restated
 GN_UN = 4                  # norm.hip: quads in flight per thread of gn_bwd_apply_rows_kernel
-EW_THREADS = 8192 * 256    # norm.hip ew_blocks: the capped grid of gn_apply / gn_apply_bf16
+EW_THREADS = 8192 * 256    # stream_common.h ew_blocks: the capped grid of gn_apply / gn_apply_bf16
 GN_GPW = 4                 # norm.hip: groups per workgroup of gn_bwd_final_kernel
 
 

@@ -1,13 +1,13 @@
 """Compiler resources and instruction-class counts of the kernels in a device assembly listing (hipcc ... --cuda-device-only -S):
 per kernel VGPRs, SGPRs, spills, scratch bytes, LDS bytes and the static number of MFMA, LDS-read, LDS-write, buffer-load,
-buffer-store, global-store and barrier instructions.  Used to set a changed kernel next to its parent (profiles/wgrad_stagger_measured.json).
+buffer-store, global-load, global-store, flat and barrier instructions.  Used to set a changed kernel next to its parent (profiles/wgrad_stagger_measured.json).
 usage: python tools/isa_counts.py FILE.s [name filter]   (prints one JSON object)"""
 import json
 import re
 import sys
 
 CLASSES = {"mfma": r"v_mfma_", "ds_read": r"ds_read_", "ds_write": r"ds_write", "buffer_load": r"buffer_load_",
-           "buffer_store": r"buffer_store_", "global_store": r"global_store_", "barrier": r"s_barrier\b", "valu": r"v_(?!mfma_)", "salu": r"s_(?!barrier|waitcnt|nop)",
+           "buffer_store": r"buffer_store_", "global_load": r"global_load_", "global_store": r"global_store_", "flat": r"flat_", "barrier": r"s_barrier\b", "valu": r"v_(?!mfma_)", "salu": r"s_(?!barrier|waitcnt|nop)",
            "waitcnt": r"s_waitcnt\b"}
 META = ("vgpr_count", "sgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
 

@@ -32,9 +32,20 @@ partials bit for bit; together they must launch all 16 instantiations (exit stat
 step (256^2, batch 16) and one bf16 step (256^2, batch 32) that one of these kernels serves (THIN_STEP, copied from the output of
 tools/launch_shapes.py --flags).
 
-usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16|thin]"""
+`--only stream`: the streaming kernels (csrc/norm.hip, track.hip, lens.hip, image_metrics.hip, elementwise.hip; what they share is
+csrc/stream_common.h).  Every launch goes through the package's loader with its library swapped per arm, so the small cases are the
+tests' own: the tables of tests/norm_refs.py and tests/streaming_refs.py through the launch helpers of tests/test_norm_edges_gpu.py,
+and the case lists of test_tracker_metrics_gpu.py, test_logit_lens_gpu.py, test_image_metrics_gpu.py and test_trainable_gpu.py.
+Every tensor a case hands to the library (operands, results, workspaces; the helpers poison them) is compared bit for bit, and
+together the cases must launch every instantiation of the five files (STREAM_NAMES, named from each call's own arguments; exit
+status 1 otherwise).  Timed (--launches 0 skips it), one call of a C entry point per case on workspaces allocated beforehand: the GroupNorm entry
+points at the step's four shapes, fp32 storage at batch 16 and bf16 storage at batch 32, over a ring of operands larger than the
+memory-side cache, the moments passes, and the optimizer kernels, vae_sqnorm and the dead-weight scans at the arena's size; each case carries its own margin (twice |parent2 / parent - 1|, at least one rounding unit of the recorded medians).
+
+usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16|thin|stream]"""
 import argparse
 import ctypes as C
+import functools
 import json
 import math
 import os
@@ -44,7 +55,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "vae-channel-dynamics_amd", "src"))
 import torch  # noqa: E402
 from vaehip import ops  # noqa: E402
-from vaehip.lib import IgemmArgs, WgradArgs, lib  # noqa: E402
+from vaehip.lib import SIGNATURES, IgemmArgs, WgradArgs, lib  # noqa: E402
 
 # kind, mode, B, H, W, Ci, Co, epilogue, timed      (H, W: the layer's forward input map)
 STEP = [("c3", m, 16, hw, hw, ci, co, e, True) for ci, co, hw in [(128, 128, 256), (256, 128, 256), (256, 256, 128), (512, 256, 128), (512, 512, 64), (512, 512, 32)]
@@ -387,15 +398,419 @@ class ThinCase:
         return launch, outs, (a,)
 
 
+# ---- the streaming family (`--only stream`): every launch goes through vaehip.lib.lib, whose library is swapped per arm, so the
+# cases are the tests' own helpers and tables.  ops._p records every tensor handed to the library: operands, results, workspaces.
+_TF = ("false", "true")
+
+
+def _w_moments(a):  # vae_moments_partial picks W = 4 from C, ld and the operand's alignment
+    return 4 if (a[7] % 4 == 0 and a[8] % 4 == 0 and (getattr(a[0], "value", 0) or 0) & (7 if a[1] else 15) == 0) else 1
+
+
+# entry point -> the kernel instantiations one call launches, from the call's own arguments
+STREAM_KERNELS = {
+    "vae_gn_stats_partial": lambda a: [f"gn_stats_partial_kernel<{_TF[a[1]]}>"], "vae_gn_stats_final": lambda a: ["gn_stats_final_kernel"],
+    "vae_gn_apply": lambda a: [f"gn_apply_kernel<{_TF[a[1]]}>"], "vae_gn_apply_bf16": lambda a: [f"gn_apply_bf16_kernel<{_TF[a[1]]}>"],
+    "vae_gn_track_partial": lambda a: [f"gn_track_partial_kernel<{_TF[a[1]]}>"], "vae_track_final": lambda a: ["track_final_kernel"],
+    "vae_gn_bwd_partial": lambda a: [f"gn_bwd_partial_kernel<{_TF[a[12]]},{_TF[a[13]]},{_TF[a[1]]}>"], "vae_gn_bwd_final": lambda a: ["gn_bwd_final_kernel"],
+    "vae_gn_bwd_apply": lambda a: [f"gn_bwd_apply_rows_kernel<{_TF[a[13]]},{_TF[a[14]]},{_TF[a[1]]}>"],
+    "vae_moments_partial": lambda a: [f"moments_partial_kernel<{_w_moments(a)},{_TF[a[1]]}>"],
+    "vae_moments_final": lambda a: ["moments_channel_kernel", "moments_total_kernel"],
+    "vae_lens_planes_partial": lambda a: ["lens_planes_partial_kernel"], "vae_lens_planes_final": lambda a: ["lens_planes_final_kernel"],
+    "vae_lens_project": lambda a: ["lens_project_kernel"],
+    "vae_image_metrics_partial": lambda a: ["image_metrics_partial_kernel"], "vae_image_metrics_final": lambda a: ["image_metrics_final_kernel"],
+    "vae_softmax_rows": lambda a: ["softmax_rows_kernel"], "vae_softmax_bwd_rows": lambda a: ["softmax_bwd_rows_kernel"],
+    "vae_sample_kl": lambda a: ["sample_kl_kernel"], "vae_sample_kl_bwd": lambda a: ["sample_kl_bwd_kernel"],
+    "vae_mse_partial": lambda a: ["mse_partial_kernel"], "vae_loss_final": lambda a: ["loss_final_kernel"], "vae_mse_bwd": lambda a: ["mse_bwd_kernel"],
+    "vae_nchw_to_nhwc": lambda a: ["nchw_to_nhwc_kernel"], "vae_nhwc_to_nchw": lambda a: ["nhwc_to_nchw_kernel"], "vae_sumpool2x2": lambda a: ["sumpool2x2_kernel"],
+    "vae_add": lambda a: ["add_kernel"], "vae_add_bf16": lambda a: ["add_bf16_kernel"], "vae_unpack_bf16": lambda a: ["unpack_bf16_kernel"],
+    "vae_pack_bf16": lambda a: ["pack_bf16_kernel"], "vae_upconv_phase_weights": lambda a: ["upconv_phase_weights_kernel"],
+    "vae_upconv_fold_wgrad": lambda a: ["upconv_fold_wgrad_kernel"], "vae_sqnorm": lambda a: ["sqnorm_partial_kernel", "sqnorm_final_kernel"],
+    "vae_adamw": lambda a: ["adamw_kernel<false>"], "vae_adamw_ema": lambda a: ["adamw_kernel<true>"],
+    "vae_sqnorm_ranges": lambda a: ["sqnorm_ranges_kernel", "sqnorm_final_kernel"],
+    "vae_adamw_ranges": lambda a: [f"adamw_ranges_kernel<{_TF[a[4] is not None]}>"],
+    "vae_dead_scan": lambda a: ["dead_scan_chunk_kernel<false>", "dead_scan_final_kernel"],
+    "vae_dead_scan_adaptive": lambda a: ["dead_scan_chunk_kernel<true>", "dead_scan_final_kernel"],
+}
+# every __global__ instantiation of norm.hip, track.hip, lens.hip, image_metrics.hip and elementwise.hip
+STREAM_NAMES = ({f"{k}<{_TF[x]}>" for k in ("gn_stats_partial_kernel", "gn_apply_kernel", "gn_apply_bf16_kernel", "gn_track_partial_kernel", "adamw_kernel",
+                                           "adamw_ranges_kernel", "dead_scan_chunk_kernel") for x in (0, 1)}
+                | {f"{k}<{_TF[s]},{_TF[g]},{_TF[x]}>" for k in ("gn_bwd_partial_kernel", "gn_bwd_apply_rows_kernel") for s in (0, 1) for g in (0, 1) for x in (0, 1)}
+                | {f"moments_partial_kernel<{w},{_TF[x]}>" for w in (1, 4) for x in (0, 1)}
+                | {k + "_kernel" for k in ("gn_stats_final", "track_final", "gn_bwd_final", "moments_channel", "moments_total", "lens_planes_partial",
+                                           "lens_planes_final", "lens_project", "image_metrics_partial", "image_metrics_final", "softmax_rows", "softmax_bwd_rows",
+                                           "sample_kl", "sample_kl_bwd", "mse_partial", "loss_final", "mse_bwd", "nchw_to_nhwc", "nhwc_to_nchw", "sumpool2x2", "add",
+                                           "add_bf16", "unpack_bf16", "pack_bf16", "upconv_phase_weights", "upconv_fold_wgrad", "sqnorm_partial", "sqnorm_final",
+                                           "sqnorm_ranges", "dead_scan_final")})
+GN_STEP = [(16, 256, 256, 128), (16, 128, 128, 256), (16, 64, 64, 512), (16, 32, 32, 512)]  # (B, H, W, C): the GroupNorms of the 256^2 step
+ARENA_N = 83_653_863   # parameters of the model: the optimizer kernels' size
+RING_BYTES = 320 << 20  # operands rotate over more than the 256 MB memory-side cache
+
+
+def stream_small(dev):
+    """-> [(id, fn)]: fn() runs one case's launches through the package's loader; the tables of tests/norm_refs.py and
+    tests/streaming_refs.py and the case lists of four GPU test files, with the helpers of the tests that own them"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import lens_refs as LR
+    import norm_refs as nr
+    import streaming_refs as sr
+    import test_image_metrics_gpu as IM
+    import test_norm_edges_gpu as NE
+    import test_tracker_metrics_gpu as TM
+    import test_trainable_gpu as TR
+    from vaehip.trainable import RangeTable
+    cases = []
+    build_case = functools.lru_cache(maxsize=1)(nr.build_case)  # (one build serves the arms of a case)
+
+    def case(cid):
+        return lambda fn: cases.append((cid, fn))
+
+    for name in nr.SHAPES:
+        for values in ("plain", "large_mean_30"):
+            for x16 in (False, True):
+                @case(f"gn/{name}/{values}/{'bf16' if x16 else 'f32'}")
+                def _(name=name, values=values, x16=x16):
+                    c = build_case(name, values)
+                    st16 = lambda t: t.to(dev).bfloat16() if x16 else t.to(dev)  # noqa: E731
+                    x, gamma, beta = st16(c.x), c.gamma.to(dev), c.beta.to(dev)
+                    st = NE.k_stats(x, gamma, beta)
+                    for xf in (NE.XF_AFFINE, NE.XF_AFFINE_SILU):
+                        NE.k_apply(x, st, xf)
+                        if x.shape[-1] % 8 == 0:
+                            NE.k_apply16(x, st, xf)
+                    NE.k_track(x, st)
+                    for silu in (False, True):
+                        for g16 in (False, True):
+                            g = c.g.to(dev).bfloat16() if g16 else c.g.to(dev)
+                            NE.k_bwd(x, g, st, gamma, beta, silu, st16(c.add) if silu else None, want32=not g16, want16=g16 or x16)
+    for rows in nr.TRACK_ROWS:
+        for Cc in nr.TRACK_C:
+            @case(f"track_final/{rows}x{Cc}")
+            def _(rows=rows, Cc=Cc):
+                NE.k_track_final(nr.track_ws(rows, Cc).to(dev), rows, torch.full((Cc,), float("nan"), device=dev))
+
+    @case("dead_scan")
+    def _():
+        flat, segs, _ = nr.dead_layout(0.0)
+        flat = flat.to(dev)
+        NE.k_dead_scan(flat, segs, nr.DEAD_THR)
+        for fixed in (0, 1):
+            NE.k_dead_scan(flat, segs, nr.DEAD_THR, [0.01 * (1 + s % 5) for s in range(len(segs))], fixed)
+    for cols in sr.SOFTMAX_COLS:
+        @case(f"softmax/{cols}")
+        def _(cols=cols):
+            S, dP = (t.to(dev) for t in sr.softmax_inputs(cols))
+            ops.softmax_bwd_rows_(ops.softmax_rows_(S), dP)
+    for shape in sr.SAMPLE_SHAPES:
+        @case(f"sample_kl/{shape}")
+        def _(shape=shape):
+            mom, eps, dz, _ = (t.to(dev) for t in sr.sample_inputs(*shape, True))
+            ops.sample_kl(mom, eps)
+            ops.sample_kl(mom, None)
+            ops.sample_kl_bwd(mom, eps, dz, 1e-3)
+    for n in sr.MSE_SIZES:
+        @case(f"mse/{n}")
+        def _(n=n):
+            recon, target, klp = (t.to(dev) for t in sr.mse_inputs(n))
+            ops.mse_kl_loss(recon, target, klp, 1e-3)
+            ops.mse_bwd(recon, target)
+            ops.add(recon, target)
+    for n in (sr.ADAM_N, sr.ADAM_GRID_N):
+        @case(f"adamw/{n}")
+        def _(n=n):
+            for ema in (False, True):
+                p, g = sr.adam_params(n).to(dev), sr.adam_grad(n, 3.0, 1).to(dev)
+                m, v, e, sq = torch.zeros_like(p), torch.zeros_like(p), p.clone(), torch.full((1,), float("nan"), device=dev)
+                ops.sqnorm(g, sq, torch.full((2048,), float("nan"), device=dev))
+                hp = (sq, 1.0, 1e-3, *sr.ADAM["betas"], sr.ADAM["eps"], sr.ADAM["wd"])
+                for step in (1, 2):
+                    if ema:
+                        ops.adamw_ema(p, g, m, v, e, *hp, step, 0.9 * (step - 1))
+                    else:
+                        ops.adamw(p, g, m, v, *hp, step)
+    for n in sr.BF16_LENGTHS:
+        @case(f"bf16_pack/{n}")
+        def _(n=n):
+            for rot in sr.bf16_rotations(n):
+                src = sr.bf16_table(n, rot).to(dev)
+                h = ops.pack_bf16(src, torch.full((n,), float("nan"), device=dev, dtype=torch.bfloat16))
+                lib.call("vae_unpack_bf16", ops._p(h), n, ops._p(torch.full((n,), float("nan"), device=dev)), ops._stream())
+
+    @case("bf16_add")
+    def _():
+        a, b = (t.to(dev) for t in sr.bf16_add_pairs())
+        ops.add(a, b)
+
+    @case("layout")
+    def _():
+        g = torch.Generator().manual_seed(3)
+        x = torch.randn((2, 3, 9, 13), generator=g).to(dev)
+        ops.nhwc_to_nchw(ops.nchw_to_nhwc(x, 4))
+        src, dst = torch.randn((2, 10, 14, 8), generator=g).to(dev), torch.full((2, 5, 7, 8), float("nan"), device=dev)
+        lib.call("vae_sumpool2x2", ops._p(src), 2, 5, 7, 8, ops._p(dst), ops._stream())
+        w, we = torch.randn((5, 3, 3, 7), generator=g).to(dev), torch.full((4, 5, 3, 3, 7), float("nan"), device=dev)
+        lib.call("vae_upconv_phase_weights", ops._p(w), 5, 7, ops._p(we), ops._stream())
+        dbe, dw, db = torch.randn((4, 5), generator=g).to(dev), torch.full((5, 3, 3, 7), float("nan"), device=dev), torch.full((5,), float("nan"), device=dev)
+        lib.call("vae_upconv_fold_wgrad", ops._p(we), ops._p(dbe), 5, 7, ops._p(dw), ops._p(db), ops._stream())
+    for Cc, dt, xf, B, H, W in TM._cases():
+        @case(f"moments/C{Cc}/{str(dt)[6:]}/xf{xf}/{B}x{H}x{W}")
+        def _(Cc=Cc, dt=dt, xf=xf, B=B, H=H, W=W):
+            g = torch.Generator(device="cpu").manual_seed(Cc * 131 + xf * 7 + B)
+            x = (torch.randn((B, H, W, Cc), generator=g) * 1.3 + 0.4).to(dev).to(dt)
+            ops.moments(x, TM._stats(B, Cc, dev, Cc + xf) if xf else None, xf)
+    for lc in LR.plane_cases():
+        @case(f"lens/{LR.case_id(lc)}")
+        def _(lc=lc):
+            H, W, cc, B, S, bf16 = lc
+            buf, Cn = LR.make_input(H, W, cc, B, bf16)
+            x, wd = buf.to(dev)[..., :Cn], [t.to(dev) for t in LR.decoder_weights(1)]
+            for ch in LR.channel_lists(Cn):
+                idx = torch.tensor(ch, dtype=torch.int32, device=dev)
+                ops.lens_planes(x, S, idx, ch)
+                ops.lens_project(x, S, idx, *wd, False, ch)
+    for lc in LR.full_map_cases():
+        @case(f"lens_full/{LR.case_id(lc)}")
+        def _(lc=lc):
+            Cn, H, W, B, S, bf16 = lc
+            x = LR.make_input(H, W, str(Cn), B, bf16)[0].to(dev)
+            ops.lens_project(x, S, torch.arange(Cn, dtype=torch.int32, device=dev), *[t.to(dev) for t in LR.decoder_weights(Cn)], True, list(range(Cn)))
+    for shape in IM.SHAPES:
+        for variant in ("noisy", "flat"):
+            @case(f"image_metrics/{'x'.join(map(str, shape))}/{variant}")
+            def _(shape=shape, variant=variant):
+                p, t = IM._inputs(shape, variant)
+                ops.image_metrics(p.to(dev), t.to(dev))
+    chunk = lib.query("vae_dead_scan_chunk")
+    for rc, (ranges, n) in TR._range_cases(chunk).items():
+        @case(f"ranges/{rc}")
+        def _(rc=rc, ranges=ranges, n=n):
+            gen = torch.Generator().manual_seed(len(rc) * 131 + n)
+            host = dict(p=sr.adam_params(n, seed=n), g=torch.randn(n, generator=gen) * 3.0, m=torch.randn(n, generator=gen) * 0.1,
+                        v=torch.rand(n, generator=gen) * 1e-2, e=sr.adam_params(n, seed=n + 1))
+            tab, out = RangeTable(ranges, dev, n), torch.full((1,), float("nan"), device=dev)
+            tab.ws.fill_(float("nan"))
+            g = host["g"].to(dev)
+            ops.sqnorm_ranges(g, tab, out)
+            for ema, max_norm, decay in ((False, 1.0, 0.0), (True, 1.0, 0.9), (True, 0.0, 0.0)):
+                t = {k: host[k].to(dev) for k in ("p", "m", "v") + (("e",) if ema else ())}
+                ops.adamw_ranges(t["p"], g, t["m"], t["v"], t.get("e"), tab, out, max_norm, 1e-3, *sr.ADAM["betas"], sr.ADAM["eps"], sr.ADAM["wd"], 2, decay)
+    return cases
+
+
+def stream_timed(dev):
+    """-> [(id, setup)]: setup() -> (ring length, fn(i)); fn(i) is ONE call of a C entry point (lib.call) on operand set i of a
+    ring of more than RING_BYTES, every workspace and result allocated beforehand -- nothing but the launch lies between the
+    events.  The GroupNorm entry points at GN_STEP in fp32 storage and, at batch 32, in bf16 storage (the final passes, whose
+    operands are workspaces of a few hundred KB, have no ring); vae_moments_partial / vae_moments_final at the widest shape; the
+    optimizer kernels, vae_sqnorm (also at 2^20 elements, where its final pass is a third of the time) and the dead-weight scans
+    at ARENA_N."""
+    G, cases, st = 32, [], ops._stream
+    p = ops._p
+    for B16, H, W, Cc in GN_STEP:
+        for x16 in (False, True):
+            B, dt = (2 * B16, torch.bfloat16) if x16 else (B16, torch.float32)
+            tag = f"{B}x{H}x{W}x{Cc}/{'bf16' if x16 else 'f32'}"
+            HW = H * W
+            ring = max(2, -(-RING_BYTES // (B * HW * Cc * (2 if x16 else 4))))
+
+            def setup(entry, silu=False, g16=False, ring=ring, B=B, HW=HW, H=H, W=W, Cc=Cc, dt=dt, x16=x16):
+                g = torch.Generator(device=dev).manual_seed(Cc + H)
+                f32 = lambda *s: torch.empty(s, device=dev)  # noqa: E731
+                xs = [(torch.randn((B, H, W, Cc), device=dev, generator=g) * 1.7 + 0.3).to(dt) for _ in range(ring)]
+                gamma, beta = 1 + 0.3 * torch.randn((Cc,), device=dev, generator=g), 0.2 * torch.randn((Cc,), device=dev, generator=g)
+                s = ops.gn_stats(xs[0], gamma, beta)  # (statistics of one set serve all: timing only)
+                nch, xb = ops._gn_nchunk(B, HW, Cc), int(x16)
+                if entry == "vae_gn_stats_partial":
+                    ws = f32(B, nch, G, 2)
+                    return ring, lambda i: lib.call(entry, p(xs[i]), xb, B, HW, Cc, G, nch, p(ws), st())
+                if entry == "vae_gn_stats_final":
+                    ws, o = f32(B, nch, G, 2), [f32(B, G), f32(B, G), f32(B, Cc), f32(B, Cc)]
+                    lib.call("vae_gn_stats_partial", p(xs[0]), xb, B, HW, Cc, G, nch, p(ws), st())
+                    return 1, lambda i: lib.call(entry, p(ws), B, HW, Cc, G, nch, p(gamma), p(beta), 1e-6, p(o[0]), p(o[1]), p(o[2]), p(o[3]), st())
+                if entry in ("vae_gn_apply", "vae_gn_apply_bf16"):
+                    y = torch.empty((B, H, W, Cc), device=dev, dtype=torch.bfloat16 if entry.endswith("bf16") else torch.float32)
+                    return ring, lambda i: lib.call(entry, p(xs[i]), xb, p(s.scale), p(s.shift), B, HW, Cc, ops.XF_AFFINE_SILU, p(y), st())
+                if entry == "vae_gn_track_partial":
+                    ws = f32(B * nch, Cc)
+                    return ring, lambda i: lib.call(entry, p(xs[i]), xb, p(s.scale), p(s.shift), B, HW, Cc, nch, p(ws), st())
+                if entry == "vae_moments_partial":
+                    mch = min(nch, 1024 // B)
+                    ws = f32(Cc, B * mch, 4)
+                    return ring, lambda i: lib.call(entry, p(xs[i]), xb, p(s.scale), p(s.shift), ops.XF_AFFINE_SILU, B, HW, Cc, Cc, mch, p(ws), st())
+                if entry == "vae_moments_final":
+                    mch = min(nch, 1024 // B)
+                    ws, chan, out = f32(Cc, B * mch, 4), torch.empty((Cc, 2), device=dev, dtype=torch.float64), f32(Cc + 2)
+                    lib.call("vae_moments_partial", p(xs[0]), xb, p(s.scale), p(s.shift), ops.XF_AFFINE_SILU, B, HW, Cc, Cc, mch, p(ws), st())
+                    return 1, lambda i: lib.call(entry, p(ws), B, HW, Cc, mch, p(chan), p(out), st())
+                gs = [torch.randn((B, H, W, Cc), device=dev, generator=g).to(torch.bfloat16 if g16 else torch.float32) for _ in range(2)]
+                ws, coef, dg, db = f32(B, nch, Cc, 2), f32(B, G, 2), f32(Cc), f32(Cc)
+                lib.call("vae_gn_bwd_partial", p(xs[0]), xb, p(gs[0]), p(s.mean), p(s.rstd), p(gamma), p(beta), B, HW, Cc, G, nch, int(silu), int(g16), p(ws), st())
+                lib.call("vae_gn_bwd_final", p(ws), p(s.rstd), p(gamma), B, HW, Cc, G, nch, p(dg), p(db), p(coef), st())
+                if entry == "vae_gn_bwd_partial":
+                    return ring, lambda i: lib.call(entry, p(xs[i]), xb, p(gs[i % 2]), p(s.mean), p(s.rstd), p(gamma), p(beta), B, HW, Cc, G, nch, int(silu),
+                                                    int(g16), p(ws), st())
+                if entry == "vae_gn_bwd_final":
+                    return 1, lambda i: lib.call(entry, p(ws), p(s.rstd), p(gamma), B, HW, Cc, G, nch, p(dg), p(db), p(coef), st())
+                dx = torch.empty((B, H, W, Cc), device=dev, dtype=torch.bfloat16 if g16 else torch.float32)
+                return ring, lambda i: lib.call("vae_gn_bwd_apply", p(xs[i]), xb, p(gs[i % 2]), p(s.mean), p(s.rstd), p(gamma), p(beta), p(coef), None, B, HW,
+                                                Cc, G, int(silu), int(g16), None if g16 else p(dx), p(dx) if g16 else None, st())
+            for entry in ("vae_gn_stats_partial", "vae_gn_stats_final", "vae_gn_apply", "vae_gn_apply_bf16", "vae_gn_track_partial", "vae_gn_bwd_final"):
+                cases.append((f"{entry}/{tag}", functools.partial(setup, entry)))
+            if (H, Cc) == (256, 128):
+                cases += [(f"{entry}/{tag}", functools.partial(setup, entry)) for entry in ("vae_moments_partial", "vae_moments_final")]
+            for silu in (False, True):
+                for g16 in (False, True):
+                    if g16 != x16 and (H, Cc) != (64, 512):
+                        continue  # the step stores g like x; the mixed storages are timed at one shape
+                    for entry in ("vae_gn_bwd_partial", "vae_gn_bwd_apply"):
+                        cases.append((f"{entry}/silu{int(silu)}/g{'bf16' if g16 else 'f32'}/{tag}", functools.partial(setup, entry, silu, g16)))
+
+    def optimizer(ema):
+        def setup():
+            t = [torch.randn((ARENA_N,), device=dev) * (0.05 if k != 3 else 0.0) for k in range(5)]
+            t[3].add_(1e-4)
+            sq = torch.zeros((1,), device=dev)
+            hp = (sq, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 2)
+            if ema:
+                return 1, lambda i: ops.adamw_ema(t[0], t[1], t[2], t[3], t[4], *hp, 0.999)
+            return 1, lambda i: ops.adamw(t[0], t[1], t[2], t[3], *hp)
+        return setup
+    cases += [("vae_adamw/arena", optimizer(False)), ("vae_adamw_ema/arena", optimizer(True))]
+
+    def sqnorm_setup(n):
+        def setup():
+            g, sq, ws = torch.randn((n,), device=dev), torch.zeros((1,), device=dev), torch.empty((2048,), device=dev)
+            return 1, lambda i: lib.call("vae_sqnorm", p(g), n, p(ws), 2048, p(sq), st())
+        return setup
+    cases += [("vae_sqnorm/arena", sqnorm_setup(ARENA_N)), ("vae_sqnorm/2^20", sqnorm_setup(1 << 20))]
+
+    def add16_setup():  # the residual add of the bf16 step at [32, 128, 128, 256]
+        n = 32 * 128 * 128 * 256
+        a, b, o = (torch.randn((3, n), device=dev).bfloat16() for _ in range(3))
+        return 3, lambda i: lib.call("vae_add_bf16", p(a[i]), p(b[i]), n, p(o[i]), st())
+    cases.append(("vae_add_bf16/32x128x128x256", add16_setup))
+
+    def dead_setup(adaptive):
+        def setup():
+            chunk = lib.query("vae_dead_scan_chunk")
+            nchunk = -(-ARENA_N // chunk)
+            w = torch.randn((ARENA_N,), device=dev) * 0.05
+            seg, chunk0 = torch.tensor([0, ARENA_N], dtype=torch.int64, device=dev), torch.tensor([0, nchunk], dtype=torch.int32, device=dev)
+            pcnt, psum = torch.zeros((nchunk,), dtype=torch.int64, device=dev), torch.zeros((nchunk,), dtype=torch.float64, device=dev)
+            cnt, asum, at = torch.zeros((1,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.float64, device=dev), torch.full((1,), 0.01, device=dev)
+            if adaptive:
+                return 1, lambda i: lib.call("vae_dead_scan_adaptive", p(w), p(seg), p(chunk0), 1, nchunk, 1e-5, 1, p(at), p(pcnt), p(cnt), st())
+            return 1, lambda i: lib.call("vae_dead_scan", p(w), p(seg), p(chunk0), 1, nchunk, 1e-5, p(pcnt), p(psum), p(cnt), p(asum), st())
+        return setup
+    cases += [("vae_dead_scan/arena", dead_setup(False)), ("vae_dead_scan_adaptive/arena", dead_setup(True))]
+    return cases
+
+
+def _stream_run(fn, dll, record):
+    """one run of fn on library dll -> the tensors it handed to the library, in order; record: set of launched instantiations"""
+    seen, order, p0, call0 = set(), [], ops._p, lib.call
+
+    def p(t):
+        if t is not None and id(t) not in seen:
+            seen.add(id(t))
+            order.append(t)
+        return p0(t)
+
+    def call(name, *a):
+        if name in STREAM_KERNELS:
+            assert len(a) == len(SIGNATURES[name]), (name, len(a))  # (the argument positions STREAM_KERNELS reads are those of this signature)
+            record.update(STREAM_KERNELS[name](a))
+        return call0(name, *a)
+    lib._dll, ops._p, lib.call = dll, p, call
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        ops._p, lib.call = p0, call0
+        del lib.call  # (the instance attribute: the class's method is back)
+    return order
+
+
+def stream_main(arg, names, paths):
+    dev = torch.device("cuda:0")
+    lib.load()
+    home, dlls = lib._dll, []
+    for s in paths:
+        d = C.CDLL(os.path.abspath(s))
+        d.vae_last_error.restype = C.c_char_p
+        for fn, argt in SIGNATURES.items():
+            getattr(d, fn).restype, getattr(d, fn).argtypes = (C.c_int64 if fn == "vae_wino_weight_floats" else C.c_int), argt
+        dlls.append(d)
+    rows, launched, all_equal = [], set(), True
+    try:
+        for cid, fn in stream_small(dev):
+            first, eq, here = None, {}, set()
+            for i, d in enumerate(dlls):
+                got = _stream_run(fn, d, here)
+                if i == 0:
+                    first = got
+                else:
+                    eq[names[i]] = len(got) == len(first) and all(a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+                                                                    for a, b in zip(got, first))
+            launched |= here
+            all_equal = all_equal and all(eq.values())
+            rows.append({"case": cid, "kernels": sorted(here), "tensors_compared": len(first), "bitwise_equal_to_new": eq, "bitwise": all(eq.values())})
+            print(json.dumps(rows[-1]), flush=True)
+            del first, got
+            torch.cuda.empty_cache()
+        timed = []
+        for cid, setup in ([] if arg.launches <= 0 else stream_timed(dev)):
+            lib._dll = home
+            ring, fn = setup()
+            here = set()
+            for d in dlls:  # warm-up, and the instantiations the case launches
+                _stream_run(lambda: [fn(i) for i in range(min(ring, 2))], d, here)
+            ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(arg.launches)] for _ in dlls]
+            for k in range(arg.launches):
+                for i in ((k + j) % len(dlls) for j in range(len(dlls))):  # (every arm takes every place in the round equally often)
+                    lib._dll = dlls[i]
+                    ev[i][k][0].record()
+                    fn((k * len(dlls) + i) % ring)
+                    ev[i][k][1].record()
+            torch.cuda.synchronize()
+            row = {"case": cid, "kernels": sorted(here), "ring": ring}
+            for i, nm in enumerate(names):
+                ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev[i])
+                row[nm] = {"median_ms": round(statistics.median(ms), 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+            for nm in names:
+                if nm != "parent":
+                    row[f"{nm}_over_parent"] = round(row[nm]["median_ms"] / row["parent"]["median_ms"], 4)
+            if "parent2" in names:  # the case's own floor, never below one rounding unit of the recorded medians
+                row["margin"] = round(max(2 * abs(row["parent2_over_parent"] - 1), 1e-4 / row["parent"]["median_ms"]), 4)
+                row["within_margin"] = row["new"]["median_ms"] / row["parent"]["median_ms"] - 1 <= row["margin"]
+            print(json.dumps(row), flush=True)
+            timed.append(row)
+            del fn, setup
+            torch.cuda.empty_cache()
+    finally:
+        lib._dll = home
+    missing = sorted(STREAM_NAMES - launched) + sorted("unknown: " + k for k in launched - STREAM_NAMES)
+    res = {"libs": dict(zip(names, [os.path.basename(s) for s in paths])), "launches_per_arm": arg.launches, "all_bitwise_equal": all_equal, "rows": rows,
+           "timed": timed, "instantiations_not_launched": missing, "all_within_margin": all(r.get("within_margin", True) for r in timed)}
+    print("instantiations not launched:", missing)
+    print("all outputs and workspaces bitwise equal:", all_equal)
+    if arg.out:
+        with open(arg.out, "w") as f:
+            json.dump(res, f, indent=1)
+    return 1 if (not all_equal or missing) else 0 if res["all_within_margin"] else 2
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs="+", help="NEW.so PARENT.so [name=OTHER.so ...]")
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16", "thin"])
+    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16", "thin", "stream"])
     arg = ap.parse_args()
     assert len(arg.libs) >= 2, "two libraries: this build and the parent's"
     names = ["new", "parent"] + [s.split("=", 1)[0] for s in arg.libs[2:]]
+    if arg.only == "stream":
+        return stream_main(arg, names, [s.split("=", 1)[-1] for s in arg.libs])
     dlls = [_open(s.split("=", 1)[-1]) for s in arg.libs]
     dev = torch.device("cuda:0")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

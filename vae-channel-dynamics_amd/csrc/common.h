@@ -81,11 +81,24 @@ __device__ __forceinline__ bool src_pixel(const SrcMap& m, int y, int x, int kh,
   return ((unsigned)ty < m.limy) & ((unsigned)tx < m.limx) & (((ty | tx) & m.pm) == 0) & ((unsigned)sy < (unsigned)m.Hs) & ((unsigned)sx < (unsigned)m.Ws);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// reduction over the 64 lanes of a wave: shuffle offsets 32 -> 1, every lane ends with the result
+struct OpAdd {
+  template <class T>
+  __device__ __forceinline__ static T f(T a, T b) { return a + b; }
+};
+struct OpMin {
+  __device__ __forceinline__ static float f(float a, float b) { return fminf(a, b); }
+};
+struct OpMax {
+  __device__ __forceinline__ static float f(float a, float b) { return fmaxf(a, b); }
+};
+template <class Op, class T>
+__device__ __forceinline__ T wave_reduce(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v = Op::f(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ float wave_sum(float v) { return wave_reduce<OpAdd>(v); }
 
 // ---------------------------------------------------------------------------------------
 // GroupNorm statistics as (mean, M2 = sum of squared deviations) per chunk, merged with Chan's formula.  Sums of x and x^2

@@ -1,39 +1,10 @@
 // Streaming kernels of the train step: attention softmax, posterior sample + KL, MSE,
 // layout conversion, nearest-up2x dgrad pooling, grad-norm, fused clip+AdamW, dead-weight scan.
 // All reductions are two-stage (per-workgroup partial, fixed-order final) => bitwise reproducible.
-#include "common.h"
+#include "stream_common.h"
 #include <math.h>
 
 namespace {
-
-__device__ __forceinline__ float block_sum(float v, float* red /*[4]*/) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-inline int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
 
 // ---------------- softmax ----------------
 __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S, int cols) {
@@ -41,14 +12,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S
   float* row = S + (int64_t)blockIdx.x * cols;
   float mx = -INFINITY;
   for (int j = threadIdx.x; j < cols; j += 256) mx = fmaxf(mx, row[j]);
-  mx = block_max(mx, red);
+  mx = block_reduce<OpMax>(mx, red);
   float s = 0.f;
   for (int j = threadIdx.x; j < cols; j += 256) {
     float e = __expf(row[j] - mx);
     row[j] = e;
     s += e;
   }
-  s = block_sum(s, red);
+  s = block_reduce<OpAdd>(s, red);
   const float inv = 1.0f / s;
   for (int j = threadIdx.x; j < cols; j += 256) row[j] *= inv;
 }
@@ -59,7 +30,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float* __re
   float* d = dP + (int64_t)blockIdx.x * cols;
   float s = 0.f;
   for (int j = threadIdx.x; j < cols; j += 256) s += p[j] * d[j];
-  s = block_sum(s, red);
+  s = block_reduce<OpAdd>(s, red);
   for (int j = threadIdx.x; j < cols; j += 256) d[j] = p[j] * (d[j] - s);
 }
 
@@ -81,7 +52,7 @@ __global__ __launch_bounds__(256) void sample_kl_kernel(const float* __restrict_
     z[((int64_t)b * hw + p) * L + l] = mu + sd * e;
     kl = 0.5f * (mu * mu + var - 1.0f - lv);
   }
-  kl = block_sum(kl, red);
+  kl = block_reduce<OpAdd>(kl, red);
   if (threadIdx.x == 0) kl_partial[b * nblk + blockIdx.x] = kl;
 }
 
@@ -111,7 +82,7 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restric
     const float d = a[i] - b[i];
     s += d * d;
   }
-  s = block_sum(s, red);
+  s = block_reduce<OpAdd>(s, red);
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 
@@ -121,10 +92,10 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
   __shared__ double red[4];
   double s = 0.0;
   for (int i = threadIdx.x; i < mse_nblk; i += 256) s += (double)mse_ws[i];
-  s = block_sum_d(s, red);
+  s = block_reduce<OpAdd>(s, red);
   double k = 0.0;
   for (int i = threadIdx.x; i < B * kl_nblk; i += 256) k += (double)kl_partial[i];
-  k = block_sum_d(k, red);
+  k = block_reduce<OpAdd>(k, red);
   if (threadIdx.x == 0) {
     const float mse = (float)(s / mse_n);
     const float kl = (float)(k / (double)B);
@@ -181,43 +152,27 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
 }
 
 // bf16 tensors: o = bf16(float(a) + float(b)), 4 elements per thread per trip
-__device__ __forceinline__ f32x4 unpack4_bf16(uint2 r) {
-  f32x4 v;
-  v[0] = __builtin_bit_cast(float, r.x << 16);
-  v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-  v[2] = __builtin_bit_cast(float, r.y << 16);
-  v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-  return v;
-}
 __global__ __launch_bounds__(256) void add_bf16_kernel(const unsigned short* __restrict__ a, const unsigned short* __restrict__ b, int64_t n4,
                                                        unsigned short* __restrict__ o) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const f32x4 v = unpack4_bf16(*reinterpret_cast<const uint2*>(a + i * 4)) + unpack4_bf16(*reinterpret_cast<const uint2*>(b + i * 4));
-    bf16x4_t h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
-    *reinterpret_cast<uint2*>(o + i * 4) = __builtin_bit_cast(uint2, h);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
+    store4<true>(o, i, load4<true>(a, i) + load4<true>(b, i));
 }
 __global__ __launch_bounds__(256) void unpack_bf16_kernel(const unsigned short* __restrict__ src, int64_t n, float* __restrict__ dst) {
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
-    *reinterpret_cast<f32x4*>(dst + i * 4) = unpack4_bf16(*reinterpret_cast<const uint2*>(src + i * 4));
+    store4<false>(dst, i, load4<true>(src, i));
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
-    dst[i] = __builtin_bit_cast(float, (unsigned)src[i] << 16);
+    dst[i] = load1(src, i, true);
   }
 }
 
 // fp32 -> bf16 image (round to nearest even), 8 elements per thread per trip: 32 B in, 16 B out
 __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ src, int64_t n, unsigned short* __restrict__ dst) {
-  typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
   const int64_t n8 = n >> 3;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(src + i * 8);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(src + i * 8 + 4);
-    bf16x8_t h;
+    const f32x4 a = load4<false>(src, i * 2), b = load4<false>(src, i * 2 + 1);
+    bf16x8 h;  // (one vector of 8, not two pack4: with those the kernel takes 4 VGPRs more)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       h[e] = (__bf16)a[e];
@@ -291,26 +246,26 @@ __global__ __launch_bounds__(256) void upconv_fold_wgrad_kernel(const float* __r
 }
 
 // ---------------- grad norm + AdamW ----------------
+// the squared norm of one quad: the only copy of its association, shared by sqnorm_partial_kernel and sqnorm_ranges_kernel
+__device__ __forceinline__ float sqnorm_quad(f32x4 v) { return (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]); }
+
 __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ ws) {
   __shared__ float red[4];
   float s = 0.f;
   const int64_t n4 = n >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    f32x4 v = *reinterpret_cast<const f32x4*>(g + i * 4);
-    s += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) s += sqnorm_quad(load4<false>(g, i));
   if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {
     float v = g[(n4 << 2) + threadIdx.x];
     s += v * v;
   }
-  s = block_sum(s, red);
+  s = block_reduce<OpAdd>(s, red);
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void sqnorm_final_kernel(const float* __restrict__ ws, int nblk, float* __restrict__ out) {
   __shared__ double red[4];
   double s = 0.0;
   for (int i = threadIdx.x; i < nblk; i += 256) s += (double)ws[i];
-  s = block_sum_d(s, red);
+  s = block_reduce<OpAdd>(s, red);
   if (threadIdx.x == 0) out[0] = (float)s;
 }
 
@@ -350,6 +305,29 @@ __device__ __forceinline__ void adam_scalar(float* __restrict__ p, const float* 
   v[i] = v2;
   if (EMA) e[i] = ema_next(e[i], pp, x);
 }
+// the four elements from offset o (16-byte aligned in every buffer)
+template <bool EMA>
+__device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, float* __restrict__ e, int64_t o, float clip, const AdamArgs& a,
+                                          const EmaArgs& x) {
+  f32x4 pv = *reinterpret_cast<f32x4*>(p + o);
+  f32x4 gv = *reinterpret_cast<const f32x4*>(g + o);
+  f32x4 mv = *reinterpret_cast<f32x4*>(m + o);
+  f32x4 vv = *reinterpret_cast<f32x4*>(v + o);
+  f32x4 ev;
+  if (EMA) ev = *reinterpret_cast<f32x4*>(e + o);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float pp = pv[k], mm = mv[k], v2 = vv[k];
+    adam_elem(pp, gv[k], mm, v2, clip, a);
+    pv[k] = pp; mv[k] = mm; vv[k] = v2;
+    if (EMA) ev[k] = ema_next(ev[k], pp, x);
+  }
+  *reinterpret_cast<f32x4*>(p + o) = pv;
+  *reinterpret_cast<f32x4*>(m + o) = mv;
+  *reinterpret_cast<f32x4*>(v + o) = vv;
+  if (EMA) *reinterpret_cast<f32x4*>(e + o) = ev;
+}
 
 template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -358,25 +336,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   float* __restrict__ e = x.e;
   const float clip = adam_clip(a, sqnorm);
   const int64_t n4 = n >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-    f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-    f32x4 ev;
-    if (EMA) ev = *reinterpret_cast<f32x4*>(e + i * 4);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pp = pv[k], mm = mv[k], v2 = vv[k];
-      adam_elem(pp, gv[k], mm, v2, clip, a);
-      pv[k] = pp; mv[k] = mm; vv[k] = v2;
-      if (EMA) ev[k] = ema_next(ev[k], pp, x);
-    }
-    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-    if (EMA) *reinterpret_cast<f32x4*>(e + i * 4) = ev;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
+    adam_quad<EMA>(p, g, m, v, e, i * 4, clip, a, x);
   if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
     adam_scalar<EMA>(p, g, m, v, e, i, clip, a, x);
@@ -407,11 +368,13 @@ __device__ __forceinline__ int dead_find_segment(const int32_t* __restrict__ seg
 // float4 body; a chunk that does not start on 16 bytes takes the scalar loop for all of it.
 struct RangeChunk {
   int64_t b, e;  // this workgroup's elements [b, e)
+  int seg;       // of this range
 };
 __device__ __forceinline__ RangeChunk range_chunk(const int64_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk0, int nseg) {
   const int chunk = blockIdx.x;
   const int s = dead_find_segment(seg_chunk0, nseg, chunk);
   RangeChunk r;
+  r.seg = s;
   r.b = seg_off[2 * s] + (int64_t)(chunk - seg_chunk0[s]) * DEAD_CHUNK;
   r.e = min(seg_off[2 * s + 1], r.b + DEAD_CHUNK);
   return r;
@@ -425,15 +388,12 @@ __global__ __launch_bounds__(256) void sqnorm_ranges_kernel(const float* __restr
   const int n4 = vec ? (int)((r.e - r.b) >> 2) : 0;
   const f32x4* g4 = reinterpret_cast<const f32x4*>(g + r.b);
   float s = 0.f;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    const f32x4 v = g4[i];
-    s += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  }
+  for (int i = threadIdx.x; i < n4; i += 256) s += sqnorm_quad(g4[i]);
   for (int64_t i = r.b + ((int64_t)n4 << 2) + threadIdx.x; i < r.e; i += 256) {
     const float v = g[i];
     s += v * v;
   }
-  s = block_sum(s, red);
+  s = block_reduce<OpAdd>(s, red);
   if (threadIdx.x == 0) ws[blockIdx.x] = s;  // every chunk writes its partial: the workspace needs no clearing
 }
 
@@ -448,26 +408,7 @@ __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p
   const uintptr_t bits = reinterpret_cast<uintptr_t>(p + r.b) | reinterpret_cast<uintptr_t>(g + r.b) | reinterpret_cast<uintptr_t>(m + r.b) |
                          reinterpret_cast<uintptr_t>(v + r.b) | (EMA ? reinterpret_cast<uintptr_t>(e + r.b) : 0);
   const int n4 = (bits & 15u) == 0 ? (int)((r.e - r.b) >> 2) : 0;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    const int64_t o = r.b + ((int64_t)i << 2);
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + o);
-    f32x4 gv = *reinterpret_cast<const f32x4*>(g + o);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + o);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + o);
-    f32x4 ev;
-    if (EMA) ev = *reinterpret_cast<f32x4*>(e + o);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pp = pv[k], mm = mv[k], v2 = vv[k];
-      adam_elem(pp, gv[k], mm, v2, clip, a);
-      pv[k] = pp; mv[k] = mm; vv[k] = v2;
-      if (EMA) ev[k] = ema_next(ev[k], pp, x);
-    }
-    *reinterpret_cast<f32x4*>(p + o) = pv;
-    *reinterpret_cast<f32x4*>(m + o) = mv;
-    *reinterpret_cast<f32x4*>(v + o) = vv;
-    if (EMA) *reinterpret_cast<f32x4*>(e + o) = ev;
-  }
+  for (int i = threadIdx.x; i < n4; i += 256) adam_quad<EMA>(p, g, m, v, e, r.b + ((int64_t)i << 2), clip, a, x);
   for (int64_t i = r.b + ((int64_t)n4 << 2) + threadIdx.x; i < r.e; i += 256) adam_scalar<EMA>(p, g, m, v, e, i, clip, a, x);
 }
 
@@ -479,10 +420,9 @@ __global__ __launch_bounds__(256) void dead_scan_chunk_kernel(const float* __res
                                                               double* __restrict__ psum) {
   __shared__ double red[4];
   const int chunk = blockIdx.x;
-  const int s = dead_find_segment(seg_chunk0, nseg, chunk);
-  const int64_t b = seg_off[2 * s] + (int64_t)(chunk - seg_chunk0[s]) * DEAD_CHUNK;
-  const int64_t e = min(seg_off[2 * s + 1], b + DEAD_CHUNK);
-  const float at = ADAPT ? athr[s] : 0.f;
+  const RangeChunk rc = range_chunk(seg_off, seg_chunk0, nseg);
+  const int64_t b = rc.b, e = rc.e;
+  const float at = ADAPT ? athr[rc.seg] : 0.f;
   double sum = 0.0;
   unsigned cnt = 0;
   // segment starts are 32-byte aligned in the arena and DEAD_CHUNK is a multiple of 4: float4 body, scalar tail
@@ -505,8 +445,8 @@ __global__ __launch_bounds__(256) void dead_scan_chunk_kernel(const float* __res
     if (ADAPT) cnt += ((a < at) && (!use_fixed || a < thr)) ? 1u : 0u;
     else { cnt += (a < thr) ? 1u : 0u; sum += (double)a; }
   }
-  const double c = block_sum_d((double)cnt, red);  // exact: counts are far below 2^53
-  if (!ADAPT) sum = block_sum_d(sum, red);
+  const double c = block_reduce<OpAdd>((double)cnt, red);  // exact: counts are far below 2^53
+  if (!ADAPT) sum = block_reduce<OpAdd>(sum, red);
   if (threadIdx.x == 0) {
     pcnt[chunk] = (unsigned long long)(c + 0.5);
     if (!ADAPT) psum[chunk] = sum;
@@ -685,10 +625,9 @@ static int adamw_launch(const char* who, float* p, const float* g, float* m, flo
   const AdamArgs a = adam_args(max_norm, lr, beta1, beta2, eps, weight_decay, step);
   EmaArgs x{e, (float)(1.0 - ema_decay), ema_decay == 0.0 ? 1 : 0};
   const dim3 grid(ew_blocks(n / 4 + 1));
-  if (e)
-    hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a, x);
-  else
-    hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a, x);
+  dispatch_bool(e != nullptr, [&](auto EMA) {
+    hipLaunchKernelGGL(adamw_kernel<decltype(EMA)::value>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sqnorm, a, x);
+  });
   VAE_LAUNCH_CHECK(who);
   return VAE_OK;
 }
@@ -738,12 +677,10 @@ extern "C" int vae_adamw_ranges(float* p, const float* g, float* m, float* v, fl
   }
   const AdamArgs a = adam_args(max_norm, lr, beta1, beta2, eps, weight_decay, step);
   EmaArgs x{e, (float)(1.0 - ema_decay), ema_decay == 0.0 ? 1 : 0};
-  if (e)
-    hipLaunchKernelGGL(adamw_ranges_kernel<true>, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, p, g, m, v, seg_off, seg_chunk0, nseg,
-                       sqnorm, a, x);
-  else
-    hipLaunchKernelGGL(adamw_ranges_kernel<false>, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, p, g, m, v, seg_off, seg_chunk0, nseg,
-                       sqnorm, a, x);
+  dispatch_bool(e != nullptr, [&](auto EMA) {
+    hipLaunchKernelGGL(adamw_ranges_kernel<decltype(EMA)::value>, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, p, g, m, v, seg_off, seg_chunk0,
+                       nseg, sqnorm, a, x);
+  });
   VAE_LAUNCH_CHECK("adamw_ranges");
   return VAE_OK;
 }

@@ -20,7 +20,7 @@
 // reads it from LDS, a lane per output pixel, 4 pixels per lane.  fp32 FMA accumulation; expf and an IEEE division for the
 // sigmoid.  Vector ALU only: 4 (layer 1) and 65 (layer 2) terms per output are no work for the matrix pipe.
 #include <math.h>
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
 
@@ -40,22 +40,6 @@ constexpr int L1_ITEMS = LHP * (LM / 4);  // (hidden pixel, group of 4 channels)
 constexpr int L1_ROUNDS = (L1_ITEMS + 255) / 256;
 static_assert(LO * LO == 256 * 4, "layer 2: four output pixels per lane");
 
-__device__ __forceinline__ float load_act(const void* x, int64_t i, bool bf16) {
-  if (bf16) return __builtin_bit_cast(float, (unsigned)((const unsigned short*)x)[i] << 16);
-  return ((const float*)x)[i];
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // maps [S][K][HW]; ws [S][K][nchunk * LP_WAVES][2] = {min, max} of the wave's pixels (+inf / -inf for a wave with none)
 __global__ __launch_bounds__(256) void lens_planes_partial_kernel(const void* __restrict__ x, int bf16, int64_t HW, int C, int ld,
                                                                   const int* __restrict__ channels, int K, int nchunk,
@@ -69,7 +53,7 @@ __global__ __launch_bounds__(256) void lens_planes_partial_kernel(const void* __
     const bool ch_ok = (unsigned)ch < (unsigned)C;  // (the host refuses such a list when it can see it; nothing outside x is read)
     float v[LP_PER];
 #pragma unroll
-    for (int i = 0; i < LP_PER; ++i) v[i] = (ch_ok && p[i] < HW) ? load_act(x, ((int64_t)s * HW + p[i]) * ld + ch, bf16) : 0.f;
+    for (int i = 0; i < LP_PER; ++i) v[i] = (ch_ok && p[i] < HW) ? load1(x, ((int64_t)s * HW + p[i]) * ld + ch, bf16) : 0.f;
     float mn = INFINITY, mx = -INFINITY;
     float* mp = maps + ((int64_t)s * K + k) * HW;
 #pragma unroll
@@ -80,8 +64,8 @@ __global__ __launch_bounds__(256) void lens_planes_partial_kernel(const void* __
         mx = fmaxf(mx, v[i]);
       }
     }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
+    mn = wave_reduce<OpMin>(mn);
+    mx = wave_reduce<OpMax>(mx);
     if ((tid & 63) == 0) {
       float* cell = ws + ((((int64_t)s * K + k) * nchunk + chunk) * LP_WAVES + (tid >> 6)) * 2;
       cell[0] = mn;
@@ -103,15 +87,16 @@ __global__ __launch_bounds__(256) void lens_planes_final_kernel(const float* __r
     mn = fminf(mn, cells[2 * i]);
     mx = fmaxf(mx, cells[2 * i + 1]);
   }
-  mn = wave_min(mn);
-  mx = wave_max(mx);
+  // (block_reduce twice would cost three more barriers: both values go through one)
+  mn = wave_reduce<OpMin>(mn);
+  mx = wave_reduce<OpMax>(mx);
   if ((tid & 63) == 0) {
     red[tid >> 6] = mn;
     red[LP_WAVES + (tid >> 6)] = mx;
   }
   __syncthreads();
-  mn = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-  mx = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+  mn = combine4<OpMin>(red);
+  mx = combine4<OpMax>(red + LP_WAVES);
   if (chunk == 0 && tid == 0) {
     range[plane * 2] = mn;
     range[plane * 2 + 1] = mx;
@@ -186,7 +171,7 @@ __global__ __launch_bounds__(256) void lens_project_kernel(const void* __restric
       const int y = y0 + pix / LI, xx = x0 + pix % LI;
       const int ch = chs[ci];
       float v = 0.f;
-      if (y < H && xx < W && (unsigned)ch < (unsigned)C) v = load_act(x, (((int64_t)s * H + y) * W + xx) * ld + ch, bf16);
+      if (y < H && xx < W && (unsigned)ch < (unsigned)C) v = load1(x, (((int64_t)s * H + y) * W + xx) * ld + ch, bf16);
       xs[pix * LXP + ci] = v;
     }
     __syncthreads();

@@ -5,52 +5,9 @@
 // fully coalesced rows), each workgroup owns one pixel chunk of one image, and every
 // cross-workgroup reduction is "per-workgroup partial + fixed-order final pass" so results
 // are bitwise reproducible (the inactivity mask of classifier.py:135 depends on it).
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
-
-// 4 consecutive elements of a gradient tensor stored as fp32 or as bf16 (bf16 mode keeps the conv dgrad outputs and the
-// GroupNorm-backward outputs that only feed convolutions as bf16: their consumers round them to bf16 anyway)
-template <bool BF>
-__device__ __forceinline__ f32x4 load4g(const void* base, int64_t idx4) {
-  if (!BF) return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx4 * 4);
-  const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + idx4 * 4);
-  f32x4 v;
-  v[0] = __builtin_bit_cast(float, r.x << 16);
-  v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-  v[2] = __builtin_bit_cast(float, r.y << 16);
-  v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-  return v;
-}
-__device__ __forceinline__ uint2 pack4_bf16(f32x4 v) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-  bf16x4_t h;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
-  return __builtin_bit_cast(uint2, h);
-}
-
-// activation tensors: element quad `idx4` of a tensor stored as fp32 or bf16
-template <bool BF>
-__device__ __forceinline__ f32x4 load4x(const void* base, int64_t idx4) { return load4g<BF>(base, idx4); }
-template <bool BF>
-__device__ __forceinline__ void store4x(void* base, int64_t idx4, f32x4 v) {
-  if (!BF) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx4 * 4) = v;
-  else *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(base) + idx4 * 4) = pack4_bf16(v);
-}
-
-// layout helper: 256 threads = PR pixel rows x Q float4 lanes (Q = C/4)
-struct Lay {
-  int Q, PR, cq, pr;
-};
-__device__ __forceinline__ Lay make_lay(int C) {
-  Lay l;
-  l.Q = C >> 2;
-  l.PR = 256 / l.Q;
-  l.cq = threadIdx.x % l.Q;
-  l.pr = threadIdx.x / l.Q;
-  return l;
-}
 
 template <bool XBF>
 __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const void* __restrict__ x, int HW, int C, int G,
@@ -58,15 +15,14 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const void* __res
   __shared__ float red[3][256];
   const Lay l = make_lay(C);
   const int chunk = blockIdx.x, b = blockIdx.y;
-  const int per = (HW + nchunk - 1) / nchunk;
-  const int p0 = chunk * per, p1 = min(HW, p0 + per);
+  const ChunkRange cr = chunk_range(HW, nchunk, chunk);
   const int64_t xb4 = (int64_t)b * HW * l.Q;
   // shifted sums around a pivot from the thread's first quad (no cancellation), then centred moments, merged over the group's
   // threads.  The pivot is the median of three of the quad's values, so that one outlier cannot become it: around a pivot of
   // 1e4 among N(0, 1) every d is -1e4 and s1 grows to cnt * 1e4, whose ulp then swallows the values (mean off by 2e-5).
   float pv = 0.f, s1 = 0.f, s2 = 0.f, cnt = 0.f;
-  for (int pix = p0 + l.pr; pix < p1; pix += l.PR) {
-    f32x4 v = load4x<XBF>(x, xb4 + (int64_t)pix * l.Q + l.cq);
+  for (int pix = cr.p0 + l.pr; pix < cr.p1; pix += l.PR) {
+    f32x4 v = load4<XBF>(x, xb4 + (int64_t)pix * l.Q + l.cq);
     if (cnt == 0.f) pv = __builtin_amdgcn_fmed3f(v[0], v[1], v[2]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -116,7 +72,7 @@ __global__ __launch_bounds__(256) void gn_stats_final_kernel(const float* __rest
   // group the 4096 chunks of a 1024^2 image took 17 us x 400 launches per step).
   const int gw = G / (int)gridDim.y, g0 = (int)blockIdx.y * gw;
   const int parts = 256 / gw;  // gw <= 64
-  const int per = (HW + nchunk - 1) / nchunk;
+  const int per = (HW + nchunk - 1) / nchunk;  // (the chunk's pixel count stays spelled out: through chunk_span the kernel takes one SGPR more)
   const int cpg_ = C / G;
   const int gl = threadIdx.x % gw, part_ = threadIdx.x / gw;
   const int g_ = g0 + gl;
@@ -183,16 +139,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const void* __restrict__ 
   for (; i < n4; i += stride) {
     const int b = (int)(i / HWQ);
     const int c = (int)(i % Q) * 4;
-    f32x4 v = load4x<XBF>(x, i);
+    f32x4 v = load4<XBF>(x, i);
     f32x4 sc = *reinterpret_cast<const f32x4*>(scale + (int64_t)b * C + c);
     f32x4 sh = *reinterpret_cast<const f32x4*>(shift + (int64_t)b * C + c);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float u = v[e] * sc[e] + sh[e];
-      o[e] = (xf == VAE_XF_AFFINE_SILU) ? silu_f(u) : u;
-    }
-    *reinterpret_cast<f32x4*>(y + i * 4) = o;
+    for (int e = 0; e < 4; ++e) o[e] = affine_xf(v[e], sc[e], sh[e], xf);
+    store4<false>(y, i, o);
   }
 }
 
@@ -201,23 +154,19 @@ template <bool XBF>
 __global__ __launch_bounds__(256) void gn_apply_bf16_kernel(const void* __restrict__ x, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, int64_t n8, int HWQ, int Q,
                                                             int C, int xf, unsigned short* __restrict__ y) {
-  typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (; i < n8; i += stride) {
     const int b = (int)(i / HWQ);
     const int c = (int)(i % Q) * 8;
-    bf16x8_t h;
+    bf16x8 h;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      const f32x4 v = load4x<XBF>(x, i * 2 + half);
+      const f32x4 v = load4<XBF>(x, i * 2 + half);
       const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + (int64_t)b * C + c + half * 4);
       const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + (int64_t)b * C + c + half * 4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float u = v[e] * sc[e] + sh[e];
-        h[half * 4 + e] = (__bf16)((xf == VAE_XF_AFFINE_SILU) ? silu_f(u) : u);
-      }
+      for (int e = 0; e < 4; ++e) h[half * 4 + e] = (__bf16)affine_xf(v[e], sc[e], sh[e], xf);
     }
     *reinterpret_cast<uint4*>(y + i * 8) = __builtin_bit_cast(uint4, h);
   }
@@ -246,14 +195,13 @@ __global__ __launch_bounds__(256) void gn_track_partial_kernel(const void* __res
   __shared__ f32x4 red[256];
   const Lay l = make_lay(C);
   const int chunk = blockIdx.x, b = blockIdx.y;
-  const int per = (HW + nchunk - 1) / nchunk;
-  const int p0 = chunk * per, p1 = min(HW, p0 + per);
+  const ChunkRange cr = chunk_range(HW, nchunk, chunk);
   const int64_t xb4 = (int64_t)b * HW * l.Q;
   const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + (int64_t)b * C + l.cq * 4);
   const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + (int64_t)b * C + l.cq * 4);
   f32x4 s = {0, 0, 0, 0};
-  for (int pix = p0 + l.pr; pix < p1; pix += l.PR) {
-    f32x4 v = load4x<XBF>(x, xb4 + (int64_t)pix * l.Q + l.cq);
+  for (int pix = cr.p0 + l.pr; pix < cr.p1; pix += l.PR) {
+    f32x4 v = load4<XBF>(x, xb4 + (int64_t)pix * l.Q + l.cq);
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] += fabsf(v[e] * sc[e] + sh[e]);
   }
@@ -300,17 +248,16 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const void* __restr
   __shared__ f32x4 red[2][256];
   const Lay l = make_lay(C);
   const int chunk = blockIdx.x, b = blockIdx.y;
-  const int per = (HW + nchunk - 1) / nchunk;
-  const int p0 = chunk * per, p1 = min(HW, p0 + per);
+  const ChunkRange cr = chunk_range(HW, nchunk, chunk);
   const int c = l.cq * 4, grp = c / (C / G);
   const float mu = mean[b * G + grp], rs = rstd[b * G + grp];
   const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
   const int64_t gb4 = (int64_t)b * HW * (C / 4);
   f32x4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
-  for (int pix = p0 + l.pr; pix < p1; pix += l.PR) {
-    f32x4 v = load4x<XBF>(x, gb4 + (int64_t)pix * (C / 4) + l.cq);
-    f32x4 gv = load4g<GBF>(g, gb4 + (int64_t)pix * (C / 4) + l.cq);
+  for (int pix = cr.p0 + l.pr; pix < cr.p1; pix += l.PR) {
+    f32x4 v = load4<XBF>(x, gb4 + (int64_t)pix * (C / 4) + l.cq);
+    f32x4 gv = load4<GBF>(g, gb4 + (int64_t)pix * (C / 4) + l.cq);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float xh = (v[e] - mu) * rs;
@@ -429,8 +376,11 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_rows_kernel(const void* __re
                                                                 const float* __restrict__ coef, const void* __restrict__ add,
                                                                 int HW, int C, int G, int per, float* __restrict__ dx,
                                                                 unsigned short* __restrict__ dx16) {
-  const int Q = C >> 2, PR = 256 / Q, q = threadIdx.x % Q, r = threadIdx.x / Q;
-  const int b = blockIdx.y, p0 = blockIdx.x * per, p1 = min(HW, p0 + per);
+  const Lay l = make_lay(C);
+  const int Q = l.Q, PR = l.PR, q = l.cq, r = l.pr;
+  const int b = blockIdx.y;
+  const ChunkRange cr = chunk_span(HW, per, blockIdx.x);
+  const int p0 = cr.p0, p1 = cr.p1;
   const int c = q * 4, grp = c / (C / G);
   const float mu = mean[b * G + grp], rs = rstd[b * G + grp];
   const float k0 = coef[((int64_t)b * G + grp) * 2 + 0], k1 = coef[((int64_t)b * G + grp) * 2 + 1];
@@ -441,9 +391,9 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_rows_kernel(const void* __re
 #pragma unroll
     for (int u = 0; u < GN_UN; ++u) {
       const int64_t i = img + (int64_t)min(p + u * PR, p1 - 1) * Q;  // (a tail re-reads the last pixel)
-      v[u] = load4x<XBF>(x, i);
-      gv[u] = load4g<GBF>(g, i);
-      if (add) o[u] = load4x<XBF>(add, i);  // (the residual-path gradient is stored like x)
+      v[u] = load4<XBF>(x, i);
+      gv[u] = load4<GBF>(g, i);
+      if (add) o[u] = load4<XBF>(add, i);  // (the residual-path gradient is stored like x)
       else o[u] = f32x4{0, 0, 0, 0};
     }
 #pragma unroll
@@ -457,8 +407,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_rows_kernel(const void* __re
       }
       if (p + u * PR < p1) {
         const int64_t i = img + (int64_t)(p + u * PR) * Q;
-        if (dx) *reinterpret_cast<f32x4*>(dx + i * 4) = o[u];
-        if (dx16) *reinterpret_cast<uint2*>(dx16 + i * 4) = pack4_bf16(o[u]);
+        if (dx) store4<false>(dx, i, o[u]);
+        if (dx16) store4<true>(dx16, i, o[u]);
       }
     }
   }
@@ -472,10 +422,6 @@ int check_gn(const char* who, int B, int HW, int C, int G, int nchunk) {
   VAE_CHECK(nchunk <= 65535 && B <= 65535, "%s: grid too large", who);
   return 0;
 }
-inline int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
 
 }  // namespace
 
@@ -483,8 +429,9 @@ extern "C" int vae_gn_stats_partial(const void* x, int32_t x_bf16, int32_t B, in
                                     float* ws, void* stream) {
   if (int e = check_gn("gn_stats_partial", B, HW, C, G, nchunk)) return e;
   VAE_CHECK(x && ws && aligned16(x), "gn_stats_partial: bad pointers");
-  if (x_bf16) hipLaunchKernelGGL(gn_stats_partial_kernel<true>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, HW, C, G, nchunk, ws);
-  else hipLaunchKernelGGL(gn_stats_partial_kernel<false>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, HW, C, G, nchunk, ws);
+  dispatch_bool(x_bf16, [&](auto XB) {
+    hipLaunchKernelGGL(gn_stats_partial_kernel<decltype(XB)::value>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, HW, C, G, nchunk, ws);
+  });
   VAE_LAUNCH_CHECK("gn_stats_partial");
   return VAE_OK;
 }
@@ -508,8 +455,9 @@ extern "C" int vae_gn_apply(const void* x, int32_t x_bf16, const float* scale, c
   VAE_CHECK(aligned16(x) && aligned16(y) && aligned16(scale) && aligned16(shift), "gn_apply: unaligned");
   const int Q = C / 4;
   const int64_t n4 = (int64_t)B * HW * Q;
-  if (x_bf16) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n4, HW * Q, Q, C, xf, y);
-  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n4, HW * Q, Q, C, xf, y);
+  dispatch_bool(x_bf16, [&](auto XB) {
+    hipLaunchKernelGGL(gn_apply_kernel<decltype(XB)::value>, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n4, HW * Q, Q, C, xf, y);
+  });
   VAE_LAUNCH_CHECK("gn_apply");
   return VAE_OK;
 }
@@ -520,10 +468,10 @@ extern "C" int vae_gn_apply_bf16(const void* x, int32_t x_bf16, const float* sca
   VAE_CHECK(aligned16(x) && aligned16(y16) && aligned16(scale) && aligned16(shift), "gn_apply_bf16: unaligned");
   const int Q = C / 8;
   const int64_t n8 = (int64_t)B * HW * Q;
-  if (x_bf16) hipLaunchKernelGGL(gn_apply_bf16_kernel<true>, dim3(ew_blocks(n8)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n8,
-                                 HW * Q, Q, C, xf, reinterpret_cast<unsigned short*>(y16));
-  else hipLaunchKernelGGL(gn_apply_bf16_kernel<false>, dim3(ew_blocks(n8)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n8,
-                          HW * Q, Q, C, xf, reinterpret_cast<unsigned short*>(y16));
+  dispatch_bool(x_bf16, [&](auto XB) {
+    hipLaunchKernelGGL(gn_apply_bf16_kernel<decltype(XB)::value>, dim3(ew_blocks(n8)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, n8,
+                       HW * Q, Q, C, xf, reinterpret_cast<unsigned short*>(y16));
+  });
   VAE_LAUNCH_CHECK("gn_apply_bf16");
   return VAE_OK;
 }
@@ -534,8 +482,9 @@ extern "C" int vae_gn_track_partial(const void* x, int32_t x_bf16, const float* 
   VAE_CHECK(C > 0 && C % 4 == 0 && (C / 4) <= 256 && 256 % (C / 4) == 0, "gn_track_partial: C=%d unsupported", C);
   VAE_CHECK(x && scale && shift && ws && aligned16(x) && aligned16(scale) && aligned16(shift) && aligned16(ws),
             "gn_track_partial: bad pointers");
-  if (x_bf16) hipLaunchKernelGGL(gn_track_partial_kernel<true>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, scale, shift, HW, C, nchunk, ws);
-  else hipLaunchKernelGGL(gn_track_partial_kernel<false>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, scale, shift, HW, C, nchunk, ws);
+  dispatch_bool(x_bf16, [&](auto XB) {
+    hipLaunchKernelGGL(gn_track_partial_kernel<decltype(XB)::value>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, scale, shift, HW, C, nchunk, ws);
+  });
   VAE_LAUNCH_CHECK("gn_track_partial");
   return VAE_OK;
 }
@@ -553,12 +502,14 @@ extern "C" int vae_gn_bwd_partial(const void* x, int32_t x_bf16, const void* g, 
   if (int e = check_gn("gn_bwd_partial", B, HW, C, G, nchunk)) return e;
   VAE_CHECK(x && g && mean && rstd && gamma && beta && ws, "gn_bwd_partial: null pointer");
   VAE_CHECK(aligned16(x) && aligned16(g) && aligned16(gamma) && aligned16(beta), "gn_bwd_partial: unaligned");
-#define GNP(S, BF, XB) hipLaunchKernelGGL((gn_bwd_partial_kernel<S, BF, XB>), dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, g, mean, rstd, gamma, beta, HW, C, G, nchunk, ws)
-#define GNP2(S, BF) do { if (x_bf16) GNP(S, BF, true); else GNP(S, BF, false); } while (0)
-  if (silu) { if (g_bf16) GNP2(true, true); else GNP2(true, false); }
-  else { if (g_bf16) GNP2(false, true); else GNP2(false, false); }
-#undef GNP2
-#undef GNP
+  dispatch_bool(silu, [&](auto S) {
+    dispatch_bool(g_bf16, [&](auto GB) {
+      dispatch_bool(x_bf16, [&](auto XB) {
+        hipLaunchKernelGGL((gn_bwd_partial_kernel<decltype(S)::value, decltype(GB)::value, decltype(XB)::value>), dim3(nchunk, B), dim3(256), 0,
+                           (hipStream_t)stream, x, g, mean, rstd, gamma, beta, HW, C, G, nchunk, ws);
+      });
+    });
+  });
   VAE_LAUNCH_CHECK("gn_bwd_partial");
   return VAE_OK;
 }
@@ -582,16 +533,15 @@ extern "C" int vae_gn_bwd_apply(const void* x, int32_t x_bf16, const void* g, co
   VAE_CHECK(aligned16(x) && aligned16(g) && aligned16(dx) && aligned16(dx16) && aligned16(gamma) && aligned16(beta) &&
                 (add == nullptr || aligned16(add)),
             "gn_bwd_apply: unaligned");
-  const int Q = C / 4;
-  const int64_t n4 = (int64_t)B * HW * Q;
-  const RowPlan pl = row_plan(B, HW, Q);  // (check_gn: C / 4 divides 256)
-  (void)n4;
-#define GNA(S, BF, XB) hipLaunchKernelGGL((gn_bwd_apply_rows_kernel<S, BF, XB>), dim3(pl.nchunk, B), dim3(256), 0, (hipStream_t)stream, x, g, mean, rstd, gamma, beta, coef, add, HW, C, G, pl.per, dx, (unsigned short*)dx16)
-#define GNA2(S, BF) do { if (x_bf16) GNA(S, BF, true); else GNA(S, BF, false); } while (0)
-  if (silu) { if (g_bf16) GNA2(true, true); else GNA2(true, false); }
-  else { if (g_bf16) GNA2(false, true); else GNA2(false, false); }
-#undef GNA2
-#undef GNA
+  const RowPlan pl = row_plan(B, HW, C / 4);  // (check_gn: C / 4 divides 256)
+  dispatch_bool(silu, [&](auto S) {
+    dispatch_bool(g_bf16, [&](auto GB) {
+      dispatch_bool(x_bf16, [&](auto XB) {
+        hipLaunchKernelGGL((gn_bwd_apply_rows_kernel<decltype(S)::value, decltype(GB)::value, decltype(XB)::value>), dim3(pl.nchunk, B), dim3(256),
+                           0, (hipStream_t)stream, x, g, mean, rstd, gamma, beta, coef, add, HW, C, G, pl.per, dx, (unsigned short*)dx16);
+      });
+    });
+  });
   VAE_LAUNCH_CHECK("gn_bwd_apply");
   return VAE_OK;
 }

@@ -8,28 +8,21 @@
 // sum(y^2) - n mean^2 is ever formed in fp32.  Final pass: the cells of each channel are turned into (mean, M2) and merged in fp64
 // with Chan's formula (one workgroup per channel), then the channels are merged the same way (one workgroup).  Every reduction is
 // a fixed-order loop or LDS tree: no atomics, repeated launches are bitwise identical.
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
 
-// W consecutive channels of one pixel, stored as fp32 or bf16 (bf16: the upper half of an fp32, as load4x in norm.hip)
+// W consecutive channels of one pixel
 template <int W, bool XBF>
 __device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4 && !XBF) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
+  if constexpr (W == 4) {
+    f32x4 q;  // (an element offset, not a quad index: off is a multiple of 4 only where the host chose W = 4)
+    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
+    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
     v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else if constexpr (W == 4) {
-    const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + off);
-    v[0] = __builtin_bit_cast(float, r.x << 16);
-    v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-    v[2] = __builtin_bit_cast(float, r.y << 16);
-    v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
   } else {
 #pragma unroll
-    for (int e = 0; e < W; ++e) {
-      if constexpr (!XBF) v[e] = reinterpret_cast<const float*>(base)[off + e];
-      else v[e] = __builtin_bit_cast(float, (unsigned)reinterpret_cast<const unsigned short*>(base)[off + e] << 16);
-    }
+    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
   }
 }
 
@@ -37,10 +30,7 @@ template <int W>
 __device__ __forceinline__ void apply_xf(float (&v)[W], const float (&sc)[W], const float (&sh)[W], int xf) {
   if (xf == VAE_XF_NONE) return;
 #pragma unroll
-  for (int e = 0; e < W; ++e) {
-    const float u = v[e] * sc[e] + sh[e];  // the arithmetic of gn_apply_kernel
-    v[e] = (xf == VAE_XF_AFFINE_SILU) ? silu_f(u) : u;
-  }
+  for (int e = 0; e < W; ++e) v[e] = affine_xf(v[e], sc[e], sh[e], xf);
 }
 
 // ws: [C][B * nchunk] cells of {sum|y|, sum(y - K), sum((y - K)^2), K}
@@ -52,12 +42,12 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const void* __rest
   const int nu = C / W;                          // channel units of W channels
   const int u0 = blockIdx.z * 256;
   const int nut = min(256, nu - u0);             // units of this workgroup
-  const int PR = 256 / nut;                      // pixel rows of the workgroup
-  const int ul = threadIdx.x % nut, pr = threadIdx.x / nut;
-  const int c0 = (u0 + ul) * W;
+  const Lay l = make_lay_q(nut);
+  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
+  const int c0 = (u0 + l.cq) * W;
   const int chunk = blockIdx.x, b = blockIdx.y;
-  const int per = (HW + nchunk - 1) / nchunk;
-  const int p0 = chunk * per, p1 = min(HW, p0 + per);  // p0 < HW: the host makes every chunk non-empty
+  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
+  const int p0 = cr.p0, p1 = cr.p1;
   float sc[W], sh[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) {
@@ -122,7 +112,7 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const void* __rest
         t[1] += red[1][e][i];
         t[2] += red[2][e][i];
       }
-      *reinterpret_cast<f32x4*>(ws + ((int64_t)(c0 + e) * rows + row) * 4) = t;
+      store4<false>(ws, (int64_t)(c0 + e) * rows + row, t);
     }
   }
 }
@@ -164,9 +154,9 @@ __global__ __launch_bounds__(256) void moments_channel_kernel(const float* __res
   Mom a{0.0, 0.0, 0.0};
   double sa = 0.0;
   for (int r = threadIdx.x; r < rows; r += 256) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(ws + ((int64_t)c * rows + r) * 4);
-    const int p0 = (r % nchunk) * per;
-    const double n = (double)(min(HW, p0 + per) - p0);
+    const f32x4 t = load4<false>(ws, (int64_t)c * rows + r);
+    const ChunkRange cr = chunk_span(HW, per, r % nchunk);
+    const double n = (double)(cr.p1 - cr.p0);
     const double s1 = t[1], dm = s1 / n;
     sa += (double)t[0];
     a = mom_merge(a, Mom{n, (double)t[3] + dm, fmax((double)t[2] - s1 * dm, 0.0)});
@@ -218,10 +208,12 @@ extern "C" int vae_moments_partial(const void* x, int32_t x_bf16, const float* s
   const int tiles = (C / W + 255) / 256;
   const dim3 grid(nchunk, B, tiles);
   hipStream_t s = (hipStream_t)stream;
-#define MPK(WW, BF) hipLaunchKernelGGL((moments_partial_kernel<WW, BF>), grid, dim3(256), 0, s, x, scale, shift, xf, HW, C, ld, nchunk, ws)
-  if (vec) { if (x_bf16) MPK(4, true); else MPK(4, false); }
-  else { if (x_bf16) MPK(1, true); else MPK(1, false); }
-#undef MPK
+  dispatch_bool(vec, [&](auto V) {
+    dispatch_bool(x_bf16, [&](auto XB) {
+      hipLaunchKernelGGL((moments_partial_kernel<decltype(V)::value ? 4 : 1, decltype(XB)::value>), grid, dim3(256), 0, s, x, scale, shift, xf, HW,
+                         C, ld, nchunk, ws);
+    });
+  });
   VAE_LAUNCH_CHECK("moments_partial");
   return VAE_OK;
 }
