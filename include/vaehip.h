@@ -382,6 +382,54 @@ int vae_mse_bwd(const float* recon, const float* target, int64_t n, float scale,
 int vae_sample_kl_bwd(const float* moments, const float* eps, const float* dz, int32_t B, int32_t hw,
                       int32_t L, float kl_weight, float* dmoments, void* stream);
 
+/* ---- reconstruction losses beyond MSE with their gradient seeds (vaehip/losses.py; not in the reference, whose loss is the
+ * MSE above), csrc/recon_loss.hip ----
+ *   rec = pixel + ssim_weight * (1 - ssim),  total = rec + kl_weight * kl,  drecon = grad_scale * d rec / d recon
+ * pixel, by kind, with d = fp32(recon - target) over n elements: mean d^2 (MSE), mean |d| (L1), or Huber's
+ * mean(|d| <= delta ? d^2 / 2 : delta * (|d| - delta / 2)).
+ * ssim: mean over images, channels and window positions of the SSIM index of u(recon) against u(target), u(v) = (v + 1) / 2 in
+ * float64 and NOT clamped (vae_image_metrics_* clamp: the two differ once a reconstruction leaves [-1, 1]); 11 x 11 gaussian
+ * window, sigma 1.5, c1 = 0.01^2, c2 = 0.03^2, over the (H - 10) x (W - 10) positions whose window lies inside the image.
+ * All sums, window statistics and the SSIM gradient are float64 up to the one fp32 store; no atomics, fixed-order second
+ * stages: repeated launches are bitwise identical.  A bad argument returns VAE_EINVAL before anything is launched. */
+#define VAE_LOSS_MSE 0
+#define VAE_LOSS_L1 1
+#define VAE_LOSS_HUBER 2
+/* pixel term and seed in one read of recon and target (n contiguous fp32 elements each, 4-byte aligned; 16-byte accesses when
+ * recon, target and drecon are all 16-byte aligned).  partial: vae_pixel_loss_blocks(n) doubles, the
+ * workgroups' sums of the term, formed in double from the fp32 d.  drecon (null: loss only) = coef * g(d) in fp32, one
+ * subtraction and one multiplication, coef = (float)(grad_scale * k / n), k = 2 for MSE and 1 otherwise; g(d) = d (MSE),
+ * sign(d) with sign(0) = 0 (L1), |d| <= delta ? d : (float)delta * sign(d) (Huber; delta > 0 is read for Huber only). */
+int vae_pixel_loss_blocks(int64_t n); /* the number of partials for n elements (needs no GPU); VAE_EINVAL for n < 1 */
+int vae_pixel_loss(const float* recon, const float* target, int64_t n, int32_t kind, double delta, double grad_scale,
+                   double* partial, float* drecon, void* stream);
+/* SSIM term.  pred, target (and drecon): fp32 images of logical shape (B, C, H, W), each with its own four ELEMENT strides
+ * (batch, channel, row, column), read in place; H < 11 or W < 11 is VAE_EINVAL.
+ * vae_ssim_tile(0 / 1): rows / columns of the tile a workgroup covers: window positions in the forward, pixels in the backward
+ *   (tests sit on its edges).
+ * vae_ssim_workspace: *npartial doubles (one sum of the index per forward workgroup, image-major) and *nmaps doubles
+ *   (3 * B * C * (H - 10) * (W - 10): per window position a = dS/d mu_p, b = dS/d E[p^2], c = dS/d E[p t]); needs no GPU.
+ * vae_ssim_fwd: writes partial, and maps unless maps is null (forward only).
+ * vae_ssim_index: out [B] float64 = each image's mean index from partial.
+ * vae_ssim_bwd: drecon[pixel] += (float)(-scale * 1/2 * (G'a + 2 u(pred) G'b + u(target) G'c) / positions), G' the transposed
+ *   gaussian over the maps (zero outside the valid positions), positions = B * C * (H - 10) * (W - 10), scale = grad_scale *
+ *   ssim_weight (the sign is that of 1 - ssim).  Every pixel is updated by exactly one workgroup, once. */
+int vae_ssim_tile(int32_t axis);
+int vae_ssim_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int64_t* npartial, int64_t* nmaps);
+int vae_ssim_fwd(const float* pred, int64_t psb, int64_t psc, int64_t psh, int64_t psw, const float* target, int64_t tsb,
+                 int64_t tsc, int64_t tsh, int64_t tsw, int32_t B, int32_t C, int32_t H, int32_t W, double* partial, double* maps,
+                 void* stream);
+int vae_ssim_index(const double* partial, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* stream);
+int vae_ssim_bwd(const float* pred, int64_t psb, int64_t psc, int64_t psh, int64_t psw, const float* target, int64_t tsb,
+                 int64_t tsc, int64_t tsh, int64_t tsw, const double* maps, int32_t B, int32_t C, int32_t H, int32_t W,
+                 double scale, float* drecon, int64_t dsb, int64_t dsc, int64_t dsh, int64_t dsw, void* stream);
+/* one workgroup: pixel_partial (of n elements), ssim_partial (of this B, C, H, W; null: no SSIM term, C / H / W unread and
+ * terms[1] = NaN) and kl_partial [B][kl_nblk] (vae_sample_kl) -> scalars[3] = {rec, kl, total} (the shape vae_loss_final
+ * writes), terms[2] = {pixel, ssim}; folded in float64, stored as fp32 */
+int vae_recon_loss_final(const double* pixel_partial, int64_t n, const double* ssim_partial, int32_t B, int32_t C, int32_t H,
+                         int32_t W, double ssim_weight, const float* kl_partial, int32_t kl_nblk, float kl_weight, float* scalars,
+                         float* terms, void* stream);
+
 /* ---- layout / misc ---- */
 int vae_nchw_to_nhwc(const float* src, int32_t B, int32_t C, int32_t HW, int32_t Cpad, float* dst, void* stream);
 int vae_nhwc_to_nchw(const float* src, int32_t B, int32_t C, int32_t HW, float* dst, void* stream);

@@ -48,6 +48,7 @@ from classification.classifier import RegionClassifier
 from intervention.nudger import InterventionHandler
 from vaehip.trainer import HipTrainer
 from vaehip.dp import allreduce_mean_
+from vaehip.losses import KINDS as LOSS_KINDS, SSIM_WINDOW, ReconLoss
 
 setup_logging()
 logger = logging.getLogger(__name__)
@@ -246,6 +247,33 @@ def ema_settings(training_cfg: dict):
     return bool(training_cfg.get("use_ema", False)), decay
 
 
+def recon_loss_settings(training_cfg: dict, resolution=None) -> ReconLoss:
+    """training.reconstruction_loss (mse | l1 | huber), training.huber_delta, training.ssim_weight (not keys of the reference) ->
+    the spec of vaehip.losses; the defaults (`mse`, weight 0) are the default spec, the reference's loss.  `resolution`:
+    data.resolution, which an SSIM term needs to be at least its window."""
+    kind = training_cfg.get("reconstruction_loss", "mse")
+    if not isinstance(kind, str) or kind not in LOSS_KINDS:
+        raise ValueError(f"training.reconstruction_loss={kind!r}: expected one of {', '.join(LOSS_KINDS)}")
+
+    def number(key, default):
+        v = training_cfg.get(key, default)
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            return float(v)  # YAML reads 1e-1 as a string
+        except (TypeError, ValueError):
+            raise ValueError(f"training.{key}={v!r}: expected a number") from None
+    delta, weight = number("huber_delta", 1.0), number("ssim_weight", 0.0)
+    if not 0.0 < delta < float("inf"):
+        raise ValueError(f"training.huber_delta={delta!r}: must be a finite number > 0")
+    if not 0.0 <= weight < float("inf"):
+        raise ValueError(f"training.ssim_weight={weight!r}: must be a finite number >= 0")
+    if weight > 0.0 and resolution is not None and int(resolution) < SSIM_WINDOW:
+        raise ValueError(f"training.ssim_weight={weight!r} with data.resolution={resolution!r}: the SSIM window is "
+                         f"{SSIM_WINDOW} x {SSIM_WINDOW} pixels and images must be at least that large")
+    return ReconLoss(kind=kind, huber_delta=delta if kind == "huber" else 1.0, ssim_weight=weight)
+
+
 def trainable_setting(training_cfg: dict):
     """training.trainable_modules (not a key of the reference) -> the `trainable` argument of HipTrainer: absent or 'all' trains
     everything, 'decoder' / 'encoder' are the shorthands of vaehip.trainable, a list holds module-name prefixes of the VAE"""
@@ -371,6 +399,9 @@ def main():
     resume = training_cfg.get("resume_from_checkpoint", None)
     # not a key of the reference: which parameters train ('all', 'decoder', 'encoder' or module-name prefixes); the rest is frozen
     trainable = trainable_setting(training_cfg)
+    # not keys of the reference: the pixel term (mse | l1 | huber) and an SSIM term of the training loss; validation and
+    # evaluate.py keep the reference's MSE, so runs stay comparable
+    recon_loss = recon_loss_settings(training_cfg, config.get("data", {}).get("resolution", 256))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -445,7 +476,7 @@ def main():
         max_grad_norm=max_grad_norm, kl_weight=kl_weight, lr_warmup_steps=int(training_cfg.get("lr_warmup_steps", 100)),
         max_train_steps=max_train_steps, scheduler_steps_per_update=world,  # accelerate steps the scheduler `world` times
         mixed_precision=mixed_precision, gradient_accumulation_steps=grad_accum, checkpoint_decoder=bool(grad_ckpt),
-        use_ema=use_ema, ema_decay=ema_decay, trainable=trainable)
+        use_ema=use_ema, ema_decay=ema_decay, trainable=trainable, recon_loss=recon_loss)
     n_tr = sum(p.numel() for p in vae_wrapper.vae.parameters() if p.requires_grad)
     logger.info(f"trainable_modules={trainable!r}: {n_tr} of {sum(p.numel() for p in vae_wrapper.vae.parameters())} parameters train, "
                 f"in {len(trainer.trainable_ranges)} arena range(s)")
@@ -496,6 +527,7 @@ def main():
         epoch_sums = torch.zeros(3, device=device, dtype=torch.float64)  # mse, kl, total (this rank)
         steps_in_epoch = 0
         sc = torch.zeros(3, device=device)
+        res = None
         for batch, ok_everywhere, last_batch in agreed_batches(train_dataloader, world):
             if skip_batches > 0:
                 skip_batches -= 1
@@ -541,8 +573,14 @@ def main():
             if global_step % log_interval == 0:
                 step_loss = allreduce_mean_(sc[2:3].clone()).item()  # the only host sync of a logging step
                 if is_main:
+                    loss_logs = {}
+                    if res is not None and not recon_loss.is_default:  # this rank's terms of the last micro-batch (ssim: with an SSIM term only)
+                        terms = res["loss_terms"].tolist()
+                        loss_logs["train/pixel_loss"] = terms[0]
+                        if recon_loss.ssim_weight > 0:
+                            loss_logs["train/ssim"] = terms[1]
                     mlog.log({"train_loss_step": step_loss, "lr": trainer.lr_scheduler.get_last_lr()[0], "epoch_current": epoch,
-                              **activity_logs}, global_step)
+                              **loss_logs, **activity_logs}, global_step)
                     logger.info(f"step {global_step}/{max_train_steps} loss {step_loss:.4e} lr {trainer.lr_scheduler.get_last_lr()[0]:.3e} "
                                 f"({(time.time() - t_start) / (global_step - step0) * 1e3:.0f} ms/step)")
             if dnt and global_step % dnt_interval == 0:

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .losses import as_spec
 from .ops import XF_AFFINE, XF_AFFINE_SILU, XF_NONE, Stats
 
 _TRACK_C = {4, 8, 16, 32, 64, 128, 256, 512, 1024}
@@ -625,11 +626,15 @@ class Engine:
     # ------------------------------------------------------------------ fused train / eval step (fast path)
     def forward_backward(self, pixel_values: torch.Tensor, eps: Optional[torch.Tensor], kl_weight: float,
                          sample_posterior: bool = True, generator: Optional[torch.Generator] = None,
-                         grad_scale: float = 1.0):
+                         grad_scale: float = 1.0, recon_loss=None):
         """fwd + loss (train.py:289-291) + bwd; gradients are WRITTEN into arena.grad (no accumulation), scaled by
         `grad_scale` (= 1/gradient_accumulation_steps: accelerate divides the loss before backward, train.py:286,299).
-        Returns dict(scalars[3]=mse,kl,total on device, reconstruction, moments, latents) as NHWC buffers."""
+        recon_loss: a vaehip.losses.ReconLoss; None or the default spec is the reference's MSE through the calls the step always
+        made, anything else goes through ops.recon_loss and scalars[0] is pixel + ssim_weight * (1 - ssim).
+        Returns dict(scalars[3]=rec,kl,total on device, loss_terms[2]=pixel term, SSIM index (None on the default path),
+        drecon = the seed grad_scale * d rec / d reconstruction, reconstruction, moments, latents) as NHWC buffers."""
         self._require_gpu()
+        spec = as_spec(recon_loss)
         pv = pixel_values.contiguous()
         with self._mode():
             x4 = ops.nchw_to_nhwc(pv, 4)
@@ -646,8 +651,12 @@ class Engine:
                 recon = self.decode_nhwc(z, td)
             finally:
                 self._live = True
-            scalars = ops.mse_kl_loss(recon, tgt, klp, kl_weight)
-            drec = ops.mse_bwd(recon, tgt, grad_scale)
+            terms = None
+            if spec.is_default:
+                scalars = ops.mse_kl_loss(recon, tgt, klp, kl_weight)
+                drec = ops.mse_bwd(recon, tgt, grad_scale)
+            else:
+                scalars, terms, drec = ops.recon_loss(recon, tgt, klp, kl_weight, spec, grad_scale)
             self.arena.attach_grads()
             dz = self.run_tape(td, drec, self.arena.grad)
             if enc_live:
@@ -655,12 +664,14 @@ class Engine:
                 self.run_tape(te, dmom, self.arena.grad)
         if self.reducer is not None:
             self.reducer.ready(0)
-        return {"scalars": scalars, "reconstruction": recon, "moments": mom, "latents": z, "kl_partial": klp}
+        return {"scalars": scalars, "loss_terms": terms, "drecon": drec, "reconstruction": recon, "moments": mom, "latents": z,
+                "kl_partial": klp}
 
     @torch.no_grad()
     def forward_eval(self, pixel_values: torch.Tensor, eps: Optional[torch.Tensor] = None, sample_posterior: bool = False,
-                     kl_weight: float = 0.0, generator: Optional[torch.Generator] = None):
+                     kl_weight: float = 0.0, generator: Optional[torch.Generator] = None, recon_loss=None):
         self._require_gpu()
+        spec = as_spec(recon_loss)
         pv = pixel_values.contiguous()
         x4 = ops.nchw_to_nhwc(pv, 4)
         tgt = ops.nchw_to_nhwc(pv, 3)
@@ -669,8 +680,12 @@ class Engine:
             e = self._eps_nhwc(eps, mom, sample_posterior, generator)
             z, klp = ops.sample_kl(mom, e)
             recon = self.decode_nhwc(z, None)
-        scalars = ops.mse_kl_loss(recon, tgt, klp, kl_weight)
-        return {"scalars": scalars, "reconstruction": recon, "moments": mom, "latents": z, "kl_partial": klp}
+        terms = None
+        if spec.is_default:
+            scalars = ops.mse_kl_loss(recon, tgt, klp, kl_weight)
+        else:
+            scalars, terms, _ = ops.recon_loss(recon, tgt, klp, kl_weight, spec, want_grad=False)
+        return {"scalars": scalars, "loss_terms": terms, "reconstruction": recon, "moments": mom, "latents": z, "kl_partial": klp}
 
     @staticmethod
     def _eps_nhwc(eps, mom, sample_posterior, generator):

@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 17  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 18  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -108,6 +108,14 @@ SIGNATURES = {
     "vae_loss_final": [vp, i32, i64, vp, i32, i32, f32, vp, vp],
     "vae_mse_bwd": [vp, vp, i64, f32, vp, vp],
     "vae_sample_kl_bwd": [vp, vp, vp, i32, i32, i32, f32, vp, vp],
+    "vae_pixel_loss_blocks": [i64],
+    "vae_pixel_loss": [vp, vp, i64, i32, f64, f64, vp, vp, vp],
+    "vae_ssim_tile": [i32],
+    "vae_ssim_workspace": [i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)],
+    "vae_ssim_fwd": [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp],
+    "vae_ssim_bwd": [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i32, i32, i32, i32, f64, vp, i64, i64, i64, i64, vp],
+    "vae_ssim_index": [vp, i32, i32, i32, i32, vp, vp],
+    "vae_recon_loss_final": [vp, i64, vp, i32, i32, i32, i32, f64, vp, i32, f32, vp, vp, vp],
     "vae_nchw_to_nhwc": [vp, i32, i32, i32, i32, vp, vp],
     "vae_nhwc_to_nchw": [vp, i32, i32, i32, vp, vp],
     "vae_sumpool2x2": [vp, i32, i32, i32, i32, vp, vp],

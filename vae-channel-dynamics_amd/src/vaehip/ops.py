@@ -1214,6 +1214,89 @@ def mse_bwd(recon: torch.Tensor, target: torch.Tensor, scale: float = 1.0) -> to
     return d
 
 
+def ssim_tile():
+    """(rows, columns) of the tile one workgroup of the SSIM kernels covers (window positions forward, pixels backward)"""
+    return lib.query("vae_ssim_tile", 0), lib.query("vae_ssim_tile", 1)
+
+
+def _ssim_pair(who: str, pred: torch.Tensor, target: torch.Tensor):
+    """checks of a (B, C, H, W) fp32 pair for the SSIM kernels (any strides), before anything is allocated"""
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"{who}: expected two (B, C, H, W) tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"{who}: expected float32 tensors, got {pred.dtype} and {target.dtype}")
+    if not (pred.is_cuda and target.is_cuda and pred.device == target.device):
+        raise ValueError(f"{who}: expected two tensors on one GPU, got {pred.device} and {target.device}")
+    B, Cc, H, W = pred.shape
+    if B < 1 or Cc < 1 or H < 11 or W < 11:
+        raise ValueError(f"{who}: {tuple(pred.shape)}: needs B >= 1, C >= 1 and images of at least 11 x 11 (the SSIM window)")
+    npart, nmaps = C.c_int64(0), C.c_int64(0)
+    lib.call("vae_ssim_workspace", B, Cc, H, W, C.byref(npart), C.byref(nmaps))
+    return B, Cc, H, W, npart.value, nmaps.value
+
+
+def ssim_index(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """float64 [B]: per image the mean SSIM index of (pred + 1) / 2 against (target + 1) / 2, NOT clamped (the training term of
+    vaehip.losses; image_metrics clamps), 11 x 11 gaussian window, positions wholly inside the image.  fp32 (B, C, H, W) tensors
+    with any strides, read in place; float64 throughout; nothing synchronises the host."""
+    B, Cc, H, W, npart, _ = _ssim_pair("ssim_index", pred, target)
+    part = torch.empty((npart,), device=pred.device, dtype=torch.float64)
+    out = torch.empty((B,), device=pred.device, dtype=torch.float64)
+    lib.call("vae_ssim_fwd", _p(pred), *pred.stride(), _p(target), *target.stride(), B, Cc, H, W, _p(part), None, _stream())
+    lib.call("vae_ssim_index", _p(part), B, Cc, H, W, _p(out), _stream())
+    return out
+
+
+def recon_loss(recon: torch.Tensor, target: torch.Tensor, kl_partial: torch.Tensor, kl_weight: float, spec, grad_scale: float = 1.0,
+               want_grad: bool = True, layout: str = "nhwc"):
+    """the reconstruction loss `spec` (vaehip.losses.ReconLoss) of two contiguous fp32 tensors of one shape, with the KL partials
+    of sample_kl -> (scalars [3] = rec, kl, total; terms [2] = pixel term, SSIM index (NaN without an SSIM term);
+    drecon = grad_scale * d rec / d recon, or None when want_grad is False).  With an SSIM term the tensors are 4-D images,
+    [B, H, W, C] as the engine holds them (layout "nhwc") or [B, C, H, W] ("nchw").  csrc/recon_loss.hip: float64 sums, no atomics."""
+    if tuple(recon.shape) != tuple(target.shape) or recon.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"recon_loss: expected two float32 tensors of one shape, got {tuple(recon.shape)} {recon.dtype} and "
+                         f"{tuple(target.shape)} {target.dtype}")
+    if not (recon.is_cuda and target.is_cuda and recon.device == target.device and kl_partial.device == recon.device):
+        raise ValueError(f"recon_loss: expected tensors on one GPU, got {recon.device}, {target.device} and {kl_partial.device}")
+    if not (recon.is_contiguous() and target.is_contiguous()) or recon.numel() < 1:
+        raise ValueError("recon_loss: expected contiguous, non-empty tensors")
+    if kl_partial.dim() != 2 or kl_partial.dtype != torch.float32 or not kl_partial.is_contiguous() or kl_partial.numel() < 1:
+        raise ValueError(f"recon_loss: kl_partial must be a contiguous float32 [B, blocks] tensor, got {tuple(kl_partial.shape)}")
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"recon_loss: layout {layout!r}: expected 'nhwc' or 'nchw'")
+    n = recon.numel()
+    B, kb = kl_partial.shape
+    dev = recon.device
+    ssim = spec.ssim_weight > 0.0
+    if ssim:
+        if recon.dim() != 4 or recon.shape[0] != B:
+            raise ValueError(f"recon_loss: an SSIM term needs 4-D images with the batch of kl_partial ({B}), got {tuple(recon.shape)}")
+        pv, tv = (recon.permute(0, 3, 1, 2), target.permute(0, 3, 1, 2)) if layout == "nhwc" else (recon, target)
+        _, Cc, H, W, npart, nmaps = _ssim_pair("recon_loss", pv, tv)
+    s = _stream()
+    part = torch.empty((lib.query("vae_pixel_loss_blocks", n),), device=dev, dtype=torch.float64)
+    d = torch.empty_like(recon) if want_grad else None
+    sc = torch.empty((3,), device=dev, dtype=torch.float32)
+    terms = torch.empty((2,), device=dev, dtype=torch.float32)
+    _timed("pixel_loss_kernel", 0.0, 0.0, "vae_pixel_loss", _p(recon), _p(target), n, spec.kind_id, float(spec.huber_delta),
+           float(grad_scale), _p(part), _p(d), s)
+    spart = None
+    if ssim:
+        spart = torch.empty((npart,), device=dev, dtype=torch.float64)
+        maps = torch.empty((nmaps,), device=dev, dtype=torch.float64) if want_grad else None
+        _timed("ssim_fwd_kernel", 0.0, 0.0, "vae_ssim_fwd", _p(pv), *pv.stride(), _p(tv), *tv.stride(), B, Cc, H, W, _p(spart),
+               _p(maps), s)
+        if want_grad:
+            dv = d.permute(0, 3, 1, 2) if layout == "nhwc" else d
+            _timed("ssim_bwd_kernel", 0.0, 0.0, "vae_ssim_bwd", _p(pv), *pv.stride(), _p(tv), *tv.stride(), _p(maps), B, Cc, H, W,
+                   float(grad_scale) * float(spec.ssim_weight), _p(dv), *dv.stride(), s)
+    else:
+        Cc = H = W = 0
+    _timed("recon_final_kernel", 0.0, 0.0, "vae_recon_loss_final", _p(part), n, _p(spart), B, Cc, H, W, float(spec.ssim_weight),
+           _p(kl_partial), kb, float(kl_weight), _p(sc), _p(terms), s)
+    return sc, terms, d
+
+
 def add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a + b; two bf16 tensors (or a mixed pair, brought to bf16) give a bf16 sum rounded once from the fp32 sum"""
     if a.dtype == torch.bfloat16 or b.dtype == torch.bfloat16:

@@ -10,6 +10,7 @@ import torch.distributed as dist
 
 from . import ops
 from .dp import GradBucketReducer, allreduce_mean_, broadcast_params
+from .losses import as_spec
 from .optim import FusedAdamW
 from .trainable import apply_trainable, span_of
 
@@ -35,13 +36,19 @@ class HipTrainer:
                  kl_weight=1e-6, lr_warmup_steps=100, max_train_steps=1000, scheduler_steps_per_update: int = 1,
                  bucket_mb: float = 64.0, generator: Optional[torch.Generator] = None, mixed_precision: str = "no",
                  gradient_accumulation_steps: int = 1, checkpoint_decoder: bool = False, time_comm: bool = False,
-                 one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999, trainable=None):
-        """trainable: None (requires_grad as the user left it, read now), 'all', 'decoder', 'encoder' or a list of module-name
+                 one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999, trainable=None,
+                 recon_loss=None):
+        """recon_loss: a vaehip.losses.ReconLoss (None: the reference's MSE), the reconstruction term of every train_step;
+        eval_step keeps the reference's MSE.
+        trainable: None (requires_grad as the user left it, read now), 'all', 'decoder', 'encoder' or a list of module-name
         prefixes (vaehip.trainable); change it later with set_trainable()."""
         self.wrapper = wrapper
         self.vae = wrapper.vae
         apply_trainable(self.vae, trainable)
         self.kl_weight = float(kl_weight)
+        self.recon_loss = as_spec(recon_loss)
+        # the default spec makes the call the step always made
+        self._loss_kw = {} if self.recon_loss.is_default else {"recon_loss": self.recon_loss}
         self.generator = generator
         self.vae.engine.set_precision(mixed_precision)
         self.vae.engine.checkpoint_decoder = bool(checkpoint_decoder)
@@ -123,7 +130,8 @@ class HipTrainer:
             self.reducer.begin()
             eng.reducer = self.reducer
         try:
-            res = eng.forward_backward(pixel_values, eps, self.kl_weight, True, self.generator, grad_scale=1.0 / self.accum_steps)
+            res = eng.forward_backward(pixel_values, eps, self.kl_weight, True, self.generator, grad_scale=1.0 / self.accum_steps,
+                                       **self._loss_kw)
         finally:
             eng.reducer = None
         grad = self.vae.arena.grad
@@ -164,7 +172,7 @@ class HipTrainer:
                 self.reducer.begin()
                 eng.reducer = self.reducer
             try:
-                res = eng.forward_backward(pixel_values, eps, self.kl_weight, True, self.generator)
+                res = eng.forward_backward(pixel_values, eps, self.kl_weight, True, self.generator, **self._loss_kw)
             finally:
                 eng.reducer = None
             if self.exchanging:
