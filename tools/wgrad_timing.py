@@ -1,7 +1,9 @@
 """Where a step of the fp32 Winograd weight gradient (csrc/wgrad3_wino.hip) spends its time: shader-clock stamps of waves 0 and 4
 (the two waves of SIMD 0) of workgroups 0..7 for steps 2..9, instrumented build (`make -C csrc timing`, loaded through
 VAEHIP_LIB; `make timing TIMING_FLAGS=-DVAE_WGRAD_DEFER=0 TIMING_LIB=libvaehip_timing_d0.so` for all waves on one program).
-Per step a wave owes 32 v_mfma_f32_32x32x2_f32 of 64 cycles = 2048 cycles of matrix work, a SIMD 4096.  Segments per step:
+Per step a wave of the exact loop (-DVAE_WGRAD_X3=0) owes 32 v_mfma_f32_32x32x2_f32 of 64 cycles = 2048 cycles of matrix work, a SIMD
+4096; in the split-bf16 loop a step is a PAIR of units, 48 v_mfma_f32_32x32x16_bf16 of 32 cycles = 1536 per wave, 3072 per SIMD,
+and nothing is held back (`held` reads zero).  Segments per step:
   held   the MFMAs held back from the step before (waves 4..7 only; 0 in waves 0..3)
   head   LDS reads and operand building up to the first own MFMA (waves 0..3: their LDS stores of the next unit included)
   mfma   first to last own MFMA issued, operand building of the later blocks interleaved
@@ -73,7 +75,7 @@ def main():
         if not t[:, :, 0].any():
             sys.exit(f"no stamps: {LIB_PATH} is not an instrumented build (make -C csrc timing)")
         units = B * (H // 2) * (H // 16)
-        print(f"Cin {Ci} Cout {Co} {H}x{H} batch {B}: nsplit {ns.value}, {units // ns.value} steps per workgroup, {e0.elapsed_time(e1):.3f} ms", flush=True)
+        print(f"Cin {Ci} Cout {Co} {H}x{H} batch {B}: nsplit {ns.value}, {units // ns.value} units per workgroup, {e0.elapsed_time(e1):.3f} ms", flush=True)
         seg = np.zeros((8, 2, 5))
         per, both = np.zeros(8), np.zeros(8)
         for wg in range(8):

@@ -24,6 +24,35 @@ __device__ __forceinline__ f32x4 unpack4(uint2 r) {
   v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
   return v;
 }
+// Split-bf16 ("x3") operands: an fp32 value a as three bf16 planes
+//   hi = bf16(a), mid = bf16(a - hi), lo = bf16((a - hi) - mid)      (round to nearest even; both subtractions are exact in fp32)
+// so that hi + mid + lo = a up to 2^-26 |a|.  About 5.5 vector instructions per value.  Used by the flat fp32 kernels (igemm.hip,
+// F32X3: planes staged in LDS) and by the Winograd weight gradient (wgrad3_wino.hip: planes built in registers).
+// (pack4 as two 2-wide conversions: element by element, hipcc converts one pair of the four singly and merges it with a v_perm_b32)
+__device__ __forceinline__ uint2 pack4_pairs(f32x4 v) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const f32x2_t a = {v[0], v[1]}, b = {v[2], v[3]};
+  return uint2{__builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2_t)), __builtin_bit_cast(unsigned, __builtin_convertvector(b, bf16x2_t))};
+}
+__device__ __forceinline__ void split3(f32x4 v, uint2& hi, uint2& mid, uint2& lo) {
+  hi = pack4_pairs(v);
+  const f32x4 h = unpack4(hi);
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = v[e] - h[e];
+  mid = pack4_pairs(r);
+  const f32x4 m = unpack4(mid);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = r[e] - m[e];
+  lo = pack4_pairs(r);
+}
+// A product a.b of split operands is the sum of the six plane products that are not below 2^-24 |a.b|, added into the fp32
+// accumulator smallest first: term t = 0..5 is hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi (planes 0 = hi, 1 = mid, 2 = lo)
+__device__ __forceinline__ f32x16 mma_x3_term(int t, const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 acc) {
+  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t]], b[PB[t]], acc, 0, 0, 0);
+}
 // 4 consecutive elements of an operand stored as fp32 or bf16, through a buffer descriptor whose range is in BYTES of that
 // storage.  ONE instruction for both storages -- a 16-byte load at element offset `eoff` (a bf16 operand's load also brings the
 // next 4 elements along, unused) -- and the conversion happens where the value is CONSUMED (raw4_to_f32 at the LDS write a

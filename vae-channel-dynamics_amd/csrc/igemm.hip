@@ -239,18 +239,11 @@ struct F32X3 : F32 {
   static constexpr bool LDS_DYNAMIC = true;
 
   static __device__ __forceinline__ void put4(elem* d, f32x4 v, int ps) {
-    const uint2 hi = pack4(v);
-    const f32x4 h = unpack4(hi);
-    f32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = v[e] - h[e];
-    const uint2 mid = pack4(r);
-    const f32x4 m = unpack4(mid);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = r[e] - m[e];
+    uint2 hi, mid, lo;
+    split3(v, hi, mid, lo);  // (bf16_frag.h)
     *reinterpret_cast<uint2*>(d) = hi;
     *reinterpret_cast<uint2*>(d + ps) = mid;
-    *reinterpret_cast<uint2*>(d + 2 * ps) = pack4(r);
+    *reinterpret_cast<uint2*>(d + 2 * ps) = lo;
   }
   static __device__ __forceinline__ void put4_stored(elem* d, raw4, f32x4 v, bool, int ps) { put4(d, v, ps); }
   static __device__ __forceinline__ frag frag_k(const elem* p, int ps) {
@@ -273,17 +266,15 @@ struct F32X3 : F32 {
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) b[ni] = frag_t(sB, ldB, kg, l, colB + ni * 32, psB);
   }
-  // term by term over the wave tile (the accumulators alternate), smallest terms first: hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi
+  // term by term over the wave tile (the accumulators alternate), smallest terms first (mma_x3_term, bf16_frag.h)
   template <int MI, int NI>
   static __device__ __forceinline__ void mma(f32x16 (&acc)[MI][NI], const frag* a, const frag* b) {
-    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].p[PA[t]], b[ni].p[PB[t]], acc[mi][ni], 0, 0, 0);
+        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = mma_x3_term(t, a[mi].p, b[ni].p, acc[mi][ni]);
   }
 };
 
