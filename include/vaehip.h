@@ -122,7 +122,7 @@ typedef struct vae_igemm_args {
   int32_t gstat_groups;  /* ws[b][chunk][gstat_groups][2] = (mean, M2) per output tile -- the layout
                           * vae_gn_stats_partial writes, so vae_gn_stats_final finishes it; saves re-reading the output */
   const float* Wu;       /* optional (prec == F32, vae_wino_ok(a)): the Winograd-transformed weights vae_wino_weights(a, Wu) built from
-                          * W; the 3x3 stride-1 layer then runs as F(2x2,3x3): 16 instead of 36 multiplications per 2x2 outputs */
+                          * W (vae_wino_weight_bytes(a) bytes: fp32 values or bf16 planes, as the serving kernel reads them); the 3x3 stride-1 layer then runs as F(2x2,3x3): 16 instead of 36 multiplications per 2x2 outputs */
   /* storage of the operands in bf16 mode (all zero = fp32 everywhere); vae_conv_io16_ok(a) tells whether the kernel that
    * serves `a` honours the combination that is set:                                                                      */
   int32_t out_bf16;      /* C is a bf16 tensor (2 B per element, same [m][ldc] layout); bias / res / gstat / c_step apply as ever
@@ -152,13 +152,17 @@ int vae_conv_gstat_chunks(const vae_igemm_args* a);
 /* Winograd minimal filtering, fp32 forward / dgrad of plain 3x3 stride-1 layers: F(4x4,3x3) (csrc/conv3_wino4.hip: 36 positions)
  * where the maps are whole 16 x 32 tiles and N whole 64-channel blocks (and option "no_wino4" is off), else F(2x2,3x3)
  * (csrc/conv3_wino.hip: 16 positions); 9 positions for the upsampler geometries (csrc/conv3_upwino.hip).  vae_wino_ok: 1 when the
- * layer `a` describes (a->Wu ignored) is served; vae_wino_weight_floats: size of the transformed weights for THAT kernel
- * (36, 16 or 9 x N * K floats: always ask, never assume); vae_wino_weights: U = G g G^T of a->W (the dgrad geometry rotates and
- * transposes), layout [K/8][positions][N][8], into Wu.  The weights are transformed per launch because they are live
+ * layer `a` describes (a->Wu ignored) is served; vae_wino_weight_floats: number of transformed weights for THAT kernel
+ * (36, 16 or 9 x N * K values); vae_wino_weight_bytes: the bytes Wu must hold for them (always ask, never assume: 4 per value
+ * where the kernel reads fp32 U, layout [K/8][positions][N][8]; the upsampler kernel reads U as three bf16 planes per value,
+ * layout [ceil(K/16)][9][3][N][16] with K padded by zero planes: 6 * 9 * N * roundup16(K) bytes); vae_wino_weights: U = G g G^T
+ * of a->W (the dgrad geometry rotates and transposes) in the serving kernel's layout into Wu (16-byte aligned,
+ * vae_wino_weight_bytes(a) bytes; an opaque image: only vae_igemm_rows under the same options reads it).  The weights are transformed per launch because they are live
  * (optimizer step, in-place nudges).  Accuracy against a float64 convolution, worst element relative to the tensor's max:
  * F(2x2) 1e-6, F(4x4) 1-2e-5 (tools/wino4_accuracy.py). */
 int vae_wino_ok(const vae_igemm_args* a);
 int64_t vae_wino_weight_floats(const vae_igemm_args* a);
+int64_t vae_wino_weight_bytes(const vae_igemm_args* a);
 int vae_wino_weights(const vae_igemm_args* a, float* Wu, void* stream);
 /* 1 when the kernel that would serve `a` honours a->out_bf16 / a->a_bf16 / a->res_bf16 exactly as they are set (with all
  * three zero: always 1).  The bf16 flat kernels take any combination; the halo-tile kernels bf16 outputs with a residual of

@@ -156,7 +156,7 @@ def _open(path):
     lib.load()  # (one HIP runtime per process: the package's loader opens torch's copy first)
     dll = C.CDLL(os.path.abspath(path))
     ia, wa, vp = C.POINTER(IgemmArgs), C.POINTER(WgradArgs), C.c_void_p
-    for fn, res, argt in (("vae_igemm_rows", C.c_int, [ia, vp]), ("vae_wino_ok", C.c_int, [ia]), ("vae_wino_weight_floats", C.c_int64, [ia]),
+    for fn, res, argt in (("vae_igemm_rows", C.c_int, [ia, vp]), ("vae_wino_ok", C.c_int, [ia]), ("vae_wino_weight_bytes", C.c_int64, [ia]),
                           ("vae_wino_weights", C.c_int, [ia, vp, vp]), ("vae_conv_gstat_chunks", C.c_int, [ia]), ("vae_conv_gnb_chunks", C.c_int, [ia]),
                           ("vae_igemm_kernel_name", C.c_int, [ia, C.c_char_p, C.c_int32]), ("vae_wgrad_wino", C.c_int, [wa, vp]),
                           ("vae_wgrad_wino_plan", C.c_int, [wa, C.POINTER(C.c_int32)]), ("vae_wgrad_wino_positions", C.c_int, [wa]),
@@ -222,7 +222,7 @@ class Case:
         out = torch.full(oshape, nan, device=dev)
         a.A, a.W, a.C = _p(src), _p(self.w), _p(out)
         assert dll.vae_wino_ok(C.byref(a)), "no Winograd kernel for this case"
-        wu = torch.full((int(dll.vae_wino_weight_floats(C.byref(a))),), nan, device=dev)
+        wu = torch.full(((int(dll.vae_wino_weight_bytes(C.byref(a))) + 3) // 4,), nan, device=dev)
         assert dll.vae_wino_weights(C.byref(a), _p(wu), st) == 0
         outs = {"out": out, "U": wu}
         a.Wu = _p(wu)  # (the epilogue queries below are about the kernel the transformed weights select)
@@ -739,7 +739,7 @@ def stream_main(arg, names, paths):
         d = C.CDLL(os.path.abspath(s))
         d.vae_last_error.restype = C.c_char_p
         for fn, argt in SIGNATURES.items():
-            getattr(d, fn).restype, getattr(d, fn).argtypes = (C.c_int64 if fn == "vae_wino_weight_floats" else C.c_int), argt
+            getattr(d, fn).restype, getattr(d, fn).argtypes = (C.c_int64 if fn in ("vae_wino_weight_floats", "vae_wino_weight_bytes") else C.c_int), argt
         dlls.append(d)
     rows, launched, all_equal = [], set(), True
     try:

@@ -27,7 +27,8 @@ __device__ __forceinline__ f32x4 unpack4(uint2 r) {
 // Split-bf16 ("x3") operands: an fp32 value a as three bf16 planes
 //   hi = bf16(a), mid = bf16(a - hi), lo = bf16((a - hi) - mid)      (round to nearest even; both subtractions are exact in fp32)
 // so that hi + mid + lo = a up to 2^-26 |a|.  About 5.5 vector instructions per value.  Used by the flat fp32 kernels (igemm.hip,
-// F32X3: planes staged in LDS) and by the Winograd weight gradient (wgrad3_wino.hip: planes built in registers).
+// F32X3: planes staged in LDS), by the Winograd weight gradient (wgrad3_wino.hip: planes built in registers) and by the upsampler
+// convolution (conv3_upwino.hip: V planes staged in LDS, U planes written by its weights kernel).
 // (pack4 as two 2-wide conversions: element by element, hipcc converts one pair of the four singly and merges it with a v_perm_b32)
 __device__ __forceinline__ uint2 pack4_pairs(f32x4 v) {
   typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -46,6 +47,16 @@ __device__ __forceinline__ void split3(f32x4 v, uint2& hi, uint2& mid, uint2& lo
 #pragma unroll
   for (int e = 0; e < 4; ++e) r[e] = r[e] - m[e];
   lo = pack4_pairs(r);
+}
+// the same split of two values (one v_cvt_pk_bf16_f32 per plane): planes as bf16 pairs, a in the low half
+__device__ __forceinline__ void split3_pair(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const auto pk = [](float x, float y) { const f32x2_t v = {x, y}; return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t)); };
+  hi = pk(a, b);
+  const float ra = a - __builtin_bit_cast(float, hi << 16), rb = b - __builtin_bit_cast(float, hi & 0xffff0000u);
+  mid = pk(ra, rb);
+  lo = pk(ra - __builtin_bit_cast(float, mid << 16), rb - __builtin_bit_cast(float, mid & 0xffff0000u));
 }
 // A product a.b of split operands is the sum of the six plane products that are not below 2^-24 |a.b|, added into the fp32
 // accumulator smallest first: term t = 0..5 is hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi (planes 0 = hi, 1 = mid, 2 = lo)

@@ -1,6 +1,9 @@
 // fp32 forward and dgrad of an Upsample2D block's convolution, conv3x3(nearest_upsample_2x(x)), as a Winograd-type minimal
 // filtering scheme with 9 multiplications per LOW-resolution pixel and channel pair (direct: 36; the four 2x2 phase
-// convolutions of round 1: 16).  Exact fp32 products on v_mfma_f32_32x32x2_f32 like every fp32 contraction here.
+// convolutions of round 1: 16).  Two loops, chosen at build time (VAE_UPW_X3): split-bf16 products on v_mfma_f32_32x32x16_bf16,
+// 16 channels per step, both operands arriving as ready bf16 planes (the default; described in front of that kernel below), or
+// exact fp32 products on v_mfma_f32_32x32x2_f32, 8 channels per step (-DVAE_UPW_X3=0, make upw_x3_off; the "Kernel" paragraph
+// below describes it; transforms, tile mapping, seating of the ninth position and the epilogue are the same in both).
 //
 // Forward.  The 2x2 outputs of low-resolution pixel (i, j) see, through F(2x2, 3x3), the 4x4 patch of the upsampled image with
 // origin (2i-1, 2j-1): its rows are x[i-1], x[i], x[i], x[i+1] -- rows (and columns) repeat in pairs, so row 2 of B^T d
@@ -25,6 +28,10 @@
 // workgroups, 2, 3 in odd ones: wave k of a workgroup runs on SIMD k % 4), so a workgroup loads the SIMDs 20 20 16 16 MFMAs per
 // step and two co-resident workgroups 36 each.  (A first version with one position per wave and 9 waves put three waves of
 // every workgroup on SIMD 0: 0.46 of the matrix peak.)
+//
+// Non-finite operands under the split build (the policy of the flat kernels' F32X3, igemm.hip): Inf and NaN stay non-finite
+// (the hi plane carries them, the residual planes become NaN), and a finite value in the top 2^-8 of the fp32 range, which
+// rounds to Inf in bf16, behaves like Inf.  Every output whose window contains such a value is non-finite; no other is.
 #include "wino_common.h"
 #include <type_traits>
 #include <algorithm>
@@ -35,22 +42,35 @@
 #ifndef VAE_UPW_PRIO
 #define VAE_UPW_PRIO 1
 #endif
+// U images up to this many bytes put the channel blocks of a spatial tile on one XCD (wino::xcd_spatial): of the step's layers the
+// 256-channel one (2.4 MB as fp32, 3.5 MB as planes)
+#ifndef VAE_UPW_XCD_LIMIT
+#define VAE_UPW_XCD_LIMIT (4 << 20)
+#endif
+#ifndef VAE_UPW_X3
+#define VAE_UPW_X3 1  // 1: split-bf16 products from bf16 planes of U and V, 16 channels per step; 0: exact fp32 products, 8 channels per step (make upw_x3_off)
+#endif
+#if VAE_UPW_X3
+#include "bf16_frag.h"
+#endif
 
 namespace {
 
 constexpr int UTH = 4, UTW = 8;            // low-resolution pixels (= Winograd tiles) per workgroup tile
 constexpr int UTL = UTH * UTW;             // 32
 static_assert(UTL == wino::TILES, "spill_acc");
-constexpr int UBK = 8;                     // channels per step
 constexpr int NPOS = 9;
 constexpr int UNT = 512;                   // 8 waves
 constexpr int UNB = 2;                     // 32-channel blocks per workgroup
-constexpr int USV = NPOS * UTL * UBK;      // floats per V buffer (9216 B)
 constexpr int UHF = (UTH + 2) * (UTW + 2); // forward halo pixels (6 x 10)
 constexpr int UHD = (2 * UTH + 2) * (2 * UTW + 2);  // dgrad halo pixels (10 x 18)
-constexpr int USH = UHD * UBK;             // floats per halo buffer (sized for the dgrad)
 constexpr int UMLD = 33;                   // epilogue image row (floats)
 constexpr int USM = NPOS * UTL * UMLD;     // epilogue image, overlays the V / halo buffers
+
+#if !VAE_UPW_X3  // ---- exact fp32 products: 8 channels per step ----
+constexpr int UBK = 8;                     // channels per step
+constexpr int USV = NPOS * UTL * UBK;      // floats per V buffer (9216 B)
+constexpr int USH = UHD * UBK;             // floats per halo buffer (sized for the dgrad)
 constexpr int UP_LDS = (USM > 2 * USV + 2 * USH ? USM : 2 * USV + 2 * USH) * 4;  // 38016 B
 
 // U[pos = a*3+b][n][k] = (G' g G'^T)[a][b] for g = W[n][.][.][k] (forward: N = Cout, K = Cin) or g = rot180(W[k][.][.][n]) (dgrad:
@@ -307,6 +327,331 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   }
 }
 
+#else  // ---- VAE_UPW_X3: split-bf16 products, 16 channels per step ----
+// v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate; a product formed as the six plane products of mma_x3_term (bf16_frag.h) on
+// v_mfma_f32_32x32x16_bf16 keeps the matrix pipe busy 2.67x shorter (12 MFMAs of 32 cycles per wave and 16 channels, 18 on the waves
+// with a ninth-position block, against 16 / 24 of 64 cycles).  Both operands arrive as ready planes, so the loop itself splits nothing:
+//   * V: the V-role threads (0..255: tile, channel PAIR of the 16-channel chunk) transform in fp32 exactly as the exact loop does,
+//     split once (split3_pair) and write three plane images [plane][9][32 tiles][16] bf16 into LDS: one split per value, shared by
+//     the workgroup's 64 output channels.  A row is 32 bytes; its two 16-byte halves are swapped in rows with (tile >> 3) & 1 set,
+//     which makes the A fragment one conflict-free ds_read_b128 per plane (the 16-lane groups of that instruction otherwise meet
+//     rows 12-15 and 20-23 on the same banks).
+//   * U: upwino_weights_kernel writes [ceil(K/16)][9][3 planes][N][16] bf16 (vae_wino_weight_bytes: 6 bytes per value); lane (r, h)
+//     reads n = r, k = 8h .. 8h+7 of a plane with one 16-byte load, L2 -> registers one step ahead, as in the exact loop.
+//   * K % 16 == 8: channels >= K of the last chunk are zero planes in U AND zero in V (the halo loads of that channel octet are
+//     masked: with Cs > K the memory behind channel K holds anything, and 0 x NaN is NaN).
+// Halo staging (two f32x4 per staging thread and chunk), the two copies of the loop, one barrier per step, the seating of the
+// ninth position and the epilogue are the exact loop's.  LDS: two V buffers 55,296 B + two halo buffers (forward 7,680 B, dgrad
+// 23,040 B): two workgroups per CU in both instantiations.
+constexpr int XBK = 16;                    // channels per step
+constexpr int XPL = NPOS * UTL * XBK;      // bf16 per V plane (9216 B)
+constexpr int XSV = 3 * XPL;               // bf16 per V buffer (27,648 B)
+template <bool DG>
+constexpr int upw_lds_bytes() {
+  constexpr int used = 2 * XSV * 2 + 2 * (DG ? UHD : UHF) * XBK * 4;
+  return used > USM * 4 ? used : USM * 4;
+}
+extern __shared__ __attribute__((aligned(16))) float upw_lds[];
+
+__host__ __device__ __forceinline__ int upw_chunks(int K) { return (K + XBK - 1) / XBK; }
+// bytes of one plane of one position of one chunk ([N][16] bf16), and of the whole image
+__host__ __device__ __forceinline__ unsigned upw_plane_bytes(int N) { return (unsigned)N * (XBK * 2u); }
+__host__ __device__ __forceinline__ size_t upw_u_bytes(int K, int N) { return (size_t)upw_chunks(K) * NPOS * 3 * upw_plane_bytes(N); }
+
+// (G' g G'^T) of the 3x3 kernel g, G' = [1 0 0; 1 1 1; 0 0 1]: o[a * 3 + b]
+__device__ __forceinline__ void upw_u_transform(const float (&g)[3][3], float (&o)[9]) {
+  float t[3][3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    t[0][b] = g[0][b];
+    t[1][b] = (g[0][b] + g[2][b]) + g[1][b];
+    t[2][b] = g[2][b];
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    o[a * 3 + 0] = t[a][0];
+    o[a * 3 + 1] = (t[a][0] + t[a][2]) + t[a][1];
+    o[a * 3 + 2] = t[a][2];
+  }
+}
+
+// U planes of (n, k), k < roundup16(K): split3 of (G' g G'^T)[a][b] (g as in the exact build), zero planes for k >= K
+__global__ __launch_bounds__(256) void upwino_weights_kernel(const float* __restrict__ W, int N, int K, int dgrad, int64_t sn, int64_t sk, int64_t st,
+                                                             u16* __restrict__ U) {
+  const int K16 = upw_chunks(K) * XBK;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)N * K16) return;
+  const int k = (int)(i % K16), n = (int)(i / K16);
+  float u[9];
+  if (k < K) {
+    float g[3][3];
+    wino::u_gather(W, n, k, dgrad, sn, sk, st, g);
+    upw_u_transform(g, u);
+  } else {
+#pragma unroll
+    for (int pos = 0; pos < 9; ++pos) u[pos] = 0.f;
+  }
+  u16* o = U + ((int64_t)(k >> 4) * NPOS * 3 * N + n) * XBK + (k & 15);
+#pragma unroll
+  for (int pos = 0; pos < 9; ++pos) {
+    unsigned hi, mid, lo;
+    split3_pair(u[pos], 0.f, hi, mid, lo);
+    o[(int64_t)(pos * 3 + 0) * N * XBK] = (u16)hi;
+    o[(int64_t)(pos * 3 + 1) * N * XBK] = (u16)mid;
+    o[(int64_t)(pos * 3 + 2) * N * XBK] = (u16)lo;
+  }
+}
+
+template <bool DG>
+__global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, const u16* __restrict__ U, int tiles_x, int tiles_y, int xcd_sp) {
+  constexpr int WBN = 32 * UNB;           // output channels per workgroup
+  constexpr int HW_ = DG ? 2 * UTW + 2 : UTW + 2;  // halo width in pixels
+  constexpr int HP = DG ? UHD : UHF;      // halo pixels
+  constexpr int XSH = HP * XBK;           // floats per halo buffer
+  u16* const sV = reinterpret_cast<u16*>(upw_lds);                 // [2][3 planes][9][32 tiles][16]
+  float* const sH = upw_lds + XSV;                                 // [2][XSH], behind the 2 XSV bf16 of sV
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;  // wave = position 0..7 of the 3 x 3 transform domain
+  // position 8: channel block 0 on wave xw0, block 1 on wave xw0 + 1
+  const int xw0 = (blockIdx.x & 1) * 2;
+  const bool extra = wave == xw0 || wave == xw0 + 1;  // uniform per wave
+  const int xnb = wave - xw0;
+  const int lr = lane & 31, lh = lane >> 5;
+  const vae_conv_geom g = p.g;
+  const int tilesN = (p.N + WBN - 1) / WBN;
+  const wino::TileId wg = wino::tile_of_workgroup(blockIdx.x, tilesN, tiles_x, tiles_y, xcd_sp);
+  const int b = wg.b;
+  const int y0 = wg.ty * UTH, x0 = wg.tx * UTW, n0 = wg.tn * WBN;  // low-resolution origin of the tile
+  const int nsteps = upw_chunks(p.K);
+
+  // ---- halo role: pixel hp of the chunk's halo, channel octet hq: loaded once per chunk, stored to sH two steps ahead.  An octet
+  // at or beyond K is not loaded (zeros): K is a multiple of 8, so this is the whole K tail ----
+  const bool hrole = tid < 2 * HP;
+  const int hp = tid >> 1, hq = tid & 1;
+  const int hy = (DG ? 2 * y0 : y0) - 1 + hp / HW_, hx = (DG ? 2 * x0 : x0) - 1 + hp % HW_;
+  const bool hin = hrole && ((unsigned)hy < (unsigned)g.Hs) && ((unsigned)hx < (unsigned)g.Ws);
+  const auto rsA = VAE_BUF_RSRC(p.A + (int64_t)b * g.Hs * g.Ws * g.Cs, (size_t)g.Hs * g.Ws * g.Cs * 4u);
+  const unsigned hbase = hin ? (unsigned)(((hy * g.Ws + hx) * g.Cs + hq * 8) * 4) : BUF_OOB;
+  f32x4 rh[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  auto load_halo_into = [&](int step, f32x4 (&h)[2]) {
+    const bool ok = hin && step * XBK + hq * 8 < p.K;
+    h[0] = VAE_BUF_LOAD4(rsA, ok ? hbase + (unsigned)(step * XBK * 4) : BUF_OOB);
+    h[1] = VAE_BUF_LOAD4(rsA, ok ? hbase + (unsigned)(step * XBK * 4 + 16) : BUF_OOB);
+  };
+  auto store_halo_from = [&](float* dst, const f32x4 (&h)[2]) {
+    if (hrole) {
+      *reinterpret_cast<f32x4*>(&dst[hp * XBK + hq * 8]) = h[0];
+      *reinterpret_cast<f32x4*>(&dst[hp * XBK + hq * 8 + 4]) = h[1];
+    }
+  };
+
+  // ---- V role (threads 0..255): tile vt, channels 2 vc, 2 vc + 1 of the chunk; a plane row holds its k octets swapped when
+  // (tile >> 3) & 1 ----
+  const bool vrole = tid < 256;
+  const int vt = (tid >> 3) & 31, vc = tid & 7;
+  const int vorg = DG ? ((2 * (vt >> 3)) * HW_ + 2 * (vt & 7)) * XBK + 2 * vc : ((vt >> 3) * HW_ + (vt & 7)) * XBK + 2 * vc;
+  const int vdst = vt * XBK + (((vc >> 2) ^ ((vt >> 3) & 1)) * 8) + (vc & 3) * 2;  // inside one position of one plane
+  auto write_v = [&](const float* sHc, u16* dst) __attribute__((always_inline)) {
+    if (!vrole) return;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    constexpr int NJ = DG ? 4 : 3;
+    // one row of the transform domain at a time, written before the next is read: the whole patch of both channels would not
+    // fit beside the accumulators and the U planes (the rows' sums and differences are the exact loop's)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      // forward, L d3: d0 - d1, d1, d1 - d2;  dgrad, Bt3 d4: d0 - d2, d1 + d2, d1 - d3
+      const int ia = DG ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 1), ib = DG ? (a == 2 ? 3 : 2) : (a == 0 ? 1 : 2);
+      float r[NJ][2];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const f32x2 x = *reinterpret_cast<const f32x2*>(&sHc[vorg + (ia * HW_ + j) * XBK]);
+        if (!DG && a == 1) {
+          r[j][0] = x[0];
+          r[j][1] = x[1];
+        } else {
+          const f32x2 y = *reinterpret_cast<const f32x2*>(&sHc[vorg + (ib * HW_ + j) * XBK]);
+          const bool add = DG && a == 1;
+          r[j][0] = add ? x[0] + y[0] : x[0] - y[0];
+          r[j][1] = add ? x[1] + y[1] : x[1] - y[1];
+        }
+      }
+      float o[3][2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        if (!DG) {  // (.) L^T
+          o[0][c] = r[0][c] - r[1][c];
+          o[1][c] = r[1][c];
+          o[2][c] = r[1][c] - r[2][c];
+        } else {    // (.) Bt3^T
+          o[0][c] = r[0][c] - r[2][c];
+          o[1][c] = r[1][c] + r[2][c];
+          o[2][c] = r[1][c] - r[NJ - 1][c];
+        }
+      }
+#pragma unroll
+      for (int bb = 0; bb < 3; ++bb) {
+        const int pos = a * 3 + bb;
+        unsigned hi, mid, lo;
+        split3_pair(o[bb][0], o[bb][1], hi, mid, lo);
+        *reinterpret_cast<unsigned*>(&dst[0 * XPL + pos * UTL * XBK + vdst]) = hi;
+        *reinterpret_cast<unsigned*>(&dst[1 * XPL + pos * UTL * XBK + vdst]) = mid;
+        *reinterpret_cast<unsigned*>(&dst[2 * XPL + pos * UTL * XBK + vdst]) = lo;
+      }
+    }
+  };
+
+  // ---- U planes of this wave's position: [step][pos][plane][n0 + 32 nb + lr][8 lh .. 8 lh + 7], L2 -> registers one step ahead ----
+  const auto rsU = VAE_BUF_RSRC(U, upw_u_bytes(p.K, p.N));
+  unsigned bvo[UNB];
+#pragma unroll
+  for (int q = 0; q < UNB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? (unsigned)(((n0 + q * 32 + lr) * XBK + lh * 8) * 2) : BUF_OOB;
+  const unsigned bpl = upw_plane_bytes(p.N);
+  const unsigned bvx = extra ? bvo[xnb & 1] : BUF_OOB;  // the ninth position's block (waves without one request nothing)
+  // ONE register set, refilled behind the MFMAs that consume it (conv3_wino.hip); every step issues the same 3 (UNB + 1) requests
+  // in code every wave runs (beyond the last chunk the last one again, never used; waves without a ninth-position block request
+  // out of range)
+  bf16x8 bq[UNB + 1][3];
+  auto load_b3 = [&](int step, int i) __attribute__((always_inline)) {
+    const int st = min(step, nsteps - 1);
+    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)((st * NPOS + (i < UNB ? wave : 8)) * 3) * bpl);
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+      bq[i][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsU, i < UNB ? bvo[i < UNB ? i : 0] : bvx, so + (unsigned)pl * bpl, 0));
+  };
+
+  f32x16 acc[UNB], accx;
+#pragma unroll
+  for (int nb = 0; nb < UNB; ++nb)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[nb][e] = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) accx[e] = 0.f;
+
+  // prologue: halo(0), halo(1) in LDS, V(0) from halo(0); halo(2) and the U planes of step 0 in registers
+#pragma unroll
+  for (int i = 0; i <= UNB; ++i) load_b3(0, i);
+  {
+    f32x4 h0[2], h1[2];
+    load_halo_into(0, h0);
+    load_halo_into(1, h1);
+    load_halo_into(2, rh);
+    store_halo_from(sH, h0);
+    store_halo_from(sH + XSH, h1);
+  }
+  __syncthreads();
+  write_v(sH, sV);
+  __syncthreads();
+  const int afrag = lr * XBK + ((lh ^ ((lr >> 3) & 1)) * 8);  // this lane's 8 k of tile lr inside one position of one plane
+  auto multiply = [&](const u16* cV, int s) __attribute__((always_inline)) {  // step s; requests step s+1's planes as it goes
+    bf16x8 a[3];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) a[pl] = frag_direct(&cV[pl * XPL + wave * UTL * XBK + afrag]);
+#pragma unroll
+    for (int nb = 0; nb < UNB; ++nb) {
+#pragma unroll
+      for (int t = 0; t < 6; ++t) acc[nb] = mma_x3_term(t, a, bq[nb], acc[nb]);
+      __builtin_amdgcn_sched_barrier(0);
+      load_b3(s + 1, nb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (extra) {  // the ninth position's A planes into the set the main blocks are done with
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) a[pl] = frag_direct(&cV[pl * XPL + 8 * UTL * XBK + afrag]);
+#pragma unroll
+      for (int t = 0; t < 6; ++t) accx = mma_x3_term(t, a, bq[UNB], accx);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_b3(s + 1, UNB);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto stage_next = [&](int s, int par) __attribute__((always_inline)) {
+    store_halo_from(sH + par * XSH, rh);                                       // halo(s+2) (first: its registers are free during the transform)
+    if (s + 1 < nsteps) write_v(sH + (par ^ 1) * XSH, sV + (par ^ 1) * XSV);  // V(s+1): nobody reads that buffer now
+    load_halo_into(s + 3, rh);
+  };
+  // waves 0..3 (which own the V transform) stage first, waves 4..7 multiply first: two copies of the loop, so that the order of
+  // the memory requests is fixed inside each and hipcc's wait counts are exact (conv3_wino.hip)
+  auto step = [&](int s, int par, auto first_c) __attribute__((always_inline)) {
+    const u16* cV = sV + par * XSV;
+    if (decltype(first_c)::value) {
+      stage_next(s, par);
+      __builtin_amdgcn_sched_barrier(0);
+      multiply(cV, s);
+    } else {
+      multiply(cV, s);
+      __builtin_amdgcn_sched_barrier(0);
+      stage_next(s, par);
+    }
+    __syncthreads();
+  };
+  auto run = [&](auto first_c) __attribute__((always_inline)) {
+    int s = 0;
+    for (; s + 1 < nsteps; s += 2) {
+      step(s, 0, first_c);
+      step(s + 1, 1, first_c);
+    }
+    if (s < nsteps) step(s, 0, first_c);
+  };
+#if VAE_UPW_PRIO  // one static s_setprio around the loop; a scalar condition: the instruction ignores EXEC
+  if (DG && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
+#endif
+  if (wave < 4) run(std::true_type{});  // uniform per wave
+  else run(std::false_type{});
+#if VAE_UPW_PRIO
+  if (DG) __builtin_amdgcn_s_setprio(0);
+#endif
+
+  // ---- epilogue: per 32-channel block, M through LDS, then the output transform ----
+  // (the exact loop's text, kept apart: shared through a function, the exact build's registers moved away from the parent's)
+  float* const sM = upw_lds;  // [9][32 tiles][UMLD], over the V / halo buffers (the last step's barrier has passed)
+  const size_t obytes = (size_t)g.Ho * g.Wo * p.ldc * 4u;
+  const auto rsC = VAE_BUF_RSRC(p.C + (int64_t)b * g.Ho * g.Wo * p.ldc, obytes);
+#pragma unroll
+  for (int nb = 0; nb < UNB; ++nb) {
+    if (nb > 0) __syncthreads();  // the previous block's reads are done
+    wino::spill_acc(sM, wave, UMLD, acc[nb], lr, lh);
+    if (wave == xw0 + nb) wino::spill_acc(sM, 8, UMLD, accx, lr, lh);  // the ninth position's block nb
+    __syncthreads();
+    {
+#pragma unroll
+      for (int rnd = 0; rnd < 2; ++rnd) {
+        const int co = tid & 31, tile = (tid >> 5) + 16 * rnd;
+        const int col = n0 + nb * 32 + co;
+        float m[9];
+#pragma unroll
+        for (int pos = 0; pos < 9; ++pos) m[pos] = sM[(pos * UTL + tile) * UMLD + co];
+        const int oy = y0 + (tile >> 3), ox = x0 + (tile & 7);  // low-resolution pixel of the tile
+        if (!DG) {
+          const float bv = (p.bias && col < p.N) ? p.bias[col] : 0.f;
+          float h[2][3];  // A'^T M
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            h[0][j] = m[0 * 3 + j] + m[1 * 3 + j];
+            h[1][j] = m[1 * 3 + j] - m[2 * 3 + j];
+          }
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            const float yv[2] = {h[a][0] + h[a][1], h[a][1] - h[a][2]};
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+              const int py = 2 * oy + a, px = 2 * ox + bb;
+              const unsigned off = (col < p.N && py < g.Ho && px < g.Wo) ? (unsigned)(((py * g.Wo + px) * p.ldc + col) * 4) : BUF_OOB;
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yv[bb] + bv), rsC, off, 0, 0);
+            }
+          }
+        } else {
+          // s^T M s with s = [1 1 -1]
+          const float h0 = (m[0] + m[3]) - m[6], h1 = (m[1] + m[4]) - m[7], h2 = (m[2] + m[5]) - m[8];
+          const float v = (h0 + h1) - h2;
+          const unsigned off = (col < p.N && oy < g.Ho && ox < g.Wo) ? (unsigned)(((oy * g.Wo + ox) * p.ldc + col) * 4) : BUF_OOB;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, off, 0, 0);
+        }
+      }
+    }
+  }
+}
+#endif  // VAE_UPW_X3
+
 }  // namespace
 
 // forward (mode UP2X: source = the low-resolution x, row grid = the high-resolution output) or dgrad (mode UP2X_DGRAD: source =
@@ -325,12 +670,31 @@ bool conv3_upwino_eligible(const vae_igemm_args& a) {
   } else {
     return false;
   }
-  if (Hl % UTH != 0 || Wl % UTW != 0 || a.K % UBK != 0 || a.K < 64 || a.K > 1024 || a.N < 32 || a.N % 4 != 0 || g.Cs < a.K) return false;
+  if (Hl % UTH != 0 || Wl % UTW != 0 || a.K % 8 != 0 || a.K < 64 || a.K > 1024 || a.N < 32 || a.N % 4 != 0 || g.Cs < a.K) return false;
+#if VAE_UPW_X3
+  if (upw_u_bytes(a.K, a.N) >= BUF_MAX) return false;  // (N beyond 77,000: the plane image through one descriptor)
+#endif
   return true;
 }
 
+// bytes of the image launch_upwino_weights writes and launch_conv3_upwino reads
+int64_t conv3_upwino_weight_bytes(const vae_igemm_args& a) {
+#if VAE_UPW_X3
+  return (int64_t)upw_u_bytes(a.K, a.N);  // 6 * 9 * N * roundup16(K)
+#else
+  return (int64_t)wino::u_bytes(a.K / UBK, NPOS, a.N);
+#endif
+}
+
 int launch_upwino_weights(const vae_igemm_args& a, float* U, hipStream_t st) {
+#if VAE_UPW_X3
+  const int64_t n = (int64_t)a.N * upw_chunks(a.K) * XBK;
+  hipLaunchKernelGGL(upwino_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.W, a.N, a.K, a.g.mode == VAE_MODE_UP2X_DGRAD ? 1 : 0,
+                     a.sn, a.sk, a.st, reinterpret_cast<u16*>(U));
+  return 0;
+#else
   return wino::launch_weights(upwino_weights_kernel, a, a.g.mode == VAE_MODE_UP2X_DGRAD, U, st);
+#endif
 }
 
 int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st) {
@@ -341,9 +705,20 @@ int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st)
   const int tilesN = (a.N + 32 * UNB - 1) / (32 * UNB);
   const int64_t nt = (int64_t)tilesN * tx * ty * g.B;
   if (nt > 0x7fffffffLL) return VAE_EINVAL;
-  constexpr size_t xcd_u = (size_t)4 << 20;
-  const int xcd_sp = wino::xcd_spatial(tilesN, wino::u_bytes(a.K / UBK, NPOS, a.N), xcd_u, (int64_t)tx * ty * g.B);
+  constexpr size_t xcd_u = (size_t)VAE_UPW_XCD_LIMIT;
+  const int xcd_sp = wino::xcd_spatial(tilesN, (size_t)conv3_upwino_weight_bytes(a), xcd_u, (int64_t)tx * ty * g.B);
+#if VAE_UPW_X3  // (the dgrad's 78,336 B are more than 64 KB of dynamic LDS: reserved once per instantiation and device)
+  const u16* Up = reinterpret_cast<const u16*>(U);
+  if (dg) {
+    VAE_RESERVE_LDS(conv3_upwino_kernel<true>, upw_lds_bytes<true>(), "conv3_upwino");
+    hipLaunchKernelGGL((conv3_upwino_kernel<true>), dim3((unsigned)nt), dim3(UNT), upw_lds_bytes<true>(), st, a, Up, tx, ty, xcd_sp);
+  } else {
+    VAE_RESERVE_LDS(conv3_upwino_kernel<false>, upw_lds_bytes<false>(), "conv3_upwino");
+    hipLaunchKernelGGL((conv3_upwino_kernel<false>), dim3((unsigned)nt), dim3(UNT), upw_lds_bytes<false>(), st, a, Up, tx, ty, xcd_sp);
+  }
+#else
   if (dg) hipLaunchKernelGGL((conv3_upwino_kernel<true>), dim3((unsigned)nt), dim3(UNT), 0, st, a, U, tx, ty, xcd_sp);
   else hipLaunchKernelGGL((conv3_upwino_kernel<false>), dim3((unsigned)nt), dim3(UNT), 0, st, a, U, tx, ty, xcd_sp);
+#endif
   return 0;
 }

@@ -346,6 +346,12 @@ extern "C" int64_t vae_wino_weight_floats(const vae_igemm_args* ap) {
   const bool up = ap->g.mode == VAE_MODE_UP2X || ap->g.mode == VAE_MODE_UP2X_DGRAD;
   return (int64_t)(up ? 9 : (select_wino(*ap) == RowsKernel::Wino4 ? 36 : 16)) * ap->N * ap->K;
 }
+// bytes Wu must hold for the kernel that serves the launch: the upsampler kernel's image may be bf16 planes, 6 bytes per value
+extern "C" int64_t vae_wino_weight_bytes(const vae_igemm_args* ap) {
+  if (!ap) return 0;
+  if (select_wino(*ap) == RowsKernel::UpWino) return conv3_upwino_weight_bytes(*ap);
+  return 4 * vae_wino_weight_floats(ap);
+}
 extern "C" int vae_wino_weights(const vae_igemm_args* ap, float* Wu, void* stream) {
   VAE_CHECK(ap && Wu && ap->W && aligned16(Wu), "wino_weights: null or unaligned pointer");
   const RowsKernel k = select_wino(*ap);

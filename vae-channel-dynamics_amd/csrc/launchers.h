@@ -37,6 +37,7 @@ int conv3_wino4_gnb_chunks(const vae_igemm_args& a);
 int launch_wino4_weights(const vae_igemm_args& a, float* U, hipStream_t st);
 int launch_conv3_wino4(const vae_igemm_args& a, const float* U, hipStream_t st);
 bool conv3_upwino_eligible(const vae_igemm_args& a);
+int64_t conv3_upwino_weight_bytes(const vae_igemm_args& a);  // of its U image: fp32, or three bf16 planes (VAE_UPW_X3)
 int launch_upwino_weights(const vae_igemm_args& a, float* U, hipStream_t st);
 int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st);
 // conv1_bf16.hip: bf16 1x1 convolutions, weights resident in LDS

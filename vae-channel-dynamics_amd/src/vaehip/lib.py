@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 18  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 19  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -62,6 +62,7 @@ SIGNATURES = {
     "vae_unpack_bf16": [vp, i64, vp, vp],
     "vae_wino_ok": [C.POINTER(IgemmArgs)],
     "vae_wino_weight_floats": [C.POINTER(IgemmArgs)],
+    "vae_wino_weight_bytes": [C.POINTER(IgemmArgs)],
     "vae_wino_weights": [C.POINTER(IgemmArgs), vp, vp],
     "vae_bf16_grad_image_ok": [C.POINTER(ConvGeom), i32, i32],
     "vae_upconv_phase_weights": [vp, i32, i32, vp, vp],
@@ -168,7 +169,7 @@ class _Lib:
                                       f"{dll.vae_sizeof_args(which)} -- lib.py and include/vaehip.h are out of sync")
             for name, argt in SIGNATURES.items():
                 fn = getattr(dll, name)
-                fn.restype = C.c_int64 if name == "vae_wino_weight_floats" else C.c_int
+                fn.restype = C.c_int64 if name in ("vae_wino_weight_floats", "vae_wino_weight_bytes") else C.c_int
                 fn.argtypes = argt
             self._dll = dll
         return self._dll

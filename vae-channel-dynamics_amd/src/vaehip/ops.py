@@ -407,7 +407,8 @@ def _wino_ok(a: IgemmArgs) -> bool:
 
 def _wino_weights(a: IgemmArgs, dev):
     """transformed weights for a launch _wino_ok accepted (a.Wu is set)"""
-    wu = torch.empty((int(lib.query("vae_wino_weight_floats", C.byref(a))),), device=dev, dtype=torch.float32)
+    nbytes = int(lib.query("vae_wino_weight_bytes", C.byref(a)))  # fp32 values or bf16 planes: the serving kernel's image
+    wu = torch.empty(((nbytes + 3) // 4,), device=dev, dtype=torch.float32)
     lib.call("vae_wino_weights", C.byref(a), _p(wu), _stream())
     a.Wu = _p(wu)
     return wu
