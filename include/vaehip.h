@@ -283,6 +283,22 @@ int vae_moments_partial(const void* x, int32_t x_bf16, const float* scale, const
  * all B*HW*C elements, their unbiased (N - 1) std                                   */
 int vae_moments_final(const float* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* chan, float* out,
                       void* stream);
+/* per-channel magnitude histogram, near-zero count and max |y| of y = XF(x) in one read (monitor.py's
+ * log2_histogram_per_channel / near_zero_fraction_per_channel / abs_max_activation_per_channel), csrc/chanhist.hip.  x, x_bf16,
+ * scale, shift, xf, ld, nchunk: exactly as vae_moments_partial.  The bin of a value is clamp(floor(log2 |y|) + 31, 0, 47), from
+ * the fp32 exponent field: bin 0 = |y| < 2^-30 (zeros, denormals), bin k = [2^(k-31), 2^(k-30)), bin 47 = |y| >= 2^16, inf, NaN.
+ * vae_chanhist_bins: 48.  vae_chanhist_workspace: *nwords = 32-bit words of ws for this shape (exactly what the partial pass
+ * writes); needs no GPU.  B * HW must stay below 2^31.
+ * partial: ws [B * nchunk][C][50] = per (b, chunk, c) the 48 bin counts, the count of |y| < tau (fp32 compare; NaN is not below)
+ * and the largest |y| bit pattern; tau >= 0.  Counts are integers (LDS integer atomics inside a workgroup, plain stores to ws)
+ * final: hist [C][48] and nzero [C] = int64 sums over ws rows, absmax [C] = max |y| (NaN if the channel holds one).  No global
+ * atomics, no zero-fill: repeated launches are bitwise identical. */
+int vae_chanhist_bins(void);
+int vae_chanhist_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords);
+int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
+                         int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float tau, uint32_t* ws, void* stream);
+int vae_chanhist_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* hist, int64_t* nzero,
+                       float* absmax, void* stream);
 /* ---- image-quality metrics of a reconstruction (evaluate.py: Average MSE, PSNR, SSIM; reference src/evaluate.py:172-183,
  * torchmetrics PeakSignalNoiseRatio / StructuralSimilarityIndexMeasure), csrc/image_metrics.hip ----
  * pred, target: fp32 images of logical shape (B, C, H, W), values nominally in [-1, 1], each with its own four ELEMENT strides

@@ -23,6 +23,15 @@ four metrics from the device as well (`device_layers`): one moments vector per f
 forward after the last step() only (step() keeps only that one).  step() makes one transfer per layer and aggregates
 exactly as the hook path does; the scalars stay rank-local like the hook path's, the mean |A| vectors are averaged
 across ranks like the fused ones.
+
+Three metrics the reference does not have, valid for any layer and capture point (CHANHIST_METRICS):
+`log2_histogram_per_channel` (int64 [C][48] counts over batch and pixels, bin = clamp(floor(log2 |A|) + 31, 0, 47) from the
+fp32 exponent: bin 0 is |A| < 2^-30, bin 47 is |A| >= 2^16, inf and NaN -- what fp16 cannot hold), `abs_max_activation_per_channel`
+(fp32 [C], NaN if the channel holds one) and `near_zero_fraction_per_channel` (fp32 [C], share of |A| <
+`tracking.near_zero_threshold`, default 1e-3).  They tell a dead channel from a small one and find outlier channels without a
+full map.  Hooks compute them with torch (compute_metrics); a device-served layer gets all three from ONE ops.chanhist pass
+per forward.  step() sums the histograms over the buffered forwards, takes the maximum of the maxima and the unweighted mean
+of the fractions; device-served layers sum / max / average them across ranks as well and come to the host in one transfer.
 """
 import logging
 from collections import defaultdict
@@ -34,7 +43,14 @@ import torch
 logger = logging.getLogger(__name__)
 
 FUSED_METRIC = "mean_abs_activation_per_channel"
-KNOWN_METRICS = (FUSED_METRIC, "full_activation_map", "mean_activation", "std_activation")
+HIST_METRIC = "log2_histogram_per_channel"
+ABSMAX_METRIC = "abs_max_activation_per_channel"
+NEARZERO_METRIC = "near_zero_fraction_per_channel"
+CHANHIST_METRICS = (HIST_METRIC, ABSMAX_METRIC, NEARZERO_METRIC)
+KNOWN_METRICS = (FUSED_METRIC, "full_activation_map", "mean_activation", "std_activation") + CHANHIST_METRICS
+HIST_BINS = 48             # bin = clamp(floor(log2 |y|) + 31, 0, 47), from the fp32 exponent field
+NEAR_ZERO_THRESHOLD = 1e-3  # default of tracking.near_zero_threshold
+DEAD_FRACTION = 0.99       # a channel with at least this share of near-zero values counts as dead in the records
 
 
 def _resolve(root: torch.nn.Module, dotted: str) -> torch.nn.Module:
@@ -50,15 +66,45 @@ def _resolve(root: torch.nn.Module, dotted: str) -> torch.nn.Module:
     return cur
 
 
-def compute_metrics(tensor: torch.Tensor, metrics: List[str]) -> Dict[str, Any]:
-    """slow-path formulas, identical to monitor.py:56-80."""
+def _per_channel(tensor: torch.Tensor) -> torch.Tensor:
+    """fp32 [C, N]: the values of each channel (dim 1, as FUSED_METRIC reduces); a tensor without a channel axis is one channel"""
+    t = tensor.detach().float()
+    if t.ndim >= 2:
+        return t.transpose(0, 1).reshape(t.shape[1], -1)
+    return t.reshape(1, -1)
+
+
+def log2_bins(t32: torch.Tensor) -> torch.Tensor:
+    """bin of every fp32 value, from its exponent field E: clamp(E - 96, 0, 47) = clamp(floor(log2 |y|) + 31, 0, 47).  Bin 0:
+    |y| < 2^-30 (zeros, denormals); bin 47: |y| >= 2^16, inf, NaN (what fp16 cannot hold)"""
+    e = (t32.contiguous().view(torch.int32) >> 23) & 0xFF
+    return (e - 96).clamp_(0, HIST_BINS - 1).long()
+
+
+def _near_zero_fraction(count, n) -> np.ndarray:
+    """counts of |y| < tau over n values each -> the fp32 fraction (one rounding, of the float64 quotient)"""
+    return (np.asarray(count, dtype=np.float64) / np.asarray(n, dtype=np.float64)).astype(np.float32)
+
+
+def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshold: float = NEAR_ZERO_THRESHOLD) -> Dict[str, Any]:
+    """slow-path formulas, identical to monitor.py:56-80; the three CHANHIST_METRICS are what ops.chanhist computes."""
     out: Dict[str, Any] = {}
     if not isinstance(tensor, torch.Tensor):
         logger.warning(f"Cannot calculate metrics for non-tensor type: {type(tensor)}")
         return out
     for name in metrics:
         try:
-            if name == FUSED_METRIC:
+            if name == HIST_METRIC:
+                yc = _per_channel(tensor)
+                idx = log2_bins(yc) + torch.arange(yc.shape[0], device=yc.device)[:, None] * HIST_BINS
+                out[name] = torch.bincount(idx.flatten(), minlength=yc.shape[0] * HIST_BINS).view(-1, HIST_BINS).cpu().numpy()
+            elif name == ABSMAX_METRIC:
+                out[name] = _per_channel(tensor).abs().amax(dim=1).cpu().numpy()  # NaN propagates
+            elif name == NEARZERO_METRIC:
+                yc = _per_channel(tensor)
+                tau = torch.tensor(near_zero_threshold, dtype=torch.float32, device=yc.device)
+                out[name] = _near_zero_fraction((yc.abs() < tau).sum(dim=1).cpu().numpy(), yc.shape[1])  # NaN is not below
+            elif name == FUSED_METRIC:
                 if tensor.ndim >= 2:
                     dims = [0] + list(range(2, tensor.ndim))
                     out[name] = tensor.abs().mean(dim=dims).detach().cpu().numpy()
@@ -85,6 +131,14 @@ class _Moments:
         self.t = t
 
 
+class _ChanHist:
+    """a buffered per-forward (hist, nzero, absmax) triple of a device-served layer (ops.chanhist; resolved in step())"""
+    __slots__ = ("t",)
+
+    def __init__(self, t: tuple):
+        self.t = t
+
+
 class ActivityMonitor:
     def __init__(self, model: torch.nn.Module, tracking_config: Dict[str, Any]):
         self.model = model
@@ -97,6 +151,7 @@ class ActivityMonitor:
         self.device_layers: List[str] = []
         self.device_metrics = bool(self.config.get("device_metrics", False))
         self.sync_across_ranks = bool(self.config.get("sync_across_ranks", True))
+        self.near_zero_threshold = float(self.config.get("near_zero_threshold", NEAR_ZERO_THRESHOLD))
         if self.config.get("enabled", False):
             self._register_hooks()
             logger.info(f"ActivityMonitor initialized for {len(self.target_layers_config)} target(s) "
@@ -113,13 +168,16 @@ class ActivityMonitor:
 
     def _device_sink(self, layer_id: str, metrics: List[str]) -> Callable:
         """engine sink of a device-served layer: buffers device tensors only, one entry per metric in config order (the
-        order compute_metrics appends in); the moments vector is shared by the metrics it serves"""
-        def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor]):
+        order compute_metrics appends in); the moments vector and the histogram triple are shared by the metrics they serve"""
+        def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor], chanhist: Optional[tuple] = None):
             buf = self.hook_collected_buffer[layer_id]
+            hist = _ChanHist(chanhist) if chanhist is not None else None
             for name in metrics:
                 if name == "full_activation_map":
                     if fmap is not None:
                         buf[name].append(fmap)
+                elif name in CHANHIST_METRICS:
+                    buf[name].append(hist)
                 else:
                     buf[name].append(_Moments(mom))
         return sink
@@ -137,7 +195,7 @@ class ActivityMonitor:
             else:
                 t = hook_output
             if isinstance(t, torch.Tensor):
-                for k, v in compute_metrics(t, metrics).items():
+                for k, v in compute_metrics(t, metrics, self.near_zero_threshold).items():
                     self.hook_collected_buffer[layer_id][k].append(v)
         return fn
 
@@ -166,8 +224,9 @@ class ActivityMonitor:
                 elif self.device_metrics and engine is not None and metrics and \
                         all(m in KNOWN_METRICS for m in metrics) and engine.metric_trackable(layer):
                     mlist = list(dict.fromkeys(metrics))
+                    extra = {"near_zero_threshold": self.near_zero_threshold} if any(m in CHANHIST_METRICS for m in mlist) else {}
                     self.hooks.append(engine.add_tracker(layer, point, self._device_sink(layer_id, mlist), metrics=mlist,
-                                                         map_due=self._map_due(layer_id)))
+                                                         map_due=self._map_due(layer_id), **extra))
                     self.device_layers.append(layer_id)
                     logger.info(f"Registered DEVICE metric tracker for layer: {name} ({point}): {mlist}")
                 elif point == "input":
@@ -189,20 +248,66 @@ class ActivityMonitor:
         self.device_layers = []
 
     # ------------------------------------------------------------------ aggregation
+    def _world(self) -> int:
+        """ranks whose buffers step() combines (1 without data parallelism or with sync_across_ranks off)"""
+        if self.sync_across_ranks and torch.distributed.is_available() and torch.distributed.is_initialized():
+            return torch.distributed.get_world_size()
+        return 1
+
+    @staticmethod
+    def _same_forward_count(forwards: int, device):
+        """ranks must have buffered the same number of forwards (train.py makes them skip batches together)"""
+        n = torch.tensor([forwards, -forwards], device=device, dtype=torch.int64)
+        torch.distributed.all_reduce(n, op=torch.distributed.ReduceOp.MAX)
+        if int(n[0]) != -int(n[1]):
+            raise RuntimeError(f"ActivityMonitor: ranks buffered different numbers of forwards "
+                               f"({forwards} here, {int(n[0])} max, {-int(n[1])} min); the per-rank "
+                               f"tracker vectors cannot be averaged")
+
     def _rank_average(self, stacked: torch.Tensor) -> torch.Tensor:
         """[forwards, C] device vectors -> their average over the ranks (the identity without data parallelism)"""
-        if self.sync_across_ranks and torch.distributed.is_available() and torch.distributed.is_initialized() \
-                and torch.distributed.get_world_size() > 1:
-            # ranks must have buffered the same number of forwards (train.py makes them skip batches together)
-            n = torch.tensor([stacked.shape[0], -stacked.shape[0]], device=stacked.device, dtype=torch.int64)
-            torch.distributed.all_reduce(n, op=torch.distributed.ReduceOp.MAX)
-            if int(n[0]) != -int(n[1]):
-                raise RuntimeError(f"ActivityMonitor: ranks buffered different numbers of forwards "
-                                   f"({stacked.shape[0]} here, {int(n[0])} max, {-int(n[1])} min); the per-rank "
-                                   f"tracker vectors cannot be averaged")
+        world = self._world()
+        if world > 1:
+            self._same_forward_count(stacked.shape[0], stacked.device)
             torch.distributed.all_reduce(stacked)
-            stacked = stacked / torch.distributed.get_world_size()
+            stacked = stacked / world
         return stacked
+
+    def _chanhist_to_host(self, metric_data: Dict[str, list]):
+        """the buffered ops.chanhist triples of a layer -> per forward the host values the hook path would have buffered, in
+        place: histogram int64 [C, 48], max |A| fp32 [C], near-zero fraction fp32 [C] = count / (B * H * W).  Across ranks the
+        histograms are summed, the maxima maxed and the fractions averaged.  ONE transfer: a float64 [forwards, C, 50] tensor
+        (counts below 2^53 and fp32 values are exact in it)"""
+        rows: Dict[int, int] = {}  # id of a buffered triple -> its row
+        stack = []
+        for values in metric_data.values():
+            for v in values:
+                if isinstance(v, _ChanHist) and id(v) not in rows:
+                    rows[id(v)] = len(stack)
+                    stack.append(v.t)
+        if not stack:
+            return
+        hist = torch.stack([t[0] for t in stack])
+        count = hist[:, 0, :].sum(dim=1).double()  # B * H * W of each forward: what every row of its histogram sums to
+        frac = torch.stack([t[1] for t in stack]).double() / count[:, None]
+        amax = torch.stack([t[2] for t in stack])
+        world = self._world()
+        if world > 1:
+            self._same_forward_count(hist.shape[0], hist.device)
+            torch.distributed.all_reduce(hist)
+            # as integers the bit patterns of |A| order like the values, a NaN above every number: it survives the maximum
+            torch.distributed.all_reduce(amax.view(torch.int32), op=torch.distributed.ReduceOp.MAX)
+            torch.distributed.all_reduce(frac)
+            frac = frac / world
+        host = torch.cat([hist.double(), frac[:, :, None], amax.double()[:, :, None]], dim=2).cpu().numpy()
+        for metric, values in metric_data.items():
+            for i, v in enumerate(values):
+                if isinstance(v, _ChanHist):
+                    row = host[rows[id(v)]]
+                    if metric == HIST_METRIC:
+                        values[i] = row[:, :HIST_BINS].astype(np.int64)
+                    else:
+                        values[i] = row[:, HIST_BINS if metric == NEARZERO_METRIC else HIST_BINS + 1].astype(np.float32)
 
     def _to_host(self, values: list) -> list:
         """device vectors of the fused path -> list of np.float32 arrays with ONE transfer."""
@@ -253,6 +358,7 @@ class ActivityMonitor:
             if any(isinstance(v, _Moments) or (m == "full_activation_map" and isinstance(v, torch.Tensor) and v.is_cuda)
                    for m, values in metric_data.items() for v in values):
                 self._device_to_host(metric_data)
+            self._chanhist_to_host(metric_data)
         for layer_id, metric_data in self.hook_collected_buffer.items():
             processed[layer_id] = {}
             for metric, values in metric_data.items():
@@ -267,6 +373,16 @@ class ActivityMonitor:
                         if isinstance(arr, np.ndarray):
                             log[key + "_mean"] = np.mean(arr.astype(np.float32))
                             log[key + "_std"] = np.std(arr.astype(np.float32))
+                    elif metric == HIST_METRIC:  # summed over the buffered forwards
+                        agg = np.sum(np.stack([np.asarray(v, dtype=np.int64) for v in values]), axis=0)
+                        log[key + "_top_bin_share"] = float(agg[..., -1].sum()) / max(float(agg.sum()), 1.0)
+                    elif metric == ABSMAX_METRIC:  # the maximum over them (a NaN stays)
+                        agg = np.max(np.stack(values), axis=0)
+                        log[key + "_overall_max"] = np.max(agg)
+                    elif metric == NEARZERO_METRIC:  # the unweighted mean, like every other metric
+                        agg = np.mean(np.stack(values), axis=0)
+                        log[key + "_overall_mean"] = np.mean(agg)
+                        log[key + "_overall_max"] = np.max(agg)
                     elif FUSED_METRIC in metric:
                         vals = self._to_host(values)
                         if all(isinstance(v, np.ndarray) for v in vals):
@@ -323,6 +439,24 @@ class ActivityMonitor:
                         add("full_map_std", float(np.std(a32)))
                         add("full_map_min", float(np.min(a32)))
                         add("full_map_max", float(np.max(a32)))
+                    elif metric == HIST_METRIC:
+                        total = arr.reshape(-1, arr.shape[-1]).sum(axis=0)  # the tensor's histogram: all channels together
+                        rows = arr.reshape(-1, arr.shape[-1]).sum(axis=1)
+                        add("histogram_shape", str(arr.shape))
+                        # forwards x B*H*W: every channel's row sums to it (-1 if the rows disagree, which no path produces)
+                        add("histogram_row_total", int(rows[0]) if (rows == rows[0]).all() else -1)
+                        add("histogram_top_bin_count", int(total[-1]))
+                        add("histogram_zero_bin_count", int(total[0]))
+                        # the bin that holds the tensor's median magnitude (the lower median)
+                        add("histogram_median_bin", int(np.searchsorted(np.cumsum(total), (int(total.sum()) + 1) // 2)))
+                    elif metric == ABSMAX_METRIC:
+                        add("abs_max_overall_max", float(np.max(arr)))
+                        add("abs_max_overall_mean", float(np.mean(arr)))
+                        add("abs_max_argmax_channel", int(np.argmax(arr)))
+                    elif metric == NEARZERO_METRIC:
+                        add("near_zero_overall_mean", float(np.mean(arr)))
+                        add("near_zero_overall_max", float(np.max(arr)))
+                        add("near_zero_dead_channels", int(np.sum(arr >= DEAD_FRACTION)))
                     elif FUSED_METRIC in metric:
                         add("per_channel_overall_mean", float(np.mean(arr)))
                         add("per_channel_overall_std", float(np.std(arr)))

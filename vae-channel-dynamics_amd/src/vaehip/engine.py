@@ -8,8 +8,9 @@ never touch HBM.  The torch.nn hook protocol the reference's plugins rely on
 forward hooks gets its input/output materialised and the hooks are called synchronously;
 the shipped metric `mean_abs_activation_per_channel` (monitor.py:66) is served by fused
 device-side reductions instead (add_tracker), without any tensor or host sync.  add_tracker(metrics=...) serves any
-subset of the four ActivityMonitor metrics at a 4-D capture point the same way: one moments pass (ops.moments) per
-forward on the tensor a hook would have received, and a full-map snapshot only when the caller says one is due.
+subset of the ActivityMonitor metrics at a 4-D capture point the same way: one moments pass (ops.moments) and one
+histogram pass (ops.chanhist: magnitude histogram, near-zero count, max |A| per channel) per forward on the tensor a hook
+would have received, each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
 """
 from __future__ import annotations
 
@@ -26,7 +27,9 @@ from .ops import XF_AFFINE, XF_AFFINE_SILU, XF_NONE, Stats
 
 _TRACK_C = {4, 8, 16, 32, 64, 128, 256, 512, 1024}
 MOMENT_METRICS = ("mean_abs_activation_per_channel", "mean_activation", "std_activation")  # one ops.moments vector
-DEVICE_METRICS = MOMENT_METRICS + ("full_activation_map",)
+# one ops.chanhist pass: (histogram, near-zero count, max |y|) per channel
+CHANHIST_METRICS = ("log2_histogram_per_channel", "abs_max_activation_per_channel", "near_zero_fraction_per_channel")
+DEVICE_METRICS = MOMENT_METRICS + CHANHIST_METRICS + ("full_activation_map",)
 
 
 class _TrackHandle:
@@ -40,10 +43,13 @@ class _TrackHandle:
 
 
 class _MetricTracker:
-    """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward"""
+    """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward; a registration that
+    names one of CHANHIST_METRICS gets sink(moments or None, full map or None, chanhist=(hist, nzero, absmax)) instead"""
 
-    def __init__(self, metrics, sink, map_due):
+    def __init__(self, metrics, sink, map_due, tau=1e-3):
         self.moments = any(m in MOMENT_METRICS for m in metrics)
+        self.chanhist = any(m in CHANHIST_METRICS for m in metrics)
+        self.tau = float(tau)
         self.full_map = "full_activation_map" in metrics
         self.sink, self.map_due = sink, map_due
 
@@ -160,11 +166,13 @@ class Engine:
 
     # ------------------------------------------------------------------ trackers and hooks
     def add_tracker(self, module: nn.Module, point: str, sink: Callable, metrics: Optional[List[str]] = None,
-                    map_due: Optional[Callable[[], bool]] = None):
+                    map_due: Optional[Callable[[], bool]] = None, near_zero_threshold: float = 1e-3):
         """metrics None: fused `mean_abs_activation_per_channel` for `module`'s input or output: sink(tensor[C]) per forward.
         metrics: any subset of DEVICE_METRICS on a module that metric_trackable() accepts: sink(moments, fmap) per forward,
         with moments = ops.moments(tensor) (None when only the full map is asked for) and fmap an fp32 NHWC copy of the
-        tensor when `full_activation_map` is asked for and map_due() (default: always) says a snapshot is wanted, else None."""
+        tensor when `full_activation_map` is asked for and map_due() (default: always) says a snapshot is wanted, else None.
+        When metrics names one of CHANHIST_METRICS the sink is called with a third, keyword argument as well:
+        chanhist = ops.chanhist(tensor, tau=near_zero_threshold), the (hist, nzero, absmax) triple of that forward."""
         assert point in ("input", "output")
         if metrics is None:
             self._trackers.setdefault(id(module), {}).setdefault(point, []).append(sink)
@@ -174,7 +182,7 @@ class Engine:
             raise ValueError(f"device trackers serve {DEVICE_METRICS}, not {list(metrics)}")
         if not self.metric_trackable(module):
             raise ValueError(f"{type(module).__name__}: no 4-D capture point the engine can reduce")
-        t = _MetricTracker(metrics, sink, map_due)
+        t = _MetricTracker(metrics, sink, map_due, near_zero_threshold)
         self._mtrackers.setdefault(id(module), {}).setdefault(point, []).append(t)
         return _TrackHandle(self._mtrackers, id(module), point, t)
 
@@ -202,9 +210,11 @@ class Engine:
     @staticmethod
     def _emit(ts: List[_MetricTracker], x: torch.Tensor, st: Optional[Stats] = None, xf: int = XF_NONE,
               make_map: Optional[Callable[[], torch.Tensor]] = None):
-        """serve device trackers from y = XF(x): one moments pass shared by all of them; a full map only for those whose
-        snapshot is due (make_map: the materialised y when xf is not XF_NONE, else a copy of x)"""
+        """serve device trackers from y = XF(x): one moments pass and one chanhist pass (per near-zero threshold) shared by all
+        that ask for them; a full map only for those whose snapshot is due (make_map: the materialised y when xf is not
+        XF_NONE, else a copy of x)"""
         mom = ops.moments(x, st, xf) if any(t.moments for t in ts) else None
+        hists = {tau: ops.chanhist(x, st, xf, tau) for tau in dict.fromkeys(t.tau for t in ts if t.chanhist)}
         fmap = None
         for t in ts:
             f = None
@@ -214,7 +224,10 @@ class Engine:
                     if not fmap.is_contiguous():
                         fmap = ops.map_snapshot(fmap)
                 f = fmap
-            t.sink(mom if t.moments else None, f)
+            if t.chanhist:
+                t.sink(mom if t.moments else None, f, chanhist=hists[t.tau])
+            else:
+                t.sink(mom if t.moments else None, f)
 
     def _mean_abs(self, t: torch.Tensor) -> torch.Tensor:
         B, Cc = t.shape[0], t.shape[-1]

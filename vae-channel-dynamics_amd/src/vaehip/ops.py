@@ -922,6 +922,47 @@ def moments(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE) -
     return out
 
 
+CHANHIST_BINS = 48  # vae_chanhist_bins(): bin = clamp(floor(log2 |y|) + 31, 0, 47)
+
+
+def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, tau: float = 1e-3):
+    """per-channel magnitude statistics of y = XF(x) in one read of x, no tensor materialised: (hist int64 [C, 48], nzero int64
+    [C], absmax fp32 [C]) on the device.  hist[c, k] counts the values of channel c whose fp32 exponent puts them in bin
+    k = clamp(floor(log2 |y|) + 31, 0, 47) (bin 0: |y| < 2^-30 with zeros and denormals, bin 47: |y| >= 2^16, inf, NaN); every
+    row sums to B * H * W.  nzero[c] counts |y| < tau (compared in fp32; NaN is not below), absmax[c] is max |y| (NaN if the
+    channel holds one).  x, stats and xf as in moments(); nothing synchronises the host."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"chanhist: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"chanhist: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    if (stats is None) != (xf == XF_NONE):
+        raise ValueError("chanhist: a GroupNorm transform (xf) needs its stats and stats need an xf")
+    if stats is not None:
+        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
+            raise ValueError(f"chanhist: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
+    HW = H * W
+    # as moments(), for this kernel's tile of 128 channels (32 units of four channels, or 128 single channels)
+    units, tile = (Cc // 4, 32) if Cc % 4 == 0 else (Cc, 128)
+    pr = max(1, 256 // min(tile, units))
+    tiles = (units + tile - 1) // tile
+    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
+    per = (HW + nch - 1) // nch
+    nch = (HW + per - 1) // per  # every chunk non-empty
+    dev = x.device
+    n = C.c_int64(0)
+    lib.call("vae_chanhist_workspace", B, HW, Cc, nch, C.byref(n))
+    ws = torch.empty((n.value,), device=dev, dtype=torch.int32)
+    hist = torch.empty((Cc, CHANHIST_BINS), device=dev, dtype=torch.int64)
+    nzero = torch.empty((Cc,), device=dev, dtype=torch.int64)
+    absmax = torch.empty((Cc,), device=dev, dtype=torch.float32)
+    lib.call("vae_chanhist_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
+             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, float(tau), _p(ws), _stream())
+    lib.call("vae_chanhist_final", _p(ws), B, HW, Cc, nch, _p(hist), _p(nzero), _p(absmax), _stream())
+    return hist, nzero, absmax
+
+
 def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """per-image quality metrics of `pred` against `target` (evaluate.py's Average MSE / PSNR / SSIM) in one read of both: a
     float64 device tensor [B, 3] = [sum (pred - target)^2, sum (u(pred) - u(target))^2 with u(x) = clamp((x + 1) / 2, 0, 1),
