@@ -11,7 +11,11 @@ every library's vae_wgrad_wino writes its own slab and bias partials.  Reported 
     quartiles and extremes per arm.
 Shapes: the six distinct plain 3x3 launches of the fp32 step (256^2, batch 16) with the split count of vae_wgrad_wino_plan.
 
-usage: python tools/wgrad_x3_ab.py NEW.so OFF.so PARENT.so [--launches 30] [--out FILE]"""
+--upsampler: the same three arms for the upsampler weight gradient (csrc/wgrad3_upwino.hip, 9 positions; OFF = the
+`make -C csrc upwgrad_x3_off` build, libvaehip_upwgrad_x3off.so, -DVAE_UPWGRAD_X3=0) on the step's three upsamplers: 512 -> 512 at
+32^2 and 64^2, 256 -> 256 at 128^2 (low resolution).  --rotate: the opening arm moves on by one every round (N O P, O P N, ...).
+
+usage: python tools/wgrad_x3_ab.py NEW.so OFF.so PARENT.so [--upsampler] [--rotate] [--launches 30] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +30,7 @@ from vaehip.lib import WgradArgs, lib  # noqa: E402
 
 # Cin, Cout, map, batch
 BENCH = [(128, 128, 256, 16), (256, 128, 256, 16), (256, 256, 128, 16), (512, 256, 128, 16), (512, 512, 64, 16), (512, 512, 32, 16)]
+BENCH_UP = [(512, 512, 32, 16), (512, 512, 64, 16), (256, 256, 128, 16)]  # (map: the low-resolution x)
 NAMES = ("new", "off", "parent")
 SUB = 8  # channels of the corner held to float64
 
@@ -42,10 +47,14 @@ def _open(path):
     return dll
 
 
-def _corner_f64(x, dy):
-    """dW[:SUB, :, :, :SUB] of the 3x3 stride-1 pad-1 weight gradient in float64: [SUB co][3][3][SUB ci]"""
-    B, H, W, _ = x.shape
-    xp = torch.nn.functional.pad(x[..., :SUB].double(), (0, 0, 1, 1, 1, 1))
+def _corner_f64(x, dy, up=False):
+    """dW[:SUB, :, :, :SUB] of the 3x3 stride-1 pad-1 weight gradient in float64: [SUB co][3][3][SUB ci] (up: of the nearest-
+    upsampled x)"""
+    xs = x[..., :SUB].double()
+    if up:
+        xs = xs.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+    B, H, W, _ = xs.shape
+    xp = torch.nn.functional.pad(xs, (0, 0, 1, 1, 1, 1))
     d = dy[..., :SUB].double().reshape(-1, SUB)
     out = torch.empty((SUB, 3, 3, SUB), dtype=torch.float64, device=x.device)
     for kh in range(3):
@@ -58,22 +67,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs=3, help="NEW.so OFF.so PARENT.so")
     ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--upsampler", action="store_true", help="wgrad3_upwino_kernel on the step's three upsamplers")
+    ap.add_argument("--rotate", action="store_true", help="rotate the opening arm every round")
     ap.add_argument("--out", default="")
     arg = ap.parse_args()
     dlls = [_open(s) for s in arg.libs]
     dev = torch.device("cuda:0")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     rows, ok = [], True
-    for Ci, Co, H, B in BENCH:
+    up = arg.upsampler
+    npos = 9 if up else 16
+    for Ci, Co, H, B in (BENCH_UP if up else BENCH):
         g = torch.Generator(device=dev).manual_seed(Ci + Co + H + B)
         x = torch.randn((B, H, H, Ci), device=dev, generator=g)
-        dy = torch.randn((B, H, H, Co), device=dev, generator=g)
-        a = ops.wgrad_args("c3", B, H, H, Ci, Co, Ci, prec=ops.PREC_F32)
+        dy = torch.randn((B, 2 * H, 2 * H, Co) if up else (B, H, H, Co), device=dev, generator=g)
+        a = ops.wgrad_args("c3up" if up else "c3", B, H, H, Ci, Co, Ci, prec=ops.PREC_F32)
         a.dY, a.X = _p(dy), _p(x)
         n = C.c_int32(0)
         assert dlls[0].vae_wgrad_wino_plan(C.byref(a), C.byref(n)) == 0 and n.value > 0
         ns = a.nsplit = n.value
-        outs = [(torch.full((ns, 16 * Ci * Co), float("nan"), device=dev), torch.full((ns, Co), float("nan"), device=dev)) for _ in dlls]
+        outs = [(torch.full((ns, npos * Ci * Co), float("nan"), device=dev), torch.full((ns, Co), float("nan"), device=dev)) for _ in dlls]
 
         def call(i, out=None):
             slab, bpart = out or outs[i]
@@ -91,10 +104,10 @@ def main():
                "off_bitwise_equal_to_parent": bool(torch.equal(bits(outs[1][0]), bits(outs[2][0])) and torch.equal(bits(outs[1][1]), bits(outs[2][1]))),
                "new_bias_partials_bitwise_equal_to_off": bool(torch.equal(bits(outs[0][1]), bits(outs[1][1]))),
                "new_two_launches_bitwise_equal": bool(torch.equal(bits(outs[0][0]), bits(again[0])) and torch.equal(bits(outs[0][1]), bits(again[1])))}
-        ref = _corner_f64(x, dy)
+        ref = _corner_f64(x, dy, up)
         for i in (0, 1):
             dW = torch.full((Co, 3, 3, Ci), float("nan"), device=dev)
-            lib.call("vae_wgrad_wino_reduce", _p(outs[i][0]), ns, 16, Ci, Co, None, _p(dW), None, None, st)
+            lib.call("vae_wgrad_wino_reduce", _p(outs[i][0]), ns, npos, Ci, Co, None, _p(dW), None, None, st)
             row[f"{NAMES[i]}_err_of_corner_max"] = float((dW[:SUB, :, :, :SUB].double() - ref).abs().max() / ref.abs().max())
         ok = ok and row["off_bitwise_equal_to_parent"] and row["new_bias_partials_bitwise_equal_to_off"] and row["new_two_launches_bitwise_equal"]
         for _ in range(3):
@@ -102,7 +115,7 @@ def main():
                 call(i)
         ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(arg.launches)] for _ in dlls]
         for k in range(arg.launches):
-            for i in range(3):
+            for i in ([(k + j) % 3 for j in range(3)] if arg.rotate else range(3)):
                 ev[i][k][0].record()
                 call(i)
                 ev[i][k][1].record()
@@ -114,6 +127,7 @@ def main():
                        "max_ms": round(ms[-1], 4)}
         row["new_over_parent"] = round(row["new"]["median_ms"] / row["parent"]["median_ms"], 4)
         row["off_over_parent"] = round(row["off"]["median_ms"] / row["parent"]["median_ms"], 4)
+        row["new_quartiles_clear_below_parent"] = bool(row["new"]["q3_ms"] < row["parent"]["q1_ms"])
         print(json.dumps(row), flush=True)
         rows.append(row)
         del outs, again, x, dy

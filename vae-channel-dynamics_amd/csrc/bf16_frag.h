@@ -27,7 +27,7 @@ __device__ __forceinline__ f32x4 unpack4(uint2 r) {
 // Split-bf16 ("x3") operands: an fp32 value a as three bf16 planes
 //   hi = bf16(a), mid = bf16(a - hi), lo = bf16((a - hi) - mid)      (round to nearest even; both subtractions are exact in fp32)
 // so that hi + mid + lo = a up to 2^-26 |a|.  About 5.5 vector instructions per value.  Used by the flat fp32 kernels (igemm.hip,
-// F32X3: planes staged in LDS), by the Winograd weight gradient (wgrad3_wino.hip: planes built in registers) and by the upsampler
+// F32X3: planes staged in LDS), by the two Winograd weight gradients (wgrad3_wino.hip, wgrad3_upwino.hip: planes built in registers) and by the upsampler
 // convolution (conv3_upwino.hip: V planes staged in LDS, U planes written by its weights kernel).
 // (pack4 as two 2-wide conversions: element by element, hipcc converts one pair of the four singly and merges it with a v_perm_b32)
 __device__ __forceinline__ uint2 pack4_pairs(f32x4 v) {
@@ -57,6 +57,20 @@ __device__ __forceinline__ void split3_pair(float a, float b, unsigned& hi, unsi
   const float ra = a - __builtin_bit_cast(float, hi << 16), rb = b - __builtin_bit_cast(float, hi & 0xffff0000u);
   mid = pk(ra, rb);
   lo = pk(ra - __builtin_bit_cast(float, mid << 16), rb - __builtin_bit_cast(float, mid & 0xffff0000u));
+}
+struct Bf3 {
+  bf16x8 p[3];  // planes hi, mid, lo of a lane half's eight k
+};
+// the MFMA operand of eight fp32 values (the two Winograd weight gradients: v0 = the four tiles of a pair's first unit, v1 = of
+// its second)
+__device__ __forceinline__ Bf3 split8(f32x4 v0, f32x4 v1) {
+  uint2 q0[3], q1[3];
+  split3(v0, q0[0], q0[1], q0[2]);
+  split3(v1, q1[0], q1[1], q1[2]);
+  Bf3 f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) f.p[i] = __builtin_bit_cast(bf16x8, uint4{q0[i].x, q0[i].y, q1[i].x, q1[i].y});
+  return f;
 }
 // A product a.b of split operands is the sum of the six plane products that are not below 2^-24 |a.b|, added into the fp32
 // accumulator smallest first: term t = 0..5 is hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi (planes 0 = hi, 1 = mid, 2 = lo)

@@ -1,6 +1,9 @@
 // fp32 weight gradient of an Upsample2D block's convolution, conv3x3(nearest_upsample_2x(x)), with 9 multiplications per
 // LOW-resolution pixel and (ci, co) pair (direct: 36; the four 2x2 phase weight gradients of round 1: 16).  Companion of
-// conv3_upwino.hip; exact fp32 products on v_mfma_f32_32x32x2_f32.
+// conv3_upwino.hip.  Two loops, chosen at build time (VAE_UPWGRAD_X3): split-bf16 products on v_mfma_f32_32x32x16_bf16, two units per
+// step (the default; described in front of its step below), or exact fp32 products on v_mfma_f32_32x32x2_f32, one unit per step
+// (-DVAE_UPWGRAD_X3=0, make upwgrad_x3_off; the "Kernel" paragraph describes it; staging roles, operand builders, slab, bias
+// partials and reduction are the same in both).
 //
 // F(3x3, 2x2) on the 2x2 block of dY that belongs to low-resolution pixel (i, j) reads the 4x4 patch of the UPSAMPLED input with
 // origin (2i-1, 2j-1), whose rows are x[i-1], x[i], x[i], x[i+1]: row 2 of B^T d vanishes, so only the positions {0, 1, 3}^2 of the
@@ -20,10 +23,22 @@
 // so every SIMD carries 36 MFMAs per step.  (A first version with one position per wave and 9 waves put three waves of every
 // workgroup on SIMD 0: 0.51 of the matrix peak.)  One workgroup per CU at 158 registers (a 128-register build spilled 27, with
 // scratch reloads inside the loop); two staging register sets, the next-but-one unit requested behind the first channel block's
-// MFMAs.
+// MFMAs.  The split loop: 168 registers, 100,352 B of dynamic LDS (two stages per pair, double buffered), no scratch.
 #include "wino_common.h"
 #include <algorithm>
 #include <type_traits>
+
+#ifndef VAE_UPWGRAD_X3
+#define VAE_UPWGRAD_X3 1  // 1: split-bf16 products, two units per step; 0: exact fp32 products, one unit per step (make upwgrad_x3_off)
+#endif
+#if VAE_UPWGRAD_X3
+#include "bf16_frag.h"
+#endif
+// VAE_UPWGRAD_PRIO 1 (default): waves 4..7 (the second-dispatched wave of every SIMD, which loses the issue arbitration to its partner)
+// run the split loop at s_setprio 1, as in wgrad3_wino.hip: 3.1-3.5 % faster on the step's three layers (profiles/upw_tiles_measured.json)
+#ifndef VAE_UPWGRAD_PRIO
+#define VAE_UPWGRAD_PRIO 1
+#endif
 
 namespace {
 
@@ -33,9 +48,18 @@ constexpr int XSY = 20;                 // x pitch of a staged dY row: 16 column
 constexpr int SXF = 3 * GCI * XSX;      // halo stage: [3 rows][32 ci][XSX]
 constexpr int SYF = 2 * GCO * XSY;      // dY stage:   [2 rows][128 co][XSY]
 constexpr int GSTAGE = SXF + SYF;       // 6272 floats (25088 B)
+#if VAE_UPWGRAD_X3
+constexpr int GPAIR = 2 * GSTAGE;                     // the two stages of a pair of units
+constexpr int GLDS = 2 * GPAIR * (int)sizeof(float);  // double buffered: 100352 B
+extern __shared__ __attribute__((aligned(16))) float upwgrad_lds[];
+#endif
 
 __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p, int strips, int64_t nunits) {
+#if VAE_UPWGRAD_X3
+  float* const smem = upwgrad_lds;
+#else
   __shared__ __attribute__((aligned(16))) float smem[2 * GSTAGE];
+#endif
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;  // wave = position (pr, pc) 0..7; position 8: block `wave` on waves 0..3
   const int lr = lane & 31, lh = lane >> 5;
@@ -110,10 +134,26 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
 #pragma unroll
   for (int e = 0; e < 16; ++e) accx[e] = 0.f;
 
+#if VAE_UPWGRAD_X3
+  // One set of staging registers per unit of a pair (s0: the first): a wave stores pair kp+1 during step kp and requests pair kp+2
+  // right behind the stores, into the same registers: a whole step in flight.  The units are stored in ascending order, dY row 0
+  // before row 1: the order of the bias sums is the exact loop's (units beyond the range add zeros)
+  auto stage_pair = [&](float* st, int kp) __attribute__((always_inline)) {
+    store_unit(st, s0);
+    store_unit(st + GSTAGE, s1);
+    load_unit(2 * kp + 2, s0);
+    load_unit(2 * kp + 3, s1);
+  };
+  load_unit(0, s0);
+  load_unit(1, s1);
+  stage_pair(smem, 0);  // pair 0 to LDS, pair 1 requested
+  __syncthreads();
+#else
   load_unit(0, s0);
   store_unit(smem, s0);
   load_unit(1, s1);
   __syncthreads();
+#endif
 
   // operand builders for position (pr, pc).  V fragment: lane (ci = lr, half lh) takes tiles 4 lh + e: halo columns 4 lh .. 4 lh + 5
   // of the rows the position combines (rows 0, 1, 2 of the halo = x[i-1], x[i], x[i+1]: pr 0: r0 - r1, 1: r1, 2: r1 - r2).
@@ -163,6 +203,57 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
   // The loop body is instantiated per position: straight-line code, no per-step branches.
   auto run = [&](auto PR, auto PC, auto EXTRA) {
     constexpr bool extra = decltype(EXTRA)::value;  // this wave also owns block `wave` of position 8 = (2, 2)
+#if VAE_UPWGRAD_X3
+    // The K = 16 of v_mfma_f32_32x32x16_bf16 is two units: a split's unit range is walked in pairs (an odd last unit is paired with
+    // the zeros load_unit delivers beyond the range), each unit in a stage of its own ([pair parity][unit of the pair][GSTAGE]).
+    // A lane half's eight k are the four tiles it takes in the exact loop, of the pair's first unit (k 0..3) and of its second
+    // (k 4..7), in the V and in the D operand alike.  build_a / build_b stay in fp32; their results are split in registers (split8)
+    // and a product is the six plane products of mma_x3_term, smallest first: 24 (30 on waves 0..3) MFMAs of 32 cycles per wave and
+    // pair against 32 (40) of 64 cycles.  Waves 0..3 store the next pair behind their V operands, waves 4..7 in front of their last
+    // block: the two waves of a SIMD store at opposite ends of the step (wgrad3_wino.hip).
+    auto step = [&](int kp) {
+      const float* cst = smem + (kp & 1) * GPAIR;
+      float* nst = smem + ((kp + 1) & 1) * GPAIR;
+      Bf3 a3, bb;
+      {
+        f32x4 a0, a1;
+        build_a(PR, PC, cst, a0);
+        build_a(PR, PC, cst + GSTAGE, a1);
+        a3 = split8(a0, a1);
+      }
+      if (extra) stage_pair(nst, kp + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      // no scheduling barrier between the blocks: block nb+1's LDS reads and additions may move up between block nb's MFMAs
+#pragma unroll
+      for (int nb = 0; nb < GNB; ++nb) {
+        if (nb == GNB - 1 && !extra) {
+          __builtin_amdgcn_sched_barrier(0);
+          stage_pair(nst, kp + 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        f32x4 b0, b1;
+        build_b(PR, PC, cst + SXF, nb, b0);
+        build_b(PR, PC, cst + GSTAGE + SXF, nb, b1);
+        bb = split8(b0, b1);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) acc[nb] = mma_x3_term(t, a3.p, bb.p, acc[nb]);
+      }
+      if (extra) {
+        f32x4 a0, a1, b0, b1;
+        build_a(I2{}, I2{}, cst, a0);
+        build_a(I2{}, I2{}, cst + GSTAGE, a1);
+        build_b(I2{}, I2{}, cst + SXF, wave, b0);
+        build_b(I2{}, I2{}, cst + GSTAGE + SXF, wave, b1);
+        a3 = split8(a0, a1);
+        bb = split8(b0, b1);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) accx = mma_x3_term(t, a3.p, bb.p, accx);
+      }
+      __syncthreads();
+    };
+    const int np = (nu + 1) / 2;  // steps
+    for (int kp = 0; kp < np; ++kp) step(kp);
+#else
     auto step = [&](int k, const Stg& cur, Stg& nxt) {  // cur: unit k+1 (requested during step k-1); nxt receives unit k+2
       const float* cx = smem + (k & 1) * GSTAGE;
       const float* cy = cx + SXF;
@@ -198,7 +289,11 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
       step(k + 1, s0, s1);
     }
     if (k < nu) step(k, s1, s0);
+#endif
   };
+#if VAE_UPWGRAD_X3 && VAE_UPWGRAD_PRIO  // one static s_setprio around the loop; a scalar condition: the instruction ignores EXEC
+  if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
+#endif
   {
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -215,6 +310,9 @@ __global__ __launch_bounds__(GNT, 2) void wgrad3_upwino_kernel(vae_wgrad_args p,
       default: run(I2{}, I1{}, F_{}); break;
     }
   }
+#if VAE_UPWGRAD_X3 && VAE_UPWGRAD_PRIO
+  __builtin_amdgcn_s_setprio(0);
+#endif
 
   // ---- epilogue: slab [split][9 positions][Cin][Cout]; lanes along co (128-byte rows) ----
   float* __restrict__ O = p.partial + (int64_t)split * NPOS * p.N * p.M;
@@ -240,6 +338,11 @@ int launch_wgrad3_upwino(const vae_wgrad_args& a, hipStream_t st) {
   const vae_conv_geom& g = a.g;
   const int64_t nunits = wgrad3_upwino_units(g);
   dim3 grid((unsigned)((a.M / GCO) * (a.N / GCI) * a.nsplit), 1, 1);
+#if VAE_UPWGRAD_X3  // (more than 64 KB of dynamic LDS: reserved once per device)
+  VAE_RESERVE_LDS(wgrad3_upwino_kernel, GLDS, "wgrad3_upwino");
+  hipLaunchKernelGGL(wgrad3_upwino_kernel, grid, dim3(GNT), GLDS, st, a, g.Ws / 8, nunits);
+#else
   hipLaunchKernelGGL(wgrad3_upwino_kernel, grid, dim3(GNT), 0, st, a, g.Ws / 8, nunits);
+#endif
   return 0;
 }

@@ -383,20 +383,6 @@ constexpr int GPAIR = 2 * GSTAGE;                  // the two stages of a pair o
 constexpr int GLDS = 2 * GPAIR * (int)sizeof(float);  // double buffered: 122880 B
 extern __shared__ __attribute__((aligned(16))) float wgrad_lds[];
 
-struct Bf3 {
-  bf16x8 p[3];  // planes hi, mid, lo of a lane half's eight k
-};
-// the MFMA operand of eight fp32 values: v0 = the four tiles of the pair's first unit, v1 = of its second
-__device__ __forceinline__ Bf3 split8(f32x4 v0, f32x4 v1) {
-  uint2 q0[3], q1[3];
-  split3(v0, q0[0], q0[1], q0[2]);
-  split3(v1, q1[0], q1[1], q1[2]);
-  Bf3 f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) f.p[i] = __builtin_bit_cast(bf16x8, uint4{q0[i].x, q0[i].y, q1[i].x, q1[i].y});
-  return f;
-}
-
 template <int XF>
 __global__ __launch_bounds__(GNT, 1) void wgrad3_wino_kernel(vae_wgrad_args p, int strips, int64_t nunits) {
   float* const smem = wgrad_lds;
