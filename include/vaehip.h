@@ -299,6 +299,26 @@ int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* scale, cons
                          int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float tau, uint32_t* ws, void* stream);
 int vae_chanhist_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* hist, int64_t* nzero,
                        float* absmax, void* stream);
+/* channel covariance and mean of y = XF(x) over the N = B * HW rows of an NHWC activation in one read (monitor.py's
+ * channel_covariance_matrix / channel_correlation_matrix / max_abs_correlation_per_channel / effective_rank), csrc/chancov.hip.
+ * x, x_bf16, scale, shift, xf, ld, nchunk: exactly as vae_moments_partial.  The sums are taken of z = fp32(y - K) with
+ * K[c] = y at (image 0, pixel 0, channel c): a constant channel gives exactly 0 in its row, column and variance, and a mean far
+ * above sigma costs no digits.  Products are split-bf16 (three bf16 planes per operand, six plane products smallest first, fp32
+ * accumulation per workgroup), the merge over workgroups is float64 in a fixed order.
+ * vae_chancov_tile: channels of a tile (128); a workgroup handles one (pixel chunk, image, tile pair of the upper triangle).
+ * vae_chancov_workspace: *nfloats = floats of ws for this shape (exactly what the partial pass writes:
+ * B * nchunk * (pairs * tile^2 + 2 * tiles * tile) + tiles * tile with tiles = ceil(C / tile), pairs = tiles (tiles + 1) / 2);
+ * needs no GPU.  2 <= B * HW < 2^31, every chunk of ceil(HW / nchunk) pixels non-empty.
+ * partial: ws = per (b, chunk) the fp32 tiles of sum z_c z_c', the float64 sums of z_c, and K.  Channels at or beyond C are
+ * zeros in ws and are never read from x.  ws 16-byte aligned.
+ * final: cov [C][C] float64 = (S - d d^T / N) / (N - 1), both triangles, bitwise symmetric; mean [C] float64 = K + d / N.
+ * No global atomics, no zero-fill: repeated launches are bitwise identical. */
+int vae_chancov_tile(void);
+int vae_chancov_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nfloats);
+int vae_chancov_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
+                        int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float* ws, void* stream);
+int vae_chancov_final(const float* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* cov, double* mean,
+                      void* stream);
 /* ---- image-quality metrics of a reconstruction (evaluate.py: Average MSE, PSNR, SSIM; reference src/evaluate.py:172-183,
  * torchmetrics PeakSignalNoiseRatio / StructuralSimilarityIndexMeasure), csrc/image_metrics.hip ----
  * pred, target: fp32 images of logical shape (B, C, H, W), values nominally in [-1, 1], each with its own four ELEMENT strides

@@ -32,6 +32,15 @@ fp32 exponent: bin 0 is |A| < 2^-30, bin 47 is |A| >= 2^16, inf and NaN -- what 
 full map.  Hooks compute them with torch (compute_metrics); a device-served layer gets all three from ONE ops.chanhist pass
 per forward.  step() sums the histograms over the buffered forwards, takes the maximum of the maxima and the unweighted mean
 of the fractions; device-served layers sum / max / average them across ranks as well and come to the host in one transfer.
+
+Four more answer "which channels carry the same signal" (CHANCOV_METRICS, any layer and capture point):
+`channel_covariance_matrix` (float64 [C][C], unbiased over batch and all trailing axes, channel = dim 1),
+`channel_correlation_matrix` (fp32 [C][C]; 0 wherever a variance is <= 0, the diagonal 1 on live channels),
+`max_abs_correlation_per_channel` (fp32 [C], max over c' != c of |rho|: a channel near 1 is a copy of another) and
+`effective_rank` (tr(cov)^2 / ||cov||_F^2, the participation ratio: how many directions the layer uses).  All four derive from
+ONE covariance per forward: torch.cov in the hook (compute_metrics), ONE ops.chancov pass on a device-served layer.  A layer
+keeps a running float64 sum and a forward count, not a list; step() averages it over the forwards (device-served: across
+ranks too), brings it to the host in one transfer and derives the rest in float64 with correlation_summary().
 """
 import logging
 from collections import defaultdict
@@ -51,6 +60,12 @@ KNOWN_METRICS = (FUSED_METRIC, "full_activation_map", "mean_activation", "std_ac
 HIST_BINS = 48             # bin = clamp(floor(log2 |y|) + 31, 0, 47), from the fp32 exponent field
 NEAR_ZERO_THRESHOLD = 1e-3  # default of tracking.near_zero_threshold
 DEAD_FRACTION = 0.99       # a channel with at least this share of near-zero values counts as dead in the records
+COV_METRIC = "channel_covariance_matrix"
+CORR_METRIC = "channel_correlation_matrix"
+MAXCORR_METRIC = "max_abs_correlation_per_channel"
+RANK_METRIC = "effective_rank"
+CHANCOV_METRICS = (COV_METRIC, CORR_METRIC, MAXCORR_METRIC, RANK_METRIC)  # accepted beside KNOWN_METRICS; one covariance serves all
+REDUNDANCY_THRESHOLD = 0.95  # default of tracking.redundancy_threshold: |rho| above it marks a redundant pair / channel
 
 
 def _resolve(root: torch.nn.Module, dotted: str) -> torch.nn.Module:
@@ -86,15 +101,54 @@ def _near_zero_fraction(count, n) -> np.ndarray:
     return (np.asarray(count, dtype=np.float64) / np.asarray(n, dtype=np.float64)).astype(np.float32)
 
 
+def correlation_summary(cov: np.ndarray, redundancy_threshold: float = REDUNDANCY_THRESHOLD) -> Dict[str, Any]:
+    """everything the CHANCOV_METRICS report, from a channel covariance, on the host in float64:
+    correlation [C, C] = cov / sqrt(var_c var_c'), 0 wherever either variance is <= 0 (so its diagonal is 1 on live channels
+    and 0 on dead ones); max_abs [C] = max over c' != c of |rho| (0 for C = 1); effective_rank = tr(cov)^2 / ||cov||_F^2, 0
+    when the trace is 0; mean_abs_offdiag / max_abs_offdiag of rho and of cov (cov_*); redundant_pairs = pairs c < c' with
+    |rho| above the threshold, redundant_channels = channels whose max_abs is above it"""
+    cov = np.atleast_2d(np.asarray(cov, dtype=np.float64))
+    Cc = cov.shape[0]
+    var = np.diag(cov)
+    live = var > 0
+    sd = np.sqrt(np.where(live, var, 1.0))
+    rho = np.where(live[:, None] & live[None, :], cov / (sd[:, None] * sd[None, :]), 0.0)
+    np.fill_diagonal(rho, live.astype(np.float64))  # exactly 1 on live channels, whatever sqrt rounds to
+    off = ~np.eye(Cc, dtype=bool)
+    arho = np.where(off, np.abs(rho), 0.0)
+    acov = np.where(off, np.abs(cov), 0.0)
+    max_abs = arho.max(axis=1) if Cc > 1 else np.zeros(Cc)
+    tr, fro2 = float(np.trace(cov)), float(np.sum(cov * cov))
+    npairs = max(Cc * (Cc - 1), 1)
+    return {"correlation": rho, "max_abs": max_abs, "effective_rank": tr * tr / fro2 if tr > 0 and fro2 > 0 else 0.0,
+            "mean_abs_offdiag": float(arho.sum() / npairs), "max_abs_offdiag": float(arho.max()) if Cc > 1 else 0.0,
+            "cov_mean_abs_offdiag": float(acov.sum() / npairs), "cov_max_abs_offdiag": float(acov.max()) if Cc > 1 else 0.0,
+            "redundant_pairs": int((np.triu(arho, 1) > redundancy_threshold).sum()),
+            "redundant_channels": int((max_abs > redundancy_threshold).sum())}
+
+
+def channel_covariance(tensor: torch.Tensor) -> torch.Tensor:
+    """float64 [C, C] on the tensor's device: unbiased covariance of the channels (dim 1) over batch and all trailing axes"""
+    yc = _per_channel(tensor).double()
+    return torch.cov(yc).reshape(yc.shape[0], yc.shape[0])
+
+
 def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshold: float = NEAR_ZERO_THRESHOLD) -> Dict[str, Any]:
-    """slow-path formulas, identical to monitor.py:56-80; the three CHANHIST_METRICS are what ops.chanhist computes."""
+    """slow-path formulas, identical to monitor.py:56-80; the three CHANHIST_METRICS are what ops.chanhist computes.  Each of
+    the CHANCOV_METRICS named gets the forward's float64 covariance (one tensor, shared, on the tensor's device): step()
+    derives the metric from the average over the forwards."""
     out: Dict[str, Any] = {}
+    cov = None
     if not isinstance(tensor, torch.Tensor):
         logger.warning(f"Cannot calculate metrics for non-tensor type: {type(tensor)}")
         return out
     for name in metrics:
         try:
-            if name == HIST_METRIC:
+            if name in CHANCOV_METRICS:
+                if cov is None:
+                    cov = channel_covariance(tensor)
+                out[name] = cov
+            elif name == HIST_METRIC:
                 yc = _per_channel(tensor)
                 idx = log2_bins(yc) + torch.arange(yc.shape[0], device=yc.device)[:, None] * HIST_BINS
                 out[name] = torch.bincount(idx.flatten(), minlength=yc.shape[0] * HIST_BINS).view(-1, HIST_BINS).cpu().numpy()
@@ -139,6 +193,32 @@ class _ChanHist:
         self.t = t
 
 
+class _CovSum:
+    """a layer's running float64 sum of per-forward channel covariances and their count, shared by the CHANCOV_METRICS the
+    layer tracks (resolved in step()); device_served: filled by ops.chancov, and averaged across ranks like the other
+    device-served vectors"""
+    __slots__ = ("sum", "n", "device_served")
+
+    def __init__(self, device_served: bool = False):
+        self.sum, self.n, self.device_served = None, 0, device_served
+
+    def add(self, cov: torch.Tensor):
+        self.sum = cov.clone() if self.sum is None else self.sum.add_(cov)  # a copy: the engine shares cov among its trackers
+        self.n += 1
+
+
+def _buffer_cov(buf, name: str, cov: torch.Tensor, device_served: bool, seen: set):
+    """add a forward's covariance to the layer's running sum (once per forward: `seen`) and list the sum under `name`"""
+    acc = next((buf[m][0] for m in CHANCOV_METRICS if m in buf and buf[m]), None)
+    if acc is None:
+        acc = _CovSum(device_served)
+    if id(acc) not in seen:
+        seen.add(id(acc))
+        acc.add(cov)
+    if not buf[name]:
+        buf[name].append(acc)
+
+
 class ActivityMonitor:
     def __init__(self, model: torch.nn.Module, tracking_config: Dict[str, Any]):
         self.model = model
@@ -152,6 +232,7 @@ class ActivityMonitor:
         self.device_metrics = bool(self.config.get("device_metrics", False))
         self.sync_across_ranks = bool(self.config.get("sync_across_ranks", True))
         self.near_zero_threshold = float(self.config.get("near_zero_threshold", NEAR_ZERO_THRESHOLD))
+        self.redundancy_threshold = float(self.config.get("redundancy_threshold", REDUNDANCY_THRESHOLD))
         if self.config.get("enabled", False):
             self._register_hooks()
             logger.info(f"ActivityMonitor initialized for {len(self.target_layers_config)} target(s) "
@@ -168,14 +249,19 @@ class ActivityMonitor:
 
     def _device_sink(self, layer_id: str, metrics: List[str]) -> Callable:
         """engine sink of a device-served layer: buffers device tensors only, one entry per metric in config order (the
-        order compute_metrics appends in); the moments vector and the histogram triple are shared by the metrics they serve"""
-        def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor], chanhist: Optional[tuple] = None):
+        order compute_metrics appends in); the moments vector and the histogram triple are shared by the metrics they serve,
+        the covariance goes into the layer's running sum"""
+        def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor], chanhist: Optional[tuple] = None,
+                 chancov: Optional[tuple] = None):
             buf = self.hook_collected_buffer[layer_id]
             hist = _ChanHist(chanhist) if chanhist is not None else None
+            seen: set = set()
             for name in metrics:
                 if name == "full_activation_map":
                     if fmap is not None:
                         buf[name].append(fmap)
+                elif name in CHANCOV_METRICS:
+                    _buffer_cov(buf, name, chancov[0], True, seen)
                 elif name in CHANHIST_METRICS:
                     buf[name].append(hist)
                 else:
@@ -195,8 +281,12 @@ class ActivityMonitor:
             else:
                 t = hook_output
             if isinstance(t, torch.Tensor):
+                seen: set = set()
                 for k, v in compute_metrics(t, metrics, self.near_zero_threshold).items():
-                    self.hook_collected_buffer[layer_id][k].append(v)
+                    if k in CHANCOV_METRICS:
+                        _buffer_cov(self.hook_collected_buffer[layer_id], k, v, False, seen)
+                    else:
+                        self.hook_collected_buffer[layer_id][k].append(v)
         return fn
 
     def _register_hooks(self):
@@ -222,7 +312,7 @@ class ActivityMonitor:
                     self.fused_layers.append(layer_id)
                     logger.info(f"Registered FUSED device tracker for layer: {name} ({point})")
                 elif self.device_metrics and engine is not None and metrics and \
-                        all(m in KNOWN_METRICS for m in metrics) and engine.metric_trackable(layer):
+                        all(m in KNOWN_METRICS + CHANCOV_METRICS for m in metrics) and engine.metric_trackable(layer):
                     mlist = list(dict.fromkeys(metrics))
                     extra = {"near_zero_threshold": self.near_zero_threshold} if any(m in CHANHIST_METRICS for m in mlist) else {}
                     self.hooks.append(engine.add_tracker(layer, point, self._device_sink(layer_id, mlist), metrics=mlist,
@@ -309,6 +399,27 @@ class ActivityMonitor:
                     else:
                         values[i] = row[:, HIST_BINS if metric == NEARZERO_METRIC else HIST_BINS + 1].astype(np.float32)
 
+    def _chancov_to_host(self, metric_data: Dict[str, list]):
+        """a layer's running covariance sum -> per CHANCOV metric the ONE host value step() stores, in place: the average over
+        the buffered forwards (device-served: over the ranks as well, like the mean |A| vectors), ONE transfer, then
+        correlation_summary() in float64.  Covariance float64 [C, C], correlation fp32 [C, C], max |rho| fp32 [C], rank float"""
+        acc = next((v for values in metric_data.values() for v in values if isinstance(v, _CovSum)), None)
+        if acc is None:
+            return
+        cov = acc.sum / acc.n
+        world = self._world() if acc.device_served else 1
+        if world > 1:
+            self._same_forward_count(acc.n, cov.device)
+            torch.distributed.all_reduce(cov)
+            cov = cov / world
+        host = cov.cpu().numpy()
+        summary = correlation_summary(host, self.redundancy_threshold)
+        for metric, values in metric_data.items():
+            if values and isinstance(values[0], _CovSum):
+                values[0] = {COV_METRIC: host, CORR_METRIC: summary["correlation"].astype(np.float32),
+                             MAXCORR_METRIC: summary["max_abs"].astype(np.float32),
+                             RANK_METRIC: float(summary["effective_rank"])}[metric]
+
     def _to_host(self, values: list) -> list:
         """device vectors of the fused path -> list of np.float32 arrays with ONE transfer."""
         if values and all(isinstance(v, torch.Tensor) and v.is_cuda for v in values):
@@ -359,6 +470,7 @@ class ActivityMonitor:
                    for m, values in metric_data.items() for v in values):
                 self._device_to_host(metric_data)
             self._chanhist_to_host(metric_data)
+            self._chancov_to_host(metric_data)
         for layer_id, metric_data in self.hook_collected_buffer.items():
             processed[layer_id] = {}
             for metric, values in metric_data.items():
@@ -373,6 +485,14 @@ class ActivityMonitor:
                         if isinstance(arr, np.ndarray):
                             log[key + "_mean"] = np.mean(arr.astype(np.float32))
                             log[key + "_std"] = np.std(arr.astype(np.float32))
+                    elif metric in CHANCOV_METRICS:  # one value, of the covariance averaged over the buffered forwards
+                        agg = values[0]
+                        if metric == CORR_METRIC:
+                            log[key + "_mean_abs_offdiag"] = correlation_summary(agg)["cov_mean_abs_offdiag"]
+                        elif metric == MAXCORR_METRIC:
+                            log[key + "_overall_max"] = np.max(agg)
+                        elif metric == RANK_METRIC:
+                            log[key] = agg
                     elif metric == HIST_METRIC:  # summed over the buffered forwards
                         agg = np.sum(np.stack([np.asarray(v, dtype=np.int64) for v in values]), axis=0)
                         log[key + "_top_bin_share"] = float(agg[..., -1].sum()) / max(float(agg.sum()), 1.0)
@@ -439,6 +559,18 @@ class ActivityMonitor:
                         add("full_map_std", float(np.std(a32)))
                         add("full_map_min", float(np.min(a32)))
                         add("full_map_max", float(np.max(a32)))
+                    elif metric in (COV_METRIC, CORR_METRIC):
+                        # (a correlation matrix is its own covariance: the cov_* figures of its summary are its own)
+                        summ = correlation_summary(arr, self.redundancy_threshold)
+                        kind = "covariance" if metric == COV_METRIC else "correlation"
+                        add(kind + "_shape", str(arr.shape))
+                        add(kind + "_mean_abs_offdiag", summ["cov_mean_abs_offdiag"])
+                        add(kind + "_max_abs_offdiag", summ["cov_max_abs_offdiag"])
+                        add(kind + "_redundant_pairs", summ["redundant_pairs"])  # pairs c < c' with |rho| above the threshold
+                    elif metric == MAXCORR_METRIC:
+                        add("max_abs_correlation_overall_mean", float(np.mean(arr)))
+                        add("max_abs_correlation_overall_max", float(np.max(arr)))
+                        add("max_abs_correlation_redundant_channels", int(np.sum(arr > self.redundancy_threshold)))
                     elif metric == HIST_METRIC:
                         total = arr.reshape(-1, arr.shape[-1]).sum(axis=0)  # the tensor's histogram: all channels together
                         rows = arr.reshape(-1, arr.shape[-1]).sum(axis=1)

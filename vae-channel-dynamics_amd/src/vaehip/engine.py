@@ -10,7 +10,8 @@ the shipped metric `mean_abs_activation_per_channel` (monitor.py:66) is served b
 device-side reductions instead (add_tracker), without any tensor or host sync.  add_tracker(metrics=...) serves any
 subset of the ActivityMonitor metrics at a 4-D capture point the same way: one moments pass (ops.moments) and one
 histogram pass (ops.chanhist: magnitude histogram, near-zero count, max |A| per channel) per forward on the tensor a hook
-would have received, each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
+would have received, and one covariance pass (ops.chancov: the channel covariance behind the correlation, redundancy and
+effective-rank metrics), each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
 """
 from __future__ import annotations
 
@@ -29,7 +30,9 @@ _TRACK_C = {4, 8, 16, 32, 64, 128, 256, 512, 1024}
 MOMENT_METRICS = ("mean_abs_activation_per_channel", "mean_activation", "std_activation")  # one ops.moments vector
 # one ops.chanhist pass: (histogram, near-zero count, max |y|) per channel
 CHANHIST_METRICS = ("log2_histogram_per_channel", "abs_max_activation_per_channel", "near_zero_fraction_per_channel")
-DEVICE_METRICS = MOMENT_METRICS + CHANHIST_METRICS + ("full_activation_map",)
+# one ops.chancov pass: (covariance, mean); the monitor derives the other three from the covariance
+CHANCOV_METRICS = ("channel_covariance_matrix", "channel_correlation_matrix", "max_abs_correlation_per_channel", "effective_rank")
+DEVICE_METRICS = MOMENT_METRICS + CHANHIST_METRICS + CHANCOV_METRICS + ("full_activation_map",)
 
 
 class _TrackHandle:
@@ -44,11 +47,13 @@ class _TrackHandle:
 
 class _MetricTracker:
     """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward; a registration that
-    names one of CHANHIST_METRICS gets sink(moments or None, full map or None, chanhist=(hist, nzero, absmax)) instead"""
+    names one of CHANHIST_METRICS gets sink(moments or None, full map or None, chanhist=(hist, nzero, absmax)) instead, one
+    that names one of CHANCOV_METRICS the keyword chancov=(cov, mean)"""
 
     def __init__(self, metrics, sink, map_due, tau=1e-3):
         self.moments = any(m in MOMENT_METRICS for m in metrics)
         self.chanhist = any(m in CHANHIST_METRICS for m in metrics)
+        self.chancov = any(m in CHANCOV_METRICS for m in metrics)
         self.tau = float(tau)
         self.full_map = "full_activation_map" in metrics
         self.sink, self.map_due = sink, map_due
@@ -172,7 +177,9 @@ class Engine:
         with moments = ops.moments(tensor) (None when only the full map is asked for) and fmap an fp32 NHWC copy of the
         tensor when `full_activation_map` is asked for and map_due() (default: always) says a snapshot is wanted, else None.
         When metrics names one of CHANHIST_METRICS the sink is called with a third, keyword argument as well:
-        chanhist = ops.chanhist(tensor, tau=near_zero_threshold), the (hist, nzero, absmax) triple of that forward."""
+        chanhist = ops.chanhist(tensor, tau=near_zero_threshold), the (hist, nzero, absmax) triple of that forward; when it
+        names one of CHANCOV_METRICS, with the keyword argument chancov = ops.chancov(tensor), the forward's float64
+        (covariance [C, C], mean [C])."""
         assert point in ("input", "output")
         if metrics is None:
             self._trackers.setdefault(id(module), {}).setdefault(point, []).append(sink)
@@ -210,11 +217,12 @@ class Engine:
     @staticmethod
     def _emit(ts: List[_MetricTracker], x: torch.Tensor, st: Optional[Stats] = None, xf: int = XF_NONE,
               make_map: Optional[Callable[[], torch.Tensor]] = None):
-        """serve device trackers from y = XF(x): one moments pass and one chanhist pass (per near-zero threshold) shared by all
-        that ask for them; a full map only for those whose snapshot is due (make_map: the materialised y when xf is not
+        """serve device trackers from y = XF(x): one moments pass, one chanhist pass (per near-zero threshold) and one chancov
+        pass shared by all that ask for them; a full map only for those whose snapshot is due (make_map: the materialised y when xf is not
         XF_NONE, else a copy of x)"""
         mom = ops.moments(x, st, xf) if any(t.moments for t in ts) else None
         hists = {tau: ops.chanhist(x, st, xf, tau) for tau in dict.fromkeys(t.tau for t in ts if t.chanhist)}
+        cov = ops.chancov(x, st, xf) if any(t.chancov for t in ts) else None
         fmap = None
         for t in ts:
             f = None
@@ -224,10 +232,12 @@ class Engine:
                     if not fmap.is_contiguous():
                         fmap = ops.map_snapshot(fmap)
                 f = fmap
+            kw = {}
             if t.chanhist:
-                t.sink(mom if t.moments else None, f, chanhist=hists[t.tau])
-            else:
-                t.sink(mom if t.moments else None, f)
+                kw["chanhist"] = hists[t.tau]
+            if t.chancov:
+                kw["chancov"] = cov
+            t.sink(mom if t.moments else None, f, **kw)
 
     def _mean_abs(self, t: torch.Tensor) -> torch.Tensor:
         B, Cc = t.shape[0], t.shape[-1]

@@ -963,6 +963,55 @@ def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, 
     return hist, nzero, absmax
 
 
+CHANCOV_WS_BYTES = 64 << 20  # ceiling of chancov()'s workspace
+
+
+def chancov_chunks(B: int, HW: int, Cc: int, tile: int = 128) -> int:
+    """pixel chunks per image of chancov(): B * nchunk * (tile pairs of the upper triangle) workgroups near _GN_TARGET, a chunk
+    no shorter than one 32-pixel step, the workspace (per (image, chunk): one fp32 tile^2 per pair and one float64 row per
+    tile) at most CHANCOV_WS_BYTES -- unless one chunk per image already exceeds it -- and every chunk non-empty"""
+    tiles = (Cc + tile - 1) // tile
+    pairs = tiles * (tiles + 1) // 2
+    row_bytes = 4 * (pairs * tile * tile + 2 * tiles * tile)
+    nch = max(1, min(_GN_TARGET // max(B * pairs, 1), HW // 32, CHANCOV_WS_BYTES // (B * row_bytes)))
+    per = (HW + nch - 1) // nch
+    return (HW + per - 1) // per
+
+
+def chancov(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE):
+    """channel covariance and mean of y = XF(x) over batch and pixels in one read of x, no tensor materialised: (cov float64
+    [C, C], mean float64 [C]) on the device.  cov is unbiased (N - 1, N = B * H * W), bitwise symmetric, and exactly 0 in the
+    row, column and variance of a constant channel; sums are taken of y minus the tensor's first pixel row, so a mean far above
+    sigma costs no digits; products are split-bf16 on the matrix pipe (csrc/chancov.hip), the merge is float64 in a fixed order:
+    two calls agree bitwise.  x, stats and xf as in moments().  The workspace rule is chancov_chunks(): at most 64 MB at every
+    shape of the shipped model (tools/launch_shapes.py).  Nothing synchronises the host."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"chancov: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"chancov: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    if (stats is None) != (xf == XF_NONE):
+        raise ValueError("chancov: a GroupNorm transform (xf) needs its stats and stats need an xf")
+    if stats is not None:
+        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
+            raise ValueError(f"chancov: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
+    HW = H * W
+    if B * HW < 2:
+        raise ValueError(f"chancov: a covariance needs at least two rows, got B * H * W = {B * HW}")
+    nch = chancov_chunks(B, HW, Cc)
+    dev = x.device
+    n = C.c_int64(0)
+    lib.call("vae_chancov_workspace", B, HW, Cc, nch, C.byref(n))
+    ws = torch.empty((n.value,), device=dev, dtype=torch.float32)
+    cov = torch.empty((Cc, Cc), device=dev, dtype=torch.float64)
+    mean = torch.empty((Cc,), device=dev, dtype=torch.float64)
+    lib.call("vae_chancov_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
+             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_chancov_final", _p(ws), B, HW, Cc, nch, _p(cov), _p(mean), _stream())
+    return cov, mean
+
+
 def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """per-image quality metrics of `pred` against `target` (evaluate.py's Average MSE / PSNR / SSIM) in one read of both: a
     float64 device tensor [B, 3] = [sum (pred - target)^2, sum (u(pred) - u(target))^2 with u(x) = clamp((x + 1) / 2, 0, 1),
