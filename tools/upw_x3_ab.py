@@ -5,7 +5,8 @@ direction the operands are filled once; every library builds its own transformed
 vae_wino_weight_bytes, or of 4 x vae_wino_weight_floats where a library does not have that query) and launches vae_igemm_rows
 into its own output.  Reported per layer and direction:
   * the off arm's output and U against the parent's BIT FOR BIT (the off build is the parent's kernel);
-  * two launches of the new arm bit for bit;
+  * two launches of the new arm bit for bit; the new arm's output against the parent's bit for bit, reported (it holds when the new
+    build changes the tiling and not the sums: the workgroup width, off arm = `make -C csrc upw_nb2`);
   * the error of the new and the off arm against float64 on a corner: the first 8 output channels of the first 8 x 8 output pixels
     of image 0 (a float64 convolution of the crop that reaches them, on the device), on the scale of that corner's max;
   * the time of vae_igemm_rows per arm, alternating launch by launch (the order reversed every round) with device events (warm-up,
@@ -14,7 +15,9 @@ into its own output.  Reported per layer and direction:
     under the split build).
 Layers: the three upsamplers of the fp32 step (256^2, batch 16): 512 -> 512 at 32^2 and 64^2, 256 -> 256 at 128^2 (low resolution).
 
-usage: python tools/upw_x3_ab.py NEW.so OFF.so PARENT.so [--launches 20] [--out FILE]"""
+--rotate: the opening arm moves on by one every round (N O P, O P N, ...).
+
+usage: python tools/upw_x3_ab.py NEW.so OFF.so PARENT.so [--launches 20] [--rotate] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -71,7 +74,7 @@ def _stats(ms):
     return {"median_ms": round(statistics.median(ms), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
 
 
-def _alternate(calls, launches):
+def _alternate(calls, launches, rotate=False):
     """time the calls, alternating launch by launch -> per call the list of its times in ms.  The order is reversed every round
     (N O P, P O N, ...): a launch reads 3-6 % slower right behind a launch of the split kernel than behind one of the exact kernel
     (identical code in two seats of a fixed order differed by that much), and this way the first and the last arm meet the same
@@ -82,6 +85,8 @@ def _alternate(calls, launches):
     ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)] for _ in calls]
     for k in range(launches):
         order = range(len(calls)) if k % 2 == 0 else range(len(calls) - 1, -1, -1)
+        if rotate:  # the opening arm moves on by one every round (N O P, O P N, ...)
+            order = [(k + j) % len(calls) for j in range(len(calls))]
         for i in order:
             ev[i][k][0].record()
             calls[i]()
@@ -94,6 +99,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs=3, help="NEW.so OFF.so PARENT.so")
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--rotate", action="store_true", help="rotate the opening arm every round")
     ap.add_argument("--out", default="")
     arg = ap.parse_args()
     dlls = [_open(s) for s in arg.libs]
@@ -132,14 +138,15 @@ def main():
             row = {"channels": Ch, "low_res_map": H, "batch": B, "direction": "dgrad" if dgrad else "forward",
                    "wu_bytes": {nm: int(t.numel() * 4) for nm, t in zip(NAMES, wus)},
                    "off_bitwise_equal_to_parent": bool(torch.equal(bits(outs[1]), bits(outs[2])) and torch.equal(bits(wus[1]), bits(wus[2]))),
+                   "new_bitwise_equal_to_parent": bool(torch.equal(bits(outs[0]), bits(outs[2]))),
                    "new_two_launches_bitwise_equal": bool(torch.equal(bits(outs[0]), bits(again)))}
             ref = _corner_f64(src, w, dgrad)
             for i in (0, 1):
                 row[f"{NAMES[i]}_err_of_corner_max"] = float((outs[i][0, :SUB, :SUB, :SUB].double() - ref).abs().max() / ref.abs().max())
             ok = ok and row["off_bitwise_equal_to_parent"] and row["new_two_launches_bitwise_equal"]
-            for nm, ms in zip(NAMES, _alternate([lambda i=i: call(i) for i in range(3)], arg.launches)):
+            for nm, ms in zip(NAMES, _alternate([lambda i=i: call(i) for i in range(3)], arg.launches, arg.rotate)):
                 row[nm] = _stats(ms)
-            for nm, ms in zip(NAMES, _alternate([lambda i=i: weights(i) for i in range(3)], arg.launches)):
+            for nm, ms in zip(NAMES, _alternate([lambda i=i: weights(i) for i in range(3)], arg.launches, arg.rotate)):
                 row[nm + "_weights"] = _stats(ms)
             row["new_over_parent"] = round(row["new"]["median_ms"] / row["parent"]["median_ms"], 4)
             row["off_over_parent"] = round(row["off"]["median_ms"] / row["parent"]["median_ms"], 4)

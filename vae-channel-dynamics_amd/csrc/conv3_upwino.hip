@@ -39,16 +39,29 @@
 // VAE_UPW_PRIO 1 (default): in the dgrad instantiation waves 4..7 (the second-dispatched wave of every SIMD, which multiplies first
 // and stages behind it) run the loop at s_setprio 1.  Measured per instantiation and wave half (tools/wino_seat_ab.py,
 // profiles/wino4_seat_measured.json): the dgrad 1.4-1.8 % faster, the forward 0.5-1.0 % slower with it, waves 0..3 no difference.
+// Re-measured with four channel blocks per workgroup (profiles/upw_wide_measured.json): the dgrad up to 2 % faster, the forward
+// 0.4-2.7 % slower with it.
 #ifndef VAE_UPW_PRIO
 #define VAE_UPW_PRIO 1
 #endif
 // U images up to this many bytes put the channel blocks of a spatial tile on one XCD (wino::xcd_spatial): of the step's layers the
-// 256-channel one (2.4 MB as fp32, 3.5 MB as planes)
+// 256-channel one (2.4 MB as fp32, 3.5 MB as planes).  Re-measured with four channel blocks per workgroup: 16 MB (the four channel
+// tiles of a 512-channel spatial tile on one XCD) 1.8-2.7 % slower at 512 -> 512, 64^2; 2 MB within 0.7 % everywhere.
 #ifndef VAE_UPW_XCD_LIMIT
 #define VAE_UPW_XCD_LIMIT (4 << 20)
 #endif
 #ifndef VAE_UPW_X3
 #define VAE_UPW_X3 1  // 1: split-bf16 products from bf16 planes of U and V, 16 channels per step; 0: exact fp32 products, 8 channels per step (make upw_x3_off)
+#endif
+// 32-channel blocks per workgroup of the split loop, per instantiation: 4 (32 tiles x 128 output channels, one workgroup per CU) or 2
+// (32 x 64, two per CU: the loop as it was; make upw_nb2).  The V transform, its split and the V / halo LDS traffic are work per
+// (tile, input channel) that every channel tile of a spatial tile repeats; four blocks halve the repeats for the same matrix work
+// and the same bits.  Measured per launch 0.92-0.98 (forward) and 0.89-0.92 (dgrad) of two blocks (profiles/upw_wide_measured.json).
+#ifndef VAE_UPW_NB_FWD
+#define VAE_UPW_NB_FWD 4
+#endif
+#ifndef VAE_UPW_NB_DG
+#define VAE_UPW_NB_DG 4
 #endif
 #if VAE_UPW_X3
 #include "bf16_frag.h"
@@ -341,11 +354,20 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 //   * K % 16 == 8: channels >= K of the last chunk are zero planes in U AND zero in V (the halo loads of that channel octet are
 //     masked: with Cs > K the memory behind channel K holds anything, and 0 x NaN is NaN).
 // Halo staging (two f32x4 per staging thread and chunk), the two copies of the loop, one barrier per step, the seating of the
-// ninth position and the epilogue are the exact loop's.  LDS: two V buffers 55,296 B + two halo buffers (forward 7,680 B, dgrad
-// 23,040 B): two workgroups per CU in both instantiations.
+// ninth position and the epilogue are the exact loop's with two channel blocks per workgroup (upw_nb<DG>() == 2).  LDS: two V
+// buffers 55,296 B + two halo buffers (forward 7,680 B, dgrad 23,040 B): two workgroups per CU in both instantiations.
+// Four channel blocks (upw_nb<DG>() == 4, the default): a wave multiplies the A planes of its position against four blocks of U
+// planes, each set re-requested behind the six MFMAs that consumed it (24 MFMAs per wave and step; 80 accumulator and 60 U-plane
+// registers, 188 / 190 in all, no scratch); the ninth position's four blocks sit on waves 4..7, one per SIMD (30 MFMAs there, 54
+// per SIMD); one workgroup per CU by registers, same LDS; the epilogue goes through the one image four times.
 constexpr int XBK = 16;                    // channels per step
 constexpr int XPL = NPOS * UTL * XBK;      // bf16 per V plane (9216 B)
 constexpr int XSV = 3 * XPL;               // bf16 per V buffer (27,648 B)
+template <bool DG>
+constexpr int upw_nb() {
+  return DG ? VAE_UPW_NB_DG : VAE_UPW_NB_FWD;
+}
+static_assert((upw_nb<false>() == 2 || upw_nb<false>() == 4) && (upw_nb<true>() == 2 || upw_nb<true>() == 4), "VAE_UPW_NB_*: 2 or 4");
 template <bool DG>
 constexpr int upw_lds_bytes() {
   constexpr int used = 2 * XSV * 2 + 2 * (DG ? UHD : UHF) * XBK * 4;
@@ -403,8 +425,10 @@ __global__ __launch_bounds__(256) void upwino_weights_kernel(const float* __rest
 }
 
 template <bool DG>
-__global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, const u16* __restrict__ U, int tiles_x, int tiles_y, int xcd_sp) {
-  constexpr int WBN = 32 * UNB;           // output channels per workgroup
+__global__ __launch_bounds__(UNT, upw_nb<DG>() > 2 ? 2 : 4) void conv3_upwino_kernel(vae_igemm_args p, const u16* __restrict__ U, int tiles_x, int tiles_y, int xcd_sp) {
+  constexpr int NB = upw_nb<DG>();        // 32-channel blocks per workgroup
+  constexpr bool WIDE = NB > 2;           // the ninth position's NB blocks on waves 4 .. 4 + NB - 1, blocks at or beyond N skipped
+  constexpr int WBN = 32 * NB;            // output channels per workgroup
   constexpr int HW_ = DG ? 2 * UTW + 2 : UTW + 2;  // halo width in pixels
   constexpr int HP = DG ? UHD : UHF;      // halo pixels
   constexpr int XSH = HP * XBK;           // floats per halo buffer
@@ -412,10 +436,6 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   float* const sH = upw_lds + XSV;                                 // [2][XSH], behind the 2 XSV bf16 of sV
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;  // wave = position 0..7 of the 3 x 3 transform domain
-  // position 8: channel block 0 on wave xw0, block 1 on wave xw0 + 1
-  const int xw0 = (blockIdx.x & 1) * 2;
-  const bool extra = wave == xw0 || wave == xw0 + 1;  // uniform per wave
-  const int xnb = wave - xw0;
   const int lr = lane & 31, lh = lane >> 5;
   const vae_conv_geom g = p.g;
   const int tilesN = (p.N + WBN - 1) / WBN;
@@ -423,6 +443,15 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   const int b = wg.b;
   const int y0 = wg.ty * UTH, x0 = wg.tx * UTW, n0 = wg.tn * WBN;  // low-resolution origin of the tile
   const int nsteps = upw_chunks(p.K);
+  // blocks of this channel tile that reach below N (uniform per workgroup).  A block wholly at or beyond N gets no MFMAs and no
+  // epilogue pass, and its U requests are out of range in every lane; the ragged block is masked lane by lane (BUF_OOB)
+  const int nlive = WIDE ? min(NB, (p.N - n0 + 31) >> 5) : NB;
+  // position 8: channel block q on wave xw0 + q.  Two blocks: waves 0, 1 in even workgroups, 2, 3 in odd ones (two co-resident
+  // workgroups then load the SIMDs alike).  Four blocks, one workgroup per CU: waves 4..7, one per SIMD, which multiply first
+  // and own no V transform
+  const int xw0 = WIDE ? 4 : (blockIdx.x & 1) * 2;
+  const int xnb = wave - xw0;
+  const bool extra = WIDE ? (wave >= 4 && xnb < nlive) : (wave == xw0 || wave == xw0 + 1);  // uniform per wave
 
   // ---- halo role: pixel hp of the chunk's halo, channel octet hq: loaded once per chunk, stored to sH two steps ahead.  An octet
   // at or beyond K is not loaded (zeros): K is a multiple of 8, so this is the whole K tail ----
@@ -502,26 +531,29 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 
   // ---- U planes of this wave's position: [step][pos][plane][n0 + 32 nb + lr][8 lh .. 8 lh + 7], L2 -> registers one step ahead ----
   const auto rsU = VAE_BUF_RSRC(U, upw_u_bytes(p.K, p.N));
-  unsigned bvo[UNB];
+  unsigned bvo[NB];
 #pragma unroll
-  for (int q = 0; q < UNB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? (unsigned)(((n0 + q * 32 + lr) * XBK + lh * 8) * 2) : BUF_OOB;
+  for (int q = 0; q < NB; ++q) bvo[q] = (n0 + q * 32 + lr < p.N) ? (unsigned)(((n0 + q * 32 + lr) * XBK + lh * 8) * 2) : BUF_OOB;
   const unsigned bpl = upw_plane_bytes(p.N);
-  const unsigned bvx = extra ? bvo[xnb & 1] : BUF_OOB;  // the ninth position's block (waves without one request nothing)
-  // ONE register set, refilled behind the MFMAs that consume it (conv3_wino.hip); every step issues the same 3 (UNB + 1) requests
+  // the ninth position's block (waves without one request nothing).  (Written out for four blocks: a lambda shared with the line
+  // above moved hipcc's register allocation of the two-block build away from the measured one)
+  const unsigned bvw = (n0 + xnb * 32 + lr < p.N) ? (unsigned)(((n0 + xnb * 32 + lr) * XBK + lh * 8) * 2) : BUF_OOB;
+  const unsigned bvx = extra ? (WIDE ? bvw : bvo[xnb & 1]) : BUF_OOB;
+  // ONE register set, refilled behind the MFMAs that consume it (conv3_wino.hip); every step issues the same 3 (NB + 1) requests
   // in code every wave runs (beyond the last chunk the last one again, never used; waves without a ninth-position block request
   // out of range)
-  bf16x8 bq[UNB + 1][3];
+  bf16x8 bq[NB + 1][3];
   auto load_b3 = [&](int step, int i) __attribute__((always_inline)) {
     const int st = min(step, nsteps - 1);
-    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)((st * NPOS + (i < UNB ? wave : 8)) * 3) * bpl);
+    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)((st * NPOS + (i < NB ? wave : 8)) * 3) * bpl);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
-      bq[i][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsU, i < UNB ? bvo[i < UNB ? i : 0] : bvx, so + (unsigned)pl * bpl, 0));
+      bq[i][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsU, i < NB ? bvo[i < NB ? i : 0] : bvx, so + (unsigned)pl * bpl, 0));
   };
 
-  f32x16 acc[UNB], accx;
+  f32x16 acc[NB], accx;
 #pragma unroll
-  for (int nb = 0; nb < UNB; ++nb)
+  for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[nb][e] = 0.f;
 #pragma unroll
@@ -529,7 +561,7 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 
   // prologue: halo(0), halo(1) in LDS, V(0) from halo(0); halo(2) and the U planes of step 0 in registers
 #pragma unroll
-  for (int i = 0; i <= UNB; ++i) load_b3(0, i);
+  for (int i = 0; i <= NB; ++i) load_b3(0, i);
   {
     f32x4 h0[2], h1[2];
     load_halo_into(0, h0);
@@ -547,9 +579,11 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) a[pl] = frag_direct(&cV[pl * XPL + wave * UTL * XBK + afrag]);
 #pragma unroll
-    for (int nb = 0; nb < UNB; ++nb) {
+    for (int nb = 0; nb < NB; ++nb) {
+      if (!WIDE || nb < nlive) {  // uniform per workgroup
 #pragma unroll
-      for (int t = 0; t < 6; ++t) acc[nb] = mma_x3_term(t, a, bq[nb], acc[nb]);
+        for (int t = 0; t < 6; ++t) acc[nb] = mma_x3_term(t, a, bq[nb], acc[nb]);
+      }
       __builtin_amdgcn_sched_barrier(0);
       load_b3(s + 1, nb);
       __builtin_amdgcn_sched_barrier(0);
@@ -558,10 +592,10 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) a[pl] = frag_direct(&cV[pl * XPL + 8 * UTL * XBK + afrag]);
 #pragma unroll
-      for (int t = 0; t < 6; ++t) accx = mma_x3_term(t, a, bq[UNB], accx);
+      for (int t = 0; t < 6; ++t) accx = mma_x3_term(t, a, bq[NB], accx);
     }
     __builtin_amdgcn_sched_barrier(0);
-    load_b3(s + 1, UNB);
+    load_b3(s + 1, NB);
     __builtin_amdgcn_sched_barrier(0);
   };
   auto stage_next = [&](int s, int par) __attribute__((always_inline)) {
@@ -607,7 +641,8 @@ __global__ __launch_bounds__(UNT, 4) void conv3_upwino_kernel(vae_igemm_args p, 
   const size_t obytes = (size_t)g.Ho * g.Wo * p.ldc * 4u;
   const auto rsC = VAE_BUF_RSRC(p.C + (int64_t)b * g.Ho * g.Wo * p.ldc, obytes);
 #pragma unroll
-  for (int nb = 0; nb < UNB; ++nb) {
+  for (int nb = 0; nb < NB; ++nb) {
+    if (WIDE && nb >= nlive) break;  // uniform per workgroup
     if (nb > 0) __syncthreads();  // the previous block's reads are done
     wino::spill_acc(sM, wave, UMLD, acc[nb], lr, lh);
     if (wave == xw0 + nb) wino::spill_acc(sM, 8, UMLD, accx, lr, lh);  // the ninth position's block nb
@@ -702,7 +737,12 @@ int launch_conv3_upwino(const vae_igemm_args& a, const float* U, hipStream_t st)
   const bool dg = g.mode == VAE_MODE_UP2X_DGRAD;
   const int Hl = dg ? g.Ho : g.Hs, Wl = dg ? g.Wo : g.Ws;
   const int tx = Wl / UTW, ty = Hl / UTH;
-  const int tilesN = (a.N + 32 * UNB - 1) / (32 * UNB);
+#if VAE_UPW_X3
+  const int wbn = 32 * (dg ? upw_nb<true>() : upw_nb<false>());  // output channels per workgroup
+#else
+  const int wbn = 32 * UNB;
+#endif
+  const int tilesN = (a.N + wbn - 1) / wbn;
   const int64_t nt = (int64_t)tilesN * tx * ty * g.B;
   if (nt > 0x7fffffffLL) return VAE_EINVAL;
   constexpr size_t xcd_u = (size_t)VAE_UPW_XCD_LIMIT;
