@@ -299,6 +299,22 @@ int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* scale, cons
                          int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float tau, uint32_t* ws, void* stream);
 int vae_chanhist_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* hist, int64_t* nzero,
                        float* absmax, void* stream);
+/* per-channel gradient metrics of one backward pass in one read of the pair (a, g): a module's NHWC output a and the gradient g
+ * of the loss with respect to it (monitor.py's mean_abs_gradient_per_channel / abs_max_gradient_per_channel /
+ * gain_gradient_per_channel / taylor_saliency_per_channel), csrc/changrad.hip.  a and g: [B][HW] pixel rows of C contiguous
+ * channels, each fp32 or bf16 (a_bf16 / g_bf16) with its own pixel stride lda / ldg >= C in elements; nchunk as
+ * vae_moments_partial.  B * HW must stay below 2^31.
+ * vae_changrad_workspace: *nwords = 32-bit words of ws for this shape (exactly what the partial pass writes); needs no GPU.
+ * partial: ws [C][B * nchunk][3] = per (c, b, chunk) the fp32 sum |g|, the fp32 sum a g (each product rounded once) and the
+ * largest |g| bit pattern; plain stores.
+ * final: float64 in a fixed order.  sums [3][C]: row 0 = sum |g| / (B * HW), row 1 = sum_b P[b, c] with P = the image's sum a g,
+ * row 2 = sum_b |P[b, c]| / B; absmax [C] = max |g| (NaN if the channel holds one).  No atomics, no zero-fill: repeated
+ * launches are bitwise identical. */
+int vae_changrad_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords);
+int vae_changrad_partial(const void* a, int32_t a_bf16, int32_t lda, const void* g, int32_t g_bf16, int32_t ldg, int32_t B,
+                         int32_t HW, int32_t C, int32_t nchunk, uint32_t* ws, void* stream);
+int vae_changrad_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* sums, float* absmax,
+                       void* stream);
 /* channel covariance and mean of y = XF(x) over the N = B * HW rows of an NHWC activation in one read (monitor.py's
  * channel_covariance_matrix / channel_correlation_matrix / max_abs_correlation_per_channel / effective_rank), csrc/chancov.hip.
  * x, x_bf16, scale, shift, xf, ld, nchunk: exactly as vae_moments_partial.  The sums are taken of z = fp32(y - K) with

@@ -41,6 +41,20 @@ Four more answer "which channels carry the same signal" (CHANCOV_METRICS, any la
 ONE covariance per forward: torch.cov in the hook (compute_metrics), ONE ops.chancov pass on a device-served layer.  A layer
 keeps a running float64 sum and a forward count, not a list; step() averages it over the forwards (device-served: across
 ranks too), brings it to the host in one transfer and derives the rest in float64 with correlation_summary().
+
+Four metrics of the BACKWARD pass, valid only at the capture point `output_grad` (CHANGRAD_METRICS; layer id
+`f"{name}.output_grad"`), with a the module's output, g the gradient of the loss with respect to it as the backward carries it
+(the 1 / gradient_accumulation_steps factor included, rank-local) and N = B * H * W: `mean_abs_gradient_per_channel` (sum |g| / N),
+`abs_max_gradient_per_channel` (max |g|, NaN if the channel holds one), `gain_gradient_per_channel` (sum_b sum_p a g: dL/ds_c at
+s_c = 1 for an output multiplied by a per-channel gain, minus the first-order change of the loss when the channel is zeroed) and
+`taylor_saliency_per_channel` ((1 / B) sum_b |sum_p a g|, the Taylor criterion of Molchanov et al. 2017 without the per-layer
+normalisation).  A channel with tiny |A| that still receives gradient is recoverable; one without is dead.  Values are buffered
+once per backward pass that computes that gradient (an eval forward buffers nothing, a micro-batch of an accumulated update one
+entry).  A plain torch module gets a forward hook that keeps the output and a tensor hook on it (compute_grad_metrics); an
+engine module gets Engine.add_grad_tracker, whatever `device_metrics` says (no torch hook sees the engine's inner gradients):
+ONE ops.changrad pass over the pair per backward.  step() takes the unweighted mean of the three sums over the buffered passes
+and the maximum of the maxima (a NaN stays); across ranks the sums are averaged and the maxima maxed on their bit patterns, with
+one host transfer per layer.
 """
 import logging
 from collections import defaultdict
@@ -65,6 +79,14 @@ CORR_METRIC = "channel_correlation_matrix"
 MAXCORR_METRIC = "max_abs_correlation_per_channel"
 RANK_METRIC = "effective_rank"
 CHANCOV_METRICS = (COV_METRIC, CORR_METRIC, MAXCORR_METRIC, RANK_METRIC)  # accepted beside KNOWN_METRICS; one covariance serves all
+MEANGRAD_METRIC = "mean_abs_gradient_per_channel"
+ABSMAXGRAD_METRIC = "abs_max_gradient_per_channel"
+GAINGRAD_METRIC = "gain_gradient_per_channel"
+SALIENCY_METRIC = "taylor_saliency_per_channel"
+# valid only at GRAD_POINT; one pass over (output, gradient) serves all (the first, third and fourth are the rows of its sums)
+CHANGRAD_METRICS = (MEANGRAD_METRIC, ABSMAXGRAD_METRIC, GAINGRAD_METRIC, SALIENCY_METRIC)
+GRAD_POINT = "output_grad"
+ZERO_GRADIENT_THRESHOLD = 0.0  # default of tracking.zero_gradient_threshold: a channel whose mean |g| is not above it got no gradient
 REDUNDANCY_THRESHOLD = 0.95  # default of tracking.redundancy_threshold: |rho| above it marks a redundant pair / channel
 
 
@@ -133,6 +155,26 @@ def channel_covariance(tensor: torch.Tensor) -> torch.Tensor:
     return torch.cov(yc).reshape(yc.shape[0], yc.shape[0])
 
 
+def compute_grad_metrics(a: torch.Tensor, g: torch.Tensor):
+    """what ops.changrad computes, with torch on the tensors' device: (sums float64 [3, C], absmax fp32 [C]); the rows of sums are
+    mean |g| over batch and all trailing axes, the gain gradient sum_b sum_p a g and the saliency (1 / B) sum_b |sum_p a g|.
+    Channel is dim 1 (as _per_channel); a tensor without a channel axis is one channel of one image.  The stored values
+    (whatever their dtype) are widened exactly, so every product is exact and every sum float64."""
+    a, g = a.detach(), g.detach()
+    if tuple(a.shape) != tuple(g.shape):
+        raise ValueError(f"output {tuple(a.shape)} and its gradient {tuple(g.shape)} differ")
+    if a.ndim >= 2:
+        a3, g3 = a.reshape(a.shape[0], a.shape[1], -1), g.reshape(g.shape[0], g.shape[1], -1)
+    else:
+        a3, g3 = a.reshape(1, 1, -1), g.reshape(1, 1, -1)
+    g64 = g3.double()
+    P = (a3.double() * g64).sum(dim=2)  # [B, C]
+    n = g3.shape[0] * g3.shape[2]
+    sums = torch.stack([g64.abs().sum(dim=(0, 2)) / n, P.sum(dim=0), P.abs().sum(dim=0) / g3.shape[0]])
+    absmax = g3.float().abs().amax(dim=(0, 2))  # NaN propagates
+    return sums, absmax
+
+
 def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshold: float = NEAR_ZERO_THRESHOLD) -> Dict[str, Any]:
     """slow-path formulas, identical to monitor.py:56-80; the three CHANHIST_METRICS are what ops.chanhist computes.  Each of
     the CHANCOV_METRICS named gets the forward's float64 covariance (one tensor, shared, on the tensor's device): step()
@@ -193,6 +235,26 @@ class _ChanHist:
         self.t = t
 
 
+class _ChanGrad:
+    """a buffered per-backward (sums float64 [3, C], absmax fp32 [C]) pair (ops.changrad on an engine layer,
+    compute_grad_metrics in a hook; resolved in step()), shared by the CHANGRAD_METRICS the layer tracks"""
+    __slots__ = ("t",)
+
+    def __init__(self, t: tuple):
+        self.t = t
+
+
+class _GradHookHandle:
+    """the forward hook of an `output_grad` target on a plain module; remove() also silences tensor hooks already placed"""
+
+    def __init__(self, handle, state: dict):
+        self._h, self._state = handle, state
+
+    def remove(self):
+        self._state["on"] = False
+        self._h.remove()
+
+
 class _CovSum:
     """a layer's running float64 sum of per-forward channel covariances and their count, shared by the CHANCOV_METRICS the
     layer tracks (resolved in step()); device_served: filled by ops.chancov, and averaged across ranks like the other
@@ -233,6 +295,7 @@ class ActivityMonitor:
         self.sync_across_ranks = bool(self.config.get("sync_across_ranks", True))
         self.near_zero_threshold = float(self.config.get("near_zero_threshold", NEAR_ZERO_THRESHOLD))
         self.redundancy_threshold = float(self.config.get("redundancy_threshold", REDUNDANCY_THRESHOLD))
+        self.zero_gradient_threshold = float(self.config.get("zero_gradient_threshold", ZERO_GRADIENT_THRESHOLD))
         if self.config.get("enabled", False):
             self._register_hooks()
             logger.info(f"ActivityMonitor initialized for {len(self.target_layers_config)} target(s) "
@@ -268,6 +331,34 @@ class ActivityMonitor:
                     buf[name].append(_Moments(mom))
         return sink
 
+    def _grad_sink(self, layer_id: str, metrics: List[str]) -> Callable:
+        """sink of an `output_grad` target: one (sums, absmax) pair per backward pass, listed under every metric asked for"""
+        def sink(sums: torch.Tensor, absmax: torch.Tensor):
+            entry = _ChanGrad((sums, absmax))
+            buf = self.hook_collected_buffer[layer_id]
+            for name in metrics:
+                buf[name].append(entry)
+        return sink
+
+    def _grad_hook(self, layer_id: str, metrics: List[str], state: dict) -> Callable:
+        """forward hook of an `output_grad` target on a plain module: keeps the output and, if a gradient will reach it, places
+        a tensor hook that computes the metrics when it does (an eval forward under no_grad places none)"""
+        sink = self._grad_sink(layer_id, metrics)
+
+        def fn(module, hook_input, hook_output):
+            out = hook_output
+            if not (isinstance(out, torch.Tensor) and out.requires_grad and state["on"]):
+                return
+
+            def on_grad(grad):
+                if state["on"]:
+                    try:
+                        sink(*compute_grad_metrics(out, grad))
+                    except Exception as e:  # metric failures are swallowed, as compute_metrics does
+                        logger.error(f"Error calculating gradient metrics for {layer_id}: {e}", exc_info=True)
+            out.register_hook(on_grad)
+        return fn
+
     def _map_due(self, layer_id: str) -> Callable[[], bool]:
         """a snapshot is taken while the buffer holds none: the first forward after the last step() (step() keeps values[0])"""
         def due():
@@ -299,14 +390,38 @@ class ActivityMonitor:
                 logger.warning("Skipping a target_layer entry with no name.")
                 continue
             layer_id = f"{name}.{point}"
-            metrics = conf.get("metrics", [FUSED_METRIC])
+            metrics = conf.get("metrics", list(CHANGRAD_METRICS) if point == GRAD_POINT else [FUSED_METRIC])
             try:
                 layer = _resolve(self.model, name)
-                if point not in ("input", "output"):
+                if point not in ("input", "output", GRAD_POINT):
                     logger.warning(f"Unknown capture_point '{point}' for layer {name}. Skipping.")
                     continue
                 engine_ref = getattr(layer, "_vae_engine", None)
                 engine = engine_ref() if engine_ref is not None else None
+                if point == GRAD_POINT:
+                    mlist = list(dict.fromkeys(metrics))
+                    bad = [m for m in mlist if m not in CHANGRAD_METRICS]
+                    if bad or not mlist:
+                        logger.error(f"Capture point '{GRAD_POINT}' of layer {name} serves {CHANGRAD_METRICS}, not {bad or mlist}. "
+                                     f"Skipping.")
+                        continue
+                    if engine is not None:  # no torch hook sees the engine's inner gradients: device_metrics or not
+                        try:
+                            self.hooks.append(engine.add_grad_tracker(layer, self._grad_sink(layer_id, mlist), mlist))
+                        except ValueError as e:  # a GroupNorm, a module without a 4-D capture point: the engine says which
+                            logger.error(f"Could not register a gradient tracker for {layer_id}: {e} Skipping.")
+                            continue
+                        self.device_layers.append(layer_id)
+                        logger.info(f"Registered DEVICE gradient tracker for layer: {name} ({point}): {mlist}")
+                    else:
+                        state = {"on": True}
+                        self.hooks.append(_GradHookHandle(layer.register_forward_hook(self._grad_hook(layer_id, mlist, state)), state))
+                        logger.info(f"Registered FORWARD HOOK + TENSOR HOOK for layer: {name} ({point})")
+                    continue
+                bad = [m for m in metrics if m in CHANGRAD_METRICS]
+                if bad:
+                    logger.error(f"Metrics {bad} of layer {name} need capture_point '{GRAD_POINT}', not '{point}'. Skipping.")
+                    continue
                 if engine is not None and list(metrics) == [FUSED_METRIC]:
                     self.hooks.append(engine.add_tracker(layer, point, self._sink(layer_id)))
                     self.fused_layers.append(layer_id)
@@ -420,6 +535,35 @@ class ActivityMonitor:
                              MAXCORR_METRIC: summary["max_abs"].astype(np.float32),
                              RANK_METRIC: float(summary["effective_rank"])}[metric]
 
+    def _changrad_to_host(self, metric_data: Dict[str, list]):
+        """the buffered (sums, absmax) pairs of a layer -> per backward pass the host vectors of each metric, in place: fp32 [C]
+        each.  Across ranks the sums are averaged like the mean |A| vectors and the maxima maxed on their bit patterns.  ONE
+        transfer: a float64 [passes, 4, C] tensor (fp32 maxima are exact in it)"""
+        rows: Dict[int, int] = {}  # id of a buffered pair -> its row
+        stack = []
+        for values in metric_data.values():
+            for v in values:
+                if isinstance(v, _ChanGrad) and id(v) not in rows:
+                    rows[id(v)] = len(stack)
+                    stack.append(v.t)
+        if not stack:
+            return
+        sums = torch.stack([t[0] for t in stack])
+        amax = torch.stack([t[1] for t in stack]).contiguous()
+        world = self._world()
+        if world > 1:
+            self._same_forward_count(sums.shape[0], sums.device)
+            torch.distributed.all_reduce(sums)
+            sums = sums / world
+            # as integers the bit patterns of |g| order like the values, a NaN above every number: it survives the maximum
+            torch.distributed.all_reduce(amax.view(torch.int32), op=torch.distributed.ReduceOp.MAX)
+        host = torch.cat([sums, amax.double()[:, None, :]], dim=1).cpu().numpy()
+        col = {MEANGRAD_METRIC: 0, GAINGRAD_METRIC: 1, SALIENCY_METRIC: 2, ABSMAXGRAD_METRIC: 3}
+        for metric, values in metric_data.items():
+            for i, v in enumerate(values):
+                if isinstance(v, _ChanGrad):
+                    values[i] = host[rows[id(v)], col[metric]].astype(np.float32)
+
     def _to_host(self, values: list) -> list:
         """device vectors of the fused path -> list of np.float32 arrays with ONE transfer."""
         if values and all(isinstance(v, torch.Tensor) and v.is_cuda for v in values):
@@ -471,6 +615,7 @@ class ActivityMonitor:
                 self._device_to_host(metric_data)
             self._chanhist_to_host(metric_data)
             self._chancov_to_host(metric_data)
+            self._changrad_to_host(metric_data)
         for layer_id, metric_data in self.hook_collected_buffer.items():
             processed[layer_id] = {}
             for metric, values in metric_data.items():
@@ -503,6 +648,14 @@ class ActivityMonitor:
                         agg = np.mean(np.stack(values), axis=0)
                         log[key + "_overall_mean"] = np.mean(agg)
                         log[key + "_overall_max"] = np.max(agg)
+                    elif metric == ABSMAXGRAD_METRIC:  # the maximum over the buffered backward passes (a NaN stays)
+                        agg = np.max(np.stack(values), axis=0)
+                        log[key + "_overall_max"] = np.max(agg)
+                    elif metric in CHANGRAD_METRICS:  # the unweighted mean over them
+                        agg = np.mean(np.stack(values), axis=0)
+                        log[key + "_overall_mean"] = np.mean(agg)
+                        if metric != GAINGRAD_METRIC:
+                            log[key + "_overall_max"] = np.max(agg)
                     elif FUSED_METRIC in metric:
                         vals = self._to_host(values)
                         if all(isinstance(v, np.ndarray) for v in vals):
@@ -585,6 +738,15 @@ class ActivityMonitor:
                         add("abs_max_overall_max", float(np.max(arr)))
                         add("abs_max_overall_mean", float(np.mean(arr)))
                         add("abs_max_argmax_channel", int(np.argmax(arr)))
+                    elif metric in CHANGRAD_METRICS:
+                        kind = metric[:-len("_per_channel")]
+                        add(kind + "_overall_mean", float(np.mean(arr)))
+                        add(kind + "_overall_min", float(np.min(arr)))
+                        add(kind + "_overall_max", float(np.max(arr)))
+                        if metric == SALIENCY_METRIC:
+                            add(kind + "_argmax_channel", int(np.argmax(arr)))
+                        elif metric == MEANGRAD_METRIC:  # channels that received (next to) no gradient
+                            add(kind + "_zero_channels", int(np.sum(arr <= self.zero_gradient_threshold)))
                     elif metric == NEARZERO_METRIC:
                         add("near_zero_overall_mean", float(np.mean(arr)))
                         add("near_zero_overall_max", float(np.max(arr)))

@@ -12,6 +12,8 @@ subset of the ActivityMonitor metrics at a 4-D capture point the same way: one m
 histogram pass (ops.chanhist: magnitude histogram, near-zero count, max |A| per channel) per forward on the tensor a hook
 would have received, and one covariance pass (ops.chancov: the channel covariance behind the correlation, redundancy and
 effective-rank metrics), each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
+add_grad_tracker serves the backward pass: per backward of a module, one ops.changrad pass over (the output the forward kept, the
+gradient the tape carries to it) gives the per-channel gradient metrics (CHANGRAD_METRICS); it launches nothing unless registered.
 """
 from __future__ import annotations
 
@@ -33,6 +35,9 @@ CHANHIST_METRICS = ("log2_histogram_per_channel", "abs_max_activation_per_channe
 # one ops.chancov pass: (covariance, mean); the monitor derives the other three from the covariance
 CHANCOV_METRICS = ("channel_covariance_matrix", "channel_correlation_matrix", "max_abs_correlation_per_channel", "effective_rank")
 DEVICE_METRICS = MOMENT_METRICS + CHANHIST_METRICS + CHANCOV_METRICS + ("full_activation_map",)
+# one ops.changrad pass over (output, gradient of the loss with respect to it) per backward: add_grad_tracker only
+CHANGRAD_METRICS = ("mean_abs_gradient_per_channel", "abs_max_gradient_per_channel", "gain_gradient_per_channel",
+                    "taylor_saliency_per_channel")
 
 
 class _TrackHandle:
@@ -64,6 +69,8 @@ class Engine:
         self._vae = weakref.ref(vae)
         self._trackers: Dict[int, Dict[str, List[Callable]]] = {}
         self._mtrackers: Dict[int, Dict[str, List[_MetricTracker]]] = {}
+        self._gtrackers: Dict[int, Dict[str, List[Callable]]] = {}  # add_grad_tracker: id(module) -> {"output_grad": sinks}
+        self._rec = False  # the block that executes now records a backward (_enter): a tracked convolution keeps its output
         self._gtarget: Optional[torch.Tensor] = None
         self.reducer = None  # optional DP bucket reducer with .ready(low_offset)
         self._low: Dict[int, int] = {}
@@ -157,7 +164,8 @@ class Engine:
         live_in = self._live
         own = self._trains(*mods)
         self._live = live_in or own
-        return tape is not None and (live_in or own), live_in
+        self._rec = tape is not None and (live_in or own)
+        return self._rec, live_in
 
     def _g(self, p: Optional[nn.Parameter]):
         return None if p is None else self.arena.grad_view(p, self._gtarget)
@@ -192,6 +200,47 @@ class Engine:
         t = _MetricTracker(metrics, sink, map_due, near_zero_threshold)
         self._mtrackers.setdefault(id(module), {}).setdefault(point, []).append(t)
         return _TrackHandle(self._mtrackers, id(module), point, t)
+
+    def add_grad_tracker(self, module: nn.Module, sink: Callable, metrics: List[str]):
+        """any subset of CHANGRAD_METRICS at `module`'s output: sink(sums, absmax) = ops.changrad(output, dL/d output) once per
+        backward pass that computes that gradient -- nothing is computed for the tracker's sake: where a frozen prefix leaves
+        the gradient uncomputed, or no tape records (an eval forward), nothing is emitted.  A composite module gets a
+        pass-through closure on the tape right behind its own; a HipConv2d emits at the top of _conv_bwd from the output its
+        forward kept (a fused residual add is un-fused, as for an output tracker, so that the output exists)."""
+        from . import autoencoder as A
+        bad = [m for m in metrics if m not in CHANGRAD_METRICS]
+        if bad or not metrics:
+            raise ValueError(f"gradient trackers serve {CHANGRAD_METRICS}, not {list(metrics)}")
+        if isinstance(module, A.HipGroupNorm):
+            raise ValueError("HipGroupNorm: the GroupNorm output is never materialised and neither is its gradient; gradient "
+                             "metrics on a norm are not served (track the convolution it feeds, or the block around it)")
+        if not self.metric_trackable(module):
+            raise ValueError(f"{type(module).__name__}: no 4-D capture point the engine can reduce")
+        self._gtrackers.setdefault(id(module), {}).setdefault("output_grad", []).append(sink)
+        return _TrackHandle(self._gtrackers, id(module), "output_grad", sink)
+
+    def _gtracked(self, m):
+        d = self._gtrackers.get(id(m)) if self._gtrackers else None
+        return d.get("output_grad") if d else None
+
+    @staticmethod
+    def _emit_grad(sinks, out: torch.Tensor, d: torch.Tensor):
+        res = ops.changrad(out, d)
+        for s in list(sinks):
+            s(*res)
+
+    def _grad_point(self, m, out: torch.Tensor, tape):
+        """behind the backward closure(s) `m`'s forward has just appended (the tape is LIFO: this one runs first and receives
+        exactly dL/d out): only with a gradient tracker on m, a recording tape, and that gradient going to be computed"""
+        sinks = self._gtracked(m)
+        if not sinks or tape is None or not self._live:
+            return
+
+        def emit(d):
+            if d is not None:
+                self._emit_grad(sinks, out, d)
+            return d
+        tape.append(emit)
 
     @staticmethod
     def metric_trackable(module: nn.Module) -> bool:
@@ -332,7 +381,8 @@ class Engine:
         self._pre(m, make_in, src=(x if x.shape[-1] == ci else x[..., :ci], xf, st))
         sinks = self._tracked(m, "output")
         mts = self._mtracked(m, "output")
-        fuse_res = res is not None and not m._forward_hooks and not sinks and not mts
+        gts = self._gtracked(m)
+        fuse_res = res is not None and not m._forward_hooks and not sinks and not mts and not gts
         tb = None
         if sinks:
             ho, wo = ops.out_hw(kind, x.shape[1], x.shape[2])
@@ -359,6 +409,11 @@ class Engine:
             self._emit(mts, y)
         if m._forward_hooks:
             self._post(m, make_in, y, tracked_already=True)
+        if gts and self._rec:  # kept with the input, which the backward closure holds: _conv_bwd finds it there
+            kept = getattr(x, "_gy", None)
+            if kept is None:
+                kept = x._gy = {}
+            kept[id(m)] = y
         if res is not None and not fuse_res:
             y = ops.add(y, res)
         return y
@@ -375,6 +430,12 @@ class Engine:
         launched unless both are frozen, on the operands a full backward would give it (the bf16 gradient image below is made
         as if dx were wanted), so a trainable parameter's gradient does not depend on what else is frozen."""
         kind = getattr(m, "kind", "c1")
+        gts = self._gtracked(m)
+        if gts and dy is not None:
+            kept = getattr(x, "_gy", None)
+            y = kept.pop(id(m), None) if kept else None
+            if y is not None:
+                self._emit_grad(gts, y, dy)
         need_dw = self._trains(m)
         want_dx = need_dx and want_dx
         if not need_dw and not want_dx:
@@ -486,6 +547,7 @@ class Engine:
                     self._done(notify)  # an enclosing module whose parameters are all final now
                 return dx
             tape.append(bwd)
+        self._grad_point(r, out, tape)
         return out
 
     def _attention(self, a, x, tape, notify=True, after_conv3=False):
@@ -551,6 +613,7 @@ class Engine:
                     self._done(a)
                 return dx
             tape.append(bwd)
+        self._grad_point(a, out, tape)
         return out
 
     def _mid(self, mb, x, tape, after_conv3=False):
@@ -561,12 +624,14 @@ class Engine:
         h = self._seg(lambda t, tp: self._attention(mb.attentions[0], t, tp, notify=False, after_conv3=True), h, tape, mb.attentions[0])
         h = self._seg(lambda t, tp: self._resnet(mb.resnets[1], t, tp, notify=False), h, tape, mb.resnets[1])
         self._post(mb, lambda: x, h)
+        self._grad_point(mb, h, tape)
         return h
 
     def _sampler(self, s, x, tape):
         self._pre(s, lambda: x)
         y = self._plain_conv(s.conv, x, tape, owner=s)
         self._post(s, lambda: x, y)
+        self._grad_point(s, y, tape)
         return y
 
     def _updown_block(self, blk, x, tape, first_after_conv3=False):
@@ -580,6 +645,7 @@ class Engine:
         if extra is not None:
             h = self._seg(lambda t, tp: self._sampler(extra[0], t, tp), h, tape, extra[0])
         self._post(blk, lambda: x, h)
+        self._grad_point(blk, h, tape)
         return h
 
     def _norm_act_conv(self, owner, x, tape):
@@ -613,6 +679,7 @@ class Engine:
         h = self._mid(enc.mid_block, h, tape, after_conv3=True)  # behind down_blocks[-1]'s last resnet
         h = self._norm_act_conv(enc, h, tape)
         self._post(enc, lambda: x4[..., :3], h)
+        self._grad_point(enc, h, tape)
         return h
 
     def encode_nhwc(self, x4, tape):
@@ -631,6 +698,7 @@ class Engine:
         finally:
             self._ckpt = False
         self._post(dec, lambda: z, h)
+        self._grad_point(dec, h, tape)
         return h
 
     def decode_nhwc(self, z, tape):

@@ -963,6 +963,53 @@ def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, 
     return hist, nzero, absmax
 
 
+def changrad_chunks(B: int, HW: int, Cc: int) -> int:
+    """pixel chunks per image of changrad(): B * nchunk * (tiles of 256 channels) workgroups near _GN_TARGET, a chunk no shorter
+    than 16 pixels per pixel row of a workgroup, and every chunk non-empty"""
+    units, tile = (Cc // 4, 64) if Cc % 4 == 0 else (Cc, 256)
+    pr = max(1, 256 // min(tile, units))
+    tiles = (units + tile - 1) // tile
+    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
+    per = (HW + nch - 1) // nch
+    return (HW + per - 1) // per
+
+
+def _nhwc_ld(who: str, x: torch.Tensor) -> int:
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"{who}: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    return ld
+
+
+def changrad(a: torch.Tensor, g: torch.Tensor):
+    """per-channel gradient metrics of one backward pass in one read of a module's output `a` and the gradient `g` of the loss
+    with respect to it: (sums float64 [3, C], absmax fp32 [C]) on the device.  sums[0] = mean |g| over the N = B * H * W pixel
+    rows, sums[1] = sum_b sum_p a g (the gradient of a per-channel gain at 1), sums[2] = (1 / B) sum_b |sum_p a g| (the Taylor
+    saliency); absmax = max |g| (NaN if the channel holds one).  a and g: 4-D NHWC of one shape, each fp32 or bf16, channels
+    contiguous, each with its own pixel stride (a channel-prefix view is read in place).  Products are rounded once and summed in
+    fp32 inside a workgroup (csrc/changrad.hip), everything after is float64 in a fixed order: two calls agree bitwise.  Nothing
+    synchronises the host."""
+    for t in (a, g):
+        if t.dim() != 4 or not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"changrad: expected 4-D NHWC fp32 / bf16 CUDA tensors, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if tuple(a.shape) != tuple(g.shape) or a.device != g.device:
+        raise ValueError(f"changrad: output {tuple(a.shape)} on {a.device} and gradient {tuple(g.shape)} on {g.device} differ")
+    lda, ldg = _nhwc_ld("changrad", a), _nhwc_ld("changrad", g)
+    B, H, W, Cc = a.shape
+    HW = H * W
+    nch = changrad_chunks(B, HW, Cc)
+    dev = a.device
+    n = C.c_int64(0)
+    lib.call("vae_changrad_workspace", B, HW, Cc, nch, C.byref(n))
+    ws = torch.empty((n.value,), device=dev, dtype=torch.int32)
+    sums = torch.empty((3, Cc), device=dev, dtype=torch.float64)
+    absmax = torch.empty((Cc,), device=dev, dtype=torch.float32)
+    lib.call("vae_changrad_partial", _p(a), _b16(a), lda, _p(g), _b16(g), ldg, B, HW, Cc, nch, _p(ws), _stream())
+    lib.call("vae_changrad_final", _p(ws), B, HW, Cc, nch, _p(sums), _p(absmax), _stream())
+    return sums, absmax
+
+
 CHANCOV_WS_BYTES = 64 << 20  # ceiling of chancov()'s workspace
 
 
