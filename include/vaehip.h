@@ -560,6 +560,40 @@ int vae_dead_scan(const float* w, const int64_t* seg_off, const int32_t* seg_chu
 int vae_dead_scan_adaptive(const float* w, const int64_t* seg_off, const int32_t* seg_chunk0, int32_t nseg, int32_t nchunk, float thr,
                            int32_t use_fixed, const float* adaptive_thr, unsigned long long* part_counts,
                            unsigned long long* out_counts, void* stream);
+/* weight-side channel dynamics (tracking/weightdynamics.py), csrc/wdyn.hip: per output slice and per input slice of every tensor
+ * of a table, in one read of the four flat fp32 arenas w, g, m, v (parameters, gradients, Adam moments; one layout), six sums
+ * and a maximum: S_ww = sum w^2, S_gg = sum g^2, S_wg = sum w g, S_mm = sum m^2, S_gm = sum g m, S_uu = sum u^2 (in this
+ * order) and A = max |w|, with u = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps) in fp32 from the float-rounded constants of
+ * vae_adamw (bc1 = (float)(1 - beta1^step), bc2_sqrt = (float)sqrt(1 - beta2^step), (float)eps).  g == NULL, or m == v == NULL,
+ * select the modes w and w+g (mode 0 / 1; all four arrays: mode 2); a sum a mode cannot form is stored as NaN.
+ * Table: int64 [nseg][8] = {off, O, K, I, out0, in0, ws0, chunk0}, 16-byte aligned.  The tensor is [O][K][I] contiguous from
+ * element off of every arena (OHWI conv weight: K = kh kw; linear [out][in]: K = 1; 1-D: K = I = 1); off is a multiple of 4.
+ * out0 / in0: the tensor's first row of the output-slice / input-slice results (a tensor with I == 1 has no input slices);
+ * ws0: its first column row of ws; chunk0: its first chunk.  All four are running sums in table order, with
+ * chunks(t) = ceil(O / rpc), rpc whole rows per workgroup: fit = max(1, vae_wdyn_chunk() / (K I)), rpc = fit when I == 1 and
+ * min(8, fit) otherwise (a row longer than the chunk is one workgroup),
+ * and ws rows(t) = chunks(t) * I when I > 1.  Tensors may be listed in any order and must not overlap (the caller's to check:
+ * vaehip.weight_table.WeightTable does).  Nothing outside them is read, no arena is written.
+ * vae_wdyn_workspace: checks a HOST copy of the table (off >= 0 and off % 4 == 0, 0 < O, K, I and K I < 2^31, the running
+ * sums) and returns nchunk, the slice counts n_out / n_in and the 32-bit words of ws; needs no GPU.
+ * partial (table in device memory): one workgroup per chunk.  Row sums are complete inside it: out_sums [n_out][6] double
+ * (the fp32 value), out_absmax [n_out].  Column sums leave it as fp32 partials, ws [ws0 + chunk * I + i][7] words (six sums, max
+ * |w| bits), plain stores.  Inside a workgroup everything is fp32 in one association order (each product rounded once; the order
+ * is stated at the head of csrc/wdyn.hip: thread chain over (k, element), wave_reduce, the four waves' slots tile after tile,
+ * (r0 + r1) + (r2 + r3); columns: thread chain over rows and k, then the thread rows in order).
+ * final: one thread per input slice adds its tensor's chunks in chunk order in float64: in_sums [n_in][6], in_absmax [n_in];
+ * n_in == 0 launches nothing.  max |w| is exact, NaN if the slice holds one.  No atomics, no zero-fill: repeated launches are
+ * bitwise identical.
+ * Checked on the host, VAE_EINVAL and no launch: null pointers (g, m, v as the modes allow; m needs v and g), nseg <= 0, counts
+ * that do not add up (nchunk < nseg, n_out < nseg, n_in < 0, mode outside 0..2), a base pointer (w, g, m, v, ws, tab) that is
+ * not 16-byte aligned, step < 1 together with m; and in vae_wdyn_workspace the table's contents as above. */
+int vae_wdyn_chunk(void);
+int vae_wdyn_workspace(const int64_t* tab_host, int32_t nseg, int32_t* nchunk, int64_t* n_out, int64_t* n_in, int64_t* nwords);
+int vae_wdyn_partial(const float* w, const float* g, const float* m, const float* v, const int64_t* tab, int32_t nseg,
+                     int32_t nchunk, int64_t n_out, double beta1, double beta2, double eps, int32_t step, uint32_t* ws,
+                     double* out_sums, float* out_absmax, void* stream);
+int vae_wdyn_final(const uint32_t* ws, const int64_t* tab, int32_t nseg, int64_t n_in, int32_t mode, double* in_sums,
+                   float* in_absmax, void* stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,7 @@ from data_utils import load_and_preprocess_dataset, create_dataloader
 from models.sdxl_vae_wrapper import SDXLVAEWrapper
 from tracking.monitor import ActivityMonitor
 from tracking.deadneuron import DeadNeuronTracker
+from tracking.weightdynamics import CSV_FIELDS as WD_CSV_FIELDS, WeightDynamicsTracker
 from classification.classifier import RegionClassifier
 from intervention.nudger import InterventionHandler
 from vaehip.trainer import HipTrainer
@@ -485,6 +486,9 @@ def main():
     dnt_cfg = config.get("dead_neuron_tracking", {})
     dnt = DeadNeuronTracker(target_layer_classes, dnt_cfg.get("target_layer_names_for_raw_weights", []), threshold_dn,
                             mean_percentage_dn, dead_type_dn) if dnt_cfg.get("enabled", False) else None
+    wd_cfg = config.get("weight_dynamics", {}) or {}
+    # main rank only and no collective: after the gradient all-reduce every rank holds the same four arenas
+    wdt = WeightDynamicsTracker(wd_cfg) if wd_cfg.get("enabled", False) and is_main else None
     monitor_cfg = config.get("tracking", {})
     monitor = ActivityMonitor(vae_wrapper, monitor_cfg) if monitor_cfg.get("enabled", False) else None
     cls_cfg = config.get("classification", {})
@@ -547,6 +551,9 @@ def main():
             if not trainer.sync_gradients:  # micro-batch of an accumulated update (train.py:286,300)
                 continue
             global_step += 1
+            # after the update, before any intervention of this step: lr * u is the Adam part of the update just applied
+            if wdt and global_step % wdt.track_interval == 0:
+                mlog.log(wdt.track(core_vae, trainer.optimizer, global_step), global_step)
             activity_logs = {}
             if monitor and global_step % track_interval == 0:
                 activity_logs = monitor.step(global_step)
@@ -627,6 +634,13 @@ def main():
                     wr.writeheader()
                     wr.writerows(recs)
                 logger.info(f"Saved activation stats to {path}")
+        if wdt and wdt.history:
+            path = os.path.join(output_dir, "weight_dynamics_history.csv")
+            with open(path, "w", newline="") as f:
+                wr = csv.DictWriter(f, fieldnames=list(WD_CSV_FIELDS))
+                wr.writeheader()
+                wr.writerows(wdt.export_records())
+            logger.info(f"Saved weight dynamics to {path}")
         if dnt and dnt.percent_history:
             path = os.path.join(output_dir, "dead_neuron_percentage_history.csv")
             with open(path, "w", newline="") as f:

@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 22  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 23  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -142,6 +142,10 @@ SIGNATURES = {
     "vae_dead_scan_chunk": [],
     "vae_dead_scan": [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp],
     "vae_dead_scan_adaptive": [vp, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp],
+    "vae_wdyn_chunk": [],
+    "vae_wdyn_workspace": [vp, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)],
+    "vae_wdyn_partial": [vp, vp, vp, vp, vp, i32, i32, i64, f64, f64, f64, i32, vp, vp, vp, vp],
+    "vae_wdyn_final": [vp, vp, i32, i64, i32, vp, vp, vp],
 }
 
 

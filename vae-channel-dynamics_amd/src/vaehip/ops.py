@@ -1483,3 +1483,44 @@ def adamw_ranges(p, g, m, v, e: Optional[torch.Tensor], table, sqn: Optional[tor
     lib.call("vae_adamw_ranges", _p(p), _p(g), _p(m), _p(v), _p(e), _p(table.seg_off), _p(table.seg_chunk0), table.nseg, table.nchunk,
              _p(sqn), float(max_norm), float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step), float(ema_decay),
              _stream())
+
+
+def weight_dynamics(flat: torch.Tensor, grad: Optional[torch.Tensor], exp_avg: Optional[torch.Tensor],
+                    exp_avg_sq: Optional[torch.Tensor], table, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                    step: int = 1):
+    """per output slice and per input slice of every tensor of `table` (a weight_table.WeightTable, which checked itself when it
+    was built), in one read of the four flat fp32 arenas: raw (out_sums float64 [n_out, 6], in_sums float64 [n_in, 6], out_absmax
+    fp32 [n_out], in_absmax fp32 [n_in]) on the device.  The six sums are S_ww, S_gg, S_wg, S_mm, S_gm, S_uu with
+    u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps) the Adam direction after `step` updates; the maxima are max |w| (NaN if the slice
+    holds one).  grad None, or exp_avg and exp_avg_sq None, are the modes w and w+g: the sums they cannot form come out NaN.
+    fp32 in one fixed order inside a workgroup (csrc/wdyn.hip), float64 in chunk order after it: two calls agree bitwise.
+    Nothing synchronises the host, no arena is written."""
+    if (exp_avg is None) != (exp_avg_sq is None) or (exp_avg is not None and grad is None):
+        raise ValueError("weight_dynamics: the modes are w, w+g and w+g+m+v")
+    for name, t in (("flat", flat), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t is None:
+            continue
+        if t.dim() != 1 or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != flat.device:
+            raise ValueError(f"weight_dynamics: {name} must be a flat contiguous fp32 CUDA tensor on one device, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        if t.numel() < table.extent:
+            raise ValueError(f"weight_dynamics: {name} holds {t.numel()} elements, the table reaches {table.extent}")
+        if t.data_ptr() % 16:
+            raise ValueError(f"weight_dynamics: {name} is not 16-byte aligned")
+    if table.tab.device != flat.device:
+        raise ValueError(f"weight_dynamics: the table lives on {table.tab.device}, the arenas on {flat.device}")
+    if exp_avg is not None and int(step) < 1:
+        raise ValueError(f"weight_dynamics: step {step} with Adam moments (the bias corrections need step >= 1)")
+    mode = 2 if exp_avg is not None else (1 if grad is not None else 0)
+    dev = flat.device
+    # everything is checked: allocate
+    ws = torch.empty((max(table.nwords, 4),), device=dev, dtype=torch.int32)
+    out_sums = torch.empty((table.n_out, 6), device=dev, dtype=torch.float64)
+    out_absmax = torch.empty((table.n_out,), device=dev, dtype=torch.float32)
+    in_sums = torch.empty((table.n_in, 6), device=dev, dtype=torch.float64)
+    in_absmax = torch.empty((table.n_in,), device=dev, dtype=torch.float32)
+    lib.call("vae_wdyn_partial", _p(flat), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(table.tab), table.nseg, table.nchunk, table.n_out,
+             float(beta1), float(beta2), float(eps), int(step), _p(ws), _p(out_sums), _p(out_absmax), _stream())
+    if table.n_in:
+        lib.call("vae_wdyn_final", _p(ws), _p(table.tab), table.nseg, table.n_in, mode, _p(in_sums), _p(in_absmax), _stream())
+    return out_sums, in_sums, out_absmax, in_absmax

@@ -41,6 +41,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.sqnorm: Optional[torch.Tensor] = None
         self._ws: Optional[torch.Tensor] = None
         self.step_count = 0
+        self.last_lr: Optional[float] = None
         # fp32 average of the weights, moved by the update kernel itself (vae_adamw_ema); None when use_ema is off
         self.use_ema = bool(use_ema)
         self.ema_decay = float(ema_decay)
@@ -100,6 +101,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW needs the parameter arena on the GPU (no CPU fallback)")
         g = self.param_groups[0]
         self.step_count += 1
+        self.last_lr = g["lr"]  # of the update this call applies (WeightDynamicsTracker's update ratio)
         hp = (self.sqnorm, self.max_grad_norm, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count)
         if self._table is not None:  # part of the model is frozen: norm and update over the trainable ranges only
             ops.sqnorm_ranges(a.grad, self._table, self.sqnorm)
