@@ -315,6 +315,36 @@ int vae_changrad_partial(const void* a, int32_t a_bf16, int32_t lda, const void*
                          int32_t HW, int32_t C, int32_t nchunk, uint32_t* ws, void* stream);
 int vae_changrad_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* sums, float* absmax,
                        void* stream);
+/* activation penalties of the fused train step (vaehip/actreg.py), csrc/actreg.hip: a loss term on a module's NHWC output
+ * a = [B][HW] pixel rows of C contiguous channels, N = B * HW, w_c the 0 / 1 channel mask.  kind 0, ceiling at threshold t:
+ * P = weight / (N C) sum_c w_c sum relu(|a| - t)^2; kind 1, floor at t: P = weight / C sum_c w_c relu(t - m_c)^2 with
+ * m_c = (1 / N) sum |a|.  Both gradients are dP/da = k_c psi(a): psi(a) = a - clamp(a, -t, t) and k_c = 2 weight w_c
+ * grad_scale / (N C) for the ceiling, psi(a) = sign(a) (sign(0) = 0) and k_c = -2 weight w_c relu(t - m_c) grad_scale / (N C)
+ * for the floor.
+ * Statistics: a fp32 or bf16 (a_bf16) with pixel stride lda >= C in elements; nchunk as vae_moments_partial; B * HW < 2^31.
+ * vae_actreg_workspace: *nwords = 32-bit words of ws for this shape (exactly what the partial pass writes); needs no GPU.
+ * partial: ws [C][B * nchunk][3] = per (c, b, chunk) the fp32 sum of (|a| - t)^2 over the elements with !(|a| <= t) (the
+ * difference and the square rounded once each), the fp32 sum |a| and the exact number of such elements; plain stores.  A NaN
+ * counts as over t and makes its channel's sums NaN, an infinity makes them infinite; neither reaches another channel.
+ * final: float64 in a fixed order.  sums [3][C]: row 0 = sum relu(|a| - t)^2, row 1 = sum |a|, row 2 = elements over t;
+ * pen [C] = the channel's share of P (grad_scale not applied); coef [C] = k_c.  mask: fp32 [C] of w_c, or NULL for all ones.
+ * weight * w_c == 0 gives pen = 0 and coef = 0 exactly.  No atomics, no zero-fill: repeated launches are bitwise identical.
+ * vae_actreg_inject: out = g + coef[c] * psi(a), out of place, over rows = B * HW pixel rows (< 2^31).  a and g each fp32 or
+ * bf16 with their own pixel strides; out is contiguous (stride C) with the storage of g.  fp32 arithmetic, the product and the
+ * sum rounded once each, a bf16 result rounded once more; an element whose product is zero receives g unchanged (bit for bit):
+ * a zero coefficient leaves g as it is wherever a is finite (0 * inf and 0 * NaN are NaN: a non-finite a makes its own
+ * element of out NaN even under a zero coefficient).
+ * 16-byte accesses (8-byte for bf16) when C % 4 == 0 and every base and stride allows them, single elements otherwise.  A NaN
+ * or an infinity in a or g stays in its element.
+ * Bad shapes, strides below C, a kind other than 0 / 1, a threshold that is not finite and > 0, a weight that is not finite
+ * and >= 0, null or (workspace) unaligned pointers: VAE_EINVAL before anything is launched. */
+int vae_actreg_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords);
+int vae_actreg_partial(const void* a, int32_t a_bf16, int32_t lda, int32_t B, int32_t HW, int32_t C, int32_t nchunk,
+                       float threshold, uint32_t* ws, void* stream);
+int vae_actreg_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int32_t kind, double threshold,
+                     double weight, const float* mask, double grad_scale, double* sums, double* pen, float* coef, void* stream);
+int vae_actreg_inject(const void* a, int32_t a_bf16, int32_t lda, const void* g, int32_t g_bf16, int32_t ldg, const float* coef,
+                      int64_t rows, int32_t C, int32_t kind, float threshold, void* out, void* stream);
 /* channel covariance and mean of y = XF(x) over the N = B * HW rows of an NHWC activation in one read (monitor.py's
  * channel_covariance_matrix / channel_correlation_matrix / max_abs_correlation_per_channel / effective_rank), csrc/chancov.hip.
  * x, x_bf16, scale, shift, xf, ld, nchunk: exactly as vae_moments_partial.  The sums are taken of z = fp32(y - K) with

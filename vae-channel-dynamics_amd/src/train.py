@@ -50,6 +50,7 @@ from intervention.nudger import InterventionHandler
 from vaehip.trainer import HipTrainer
 from vaehip.dp import allreduce_mean_
 from vaehip.losses import KINDS as LOSS_KINDS, SSIM_WINDOW, ReconLoss
+from vaehip.actreg import from_mapping as penalty_from_mapping
 
 setup_logging()
 logger = logging.getLogger(__name__)
@@ -275,6 +276,44 @@ def recon_loss_settings(training_cfg: dict, resolution=None) -> ReconLoss:
     return ReconLoss(kind=kind, huber_delta=delta if kind == "huber" else 1.0, ssim_weight=weight)
 
 
+AP_CSV_FIELDS = ("step", "name", "kind", "penalty", "elements_over_threshold", "channels_under_floor")
+
+
+def activation_penalty_settings(config: dict):
+    """the YAML section `activation_penalty:` (not a section of the reference) -> the `activation_penalties` argument of
+    HipTrainer, a list of (module name, vaehip.actreg.ActivationPenalty); [] when the section is absent or not enabled.
+    `targets:` entries: name (as a tracking.target_layers name), kind (ceiling | floor), threshold, weight (default 1.0) and
+    channels (optional list).  A bad entry is refused with its position and name."""
+    sec = config.get("activation_penalty") or {}
+    if not isinstance(sec, dict):
+        raise ValueError(f"activation_penalty={sec!r}: expected a section with `enabled` and `targets`")
+    if not sec.get("enabled", False):
+        return []
+    targets = sec.get("targets")
+    if not isinstance(targets, (list, tuple)) or not targets:
+        raise ValueError(f"activation_penalty.targets={targets!r}: expected a non-empty list of targets")
+    out = []
+    for i, entry in enumerate(targets):
+        where = f"activation_penalty.targets[{i}]"
+        if not isinstance(entry, dict):
+            raise ValueError(f"{where}={entry!r}: expected a mapping with name, kind, threshold")
+        name = entry.get("name")
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"{where}: `name` is missing")
+        rest = {k: v for k, v in entry.items() if k != "name"}
+        for key in ("threshold", "weight"):  # YAML reads 1e-1 as a string
+            if isinstance(rest.get(key), str):
+                try:
+                    rest[key] = float(rest[key])
+                except ValueError:
+                    raise ValueError(f"{where} ({name}): {key}={rest[key]!r}: expected a number") from None
+        try:
+            out.append((name, penalty_from_mapping(rest)))
+        except ValueError as e:
+            raise ValueError(f"{where} ({name}): {e}") from None
+    return out
+
+
 def trainable_setting(training_cfg: dict):
     """training.trainable_modules (not a key of the reference) -> the `trainable` argument of HipTrainer: absent or 'all' trains
     everything, 'decoder' / 'encoder' are the shorthands of vaehip.trainable, a list holds module-name prefixes of the VAE"""
@@ -403,6 +442,8 @@ def main():
     # not keys of the reference: the pixel term (mse | l1 | huber) and an SSIM term of the training loss; validation and
     # evaluate.py keep the reference's MSE, so runs stay comparable
     recon_loss = recon_loss_settings(training_cfg, config.get("data", {}).get("resolution", 256))
+    # not a section of the reference: loss terms on module outputs (an outlier ceiling, a channel floor), vaehip/actreg.py
+    penalties = activation_penalty_settings(config)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -477,7 +518,9 @@ def main():
         max_grad_norm=max_grad_norm, kl_weight=kl_weight, lr_warmup_steps=int(training_cfg.get("lr_warmup_steps", 100)),
         max_train_steps=max_train_steps, scheduler_steps_per_update=world,  # accelerate steps the scheduler `world` times
         mixed_precision=mixed_precision, gradient_accumulation_steps=grad_accum, checkpoint_decoder=bool(grad_ckpt),
-        use_ema=use_ema, ema_decay=ema_decay, trainable=trainable, recon_loss=recon_loss)
+        use_ema=use_ema, ema_decay=ema_decay, trainable=trainable, recon_loss=recon_loss, activation_penalties=penalties)
+    if penalties:
+        logger.info("activation penalties: " + "; ".join(f"{n}: {p.kind} {p.threshold:g} x {p.weight:g}" for n, p in penalties))
     n_tr = sum(p.numel() for p in vae_wrapper.vae.parameters() if p.requires_grad)
     logger.info(f"trainable_modules={trainable!r}: {n_tr} of {sum(p.numel() for p in vae_wrapper.vae.parameters())} parameters train, "
                 f"in {len(trainer.trainable_ranges)} arena range(s)")
@@ -578,9 +621,23 @@ def main():
                 else:
                     logger.info(f"Step {global_step}: Intervention due, but no regions classified.")
             if global_step % log_interval == 0:
+                # device values of the last micro-batch of the main rank, read behind the sync
+                ap = trainer.activation_penalty_report() if is_main else None
                 step_loss = allreduce_mean_(sc[2:3].clone()).item()  # the only host sync of a logging step
                 if is_main:
                     loss_logs = {}
+                    if ap is not None:
+                        rows = ap.tolist()
+                        loss_logs["train/activation_penalty"] = math.fsum(r[0] for r in rows)
+                        new_file = not os.path.exists(os.path.join(output_dir, "activation_penalty_history.csv"))
+                        with open(os.path.join(output_dir, "activation_penalty_history.csv"), "a", newline="") as fh:
+                            wr = csv.writer(fh)
+                            if new_file:
+                                wr.writerow(AP_CSV_FIELDS)
+                            for (name, handle), (value, over, under) in zip(trainer.activation_penalties, rows):
+                                loss_logs[f"train/activation_penalty/{name}"] = value
+                                wr.writerow([global_step, name, handle.spec.kind, repr(value), int(over) if over == over else "",
+                                             int(under) if under == under else ""])
                     if res is not None and not recon_loss.is_default:  # this rank's terms of the last micro-batch (ssim: with an SSIM term only)
                         terms = res["loss_terms"].tolist()
                         loss_logs["train/pixel_loss"] = terms[0]

@@ -14,6 +14,9 @@ would have received, and one covariance pass (ops.chancov: the channel covarianc
 effective-rank metrics), each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
 add_grad_tracker serves the backward pass: per backward of a module, one ops.changrad pass over (the output the forward kept, the
 gradient the tape carries to it) gives the per-channel gradient metrics (CHANGRAD_METRICS); it launches nothing unless registered.
+add_activation_penalty acts at the same points: one ops.actreg_stats pass over the output in the forward of forward_backward gives
+the value of a loss term on it (vaehip/actreg.py) and a per-channel coefficient, and where the tape carries the gradient of
+that output past, ops.actreg_inject replaces it by gradient + the term's own gradient.
 """
 from __future__ import annotations
 
@@ -25,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .actreg import ActivationPenalty
 from .losses import as_spec
 from .ops import XF_AFFINE, XF_AFFINE_SILU, XF_NONE, Stats
 
@@ -50,6 +54,33 @@ class _TrackHandle:
             lst.remove(self._f)
 
 
+class _PenaltyHandle:
+    """one add_activation_penalty registration.  last: (sums float64 [3, C], penalty float64 scalar) on the device, of the last
+    forward_backward that ran the module: ops.actreg_stats' sums and the term's value (grad_scale not applied)"""
+
+    def __init__(self, store: dict, module: nn.Module, spec: ActivationPenalty, channels: int):
+        self._s, self.module, self.spec, self.channels = store, module, spec, channels
+        self.last = None
+        self.rows = 0  # pixel rows N = B H W of the output `last` describes
+        self._mask: Optional[torch.Tensor] = None
+
+    def mask(self, device) -> Optional[torch.Tensor]:
+        if self.spec.channels is None:
+            return None
+        if self._mask is None or self._mask.device != device:
+            m = torch.zeros(self.channels, dtype=torch.float32)
+            m[list(self.spec.channels)] = 1.0
+            self._mask = m.to(device)
+        return self._mask
+
+    def remove(self):
+        lst = self._s.get(id(self.module), [])
+        if self in lst:
+            lst.remove(self)
+        if not lst:
+            self._s.pop(id(self.module), None)
+
+
 class _MetricTracker:
     """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward; a registration that
     names one of CHANHIST_METRICS gets sink(moments or None, full map or None, chanhist=(hist, nzero, absmax)) instead, one
@@ -71,6 +102,10 @@ class Engine:
         self._mtrackers: Dict[int, Dict[str, List[_MetricTracker]]] = {}
         self._gtrackers: Dict[int, Dict[str, List[Callable]]] = {}  # add_grad_tracker: id(module) -> {"output_grad": sinks}
         self._rec = False  # the block that executes now records a backward (_enter): a tracked convolution keeps its output
+        self._penalties: Dict[int, List[_PenaltyHandle]] = {}  # add_activation_penalty: id(module) -> handles
+        # the forward_backward in progress when a penalty is registered, {"scale": grad_scale, "terms": [(handle, value)]}; None
+        # anywhere else (eval, stand-alone calls, no penalty): then no module is treated as penalised and nothing new is launched
+        self._pen: Optional[dict] = None
         self._gtarget: Optional[torch.Tensor] = None
         self.reducer = None  # optional DP bucket reducer with .ready(low_offset)
         self._low: Dict[int, int] = {}
@@ -229,16 +264,91 @@ class Engine:
         for s in list(sinks):
             s(*res)
 
+    @staticmethod
+    def _out_channels(module: nn.Module) -> int:
+        """channels of the output of a module that metric_trackable() accepts"""
+        from . import autoencoder as A
+        if isinstance(module, A.ResnetBlock2D):
+            module = module.conv2
+        elif isinstance(module, A.Attention):
+            return module.to_out[0].weight.shape[0]
+        elif isinstance(module, (A.UNetMidBlock2D, A.DownEncoderBlock2D, A.UpDecoderBlock2D)):
+            module = module.resnets[-1].conv2
+        elif isinstance(module, (A.Downsample2D, A.Upsample2D)):
+            module = module.conv
+        elif isinstance(module, (A.Encoder, A.Decoder)):
+            module = module.conv_out
+        return module.weight.shape[0]
+
+    def add_activation_penalty(self, module: nn.Module, spec: ActivationPenalty) -> _PenaltyHandle:
+        """a loss term on `module`'s output (vaehip.actreg.ActivationPenalty), for the modules add_grad_tracker accepts.  In the
+        forward of forward_backward one ops.actreg_stats pass over the output gives the term's value, which joins the step's
+        loss, and the coefficients of its gradient; in the backward, where the gradient d of that output is computed at all,
+        ops.actreg_inject replaces it by d + the term's gradient before anything else reads it (a gradient tracker on the same
+        module sees the total).  Where a frozen prefix leaves the gradient uncomputed the value is still reported and the
+        backward launches nothing.  A HipConv2d keeps its output as for a gradient tracker (a fused residual add is un-fused).
+        A checkpointed segment's replay recomputes the coefficients (same kernels, same bits) and adds nothing to the value.
+        forward_eval ignores penalties.  The handle has .remove() and .last = (sums, value) of the last step, on the device."""
+        from . import autoencoder as A
+        if not isinstance(spec, ActivationPenalty):
+            raise TypeError(f"activation penalty: expected a vaehip.actreg.ActivationPenalty, got {type(spec).__name__}")
+        if isinstance(module, A.HipGroupNorm):
+            raise ValueError("HipGroupNorm: the GroupNorm output is never materialised and neither is its gradient; a penalty "
+                             "on a norm is not served (penalise the convolution it feeds, or the block around it)")
+        if not self.metric_trackable(module):
+            raise ValueError(f"{type(module).__name__}: no 4-D capture point the engine can reduce")
+        C = self._out_channels(module)
+        spec.check_channels(C)
+        h = _PenaltyHandle(self._penalties, module, spec, C)
+        self._penalties.setdefault(id(module), []).append(h)
+        return h
+
+    def _penalised(self, m):
+        return self._penalties.get(id(m)) if self._pen is not None else None
+
+    def _pen_forward(self, pens, out: torch.Tensor, want: bool):
+        """the statistics pass of every penalty on a module whose output is `out`; want: the gradient of out is going to be
+        computed and a closure will receive it.  Returns [(spec, coef)] for that closure, None when there is none.  The value
+        is added to the pass's penalty by the forward itself, never by a checkpointed segment's replay, which runs only for
+        the coefficients."""
+        st = self._pen
+        if self._replay and not want:
+            return None
+        res = []
+        for h in pens:
+            sp = h.spec
+            sums, pen, coef = ops.actreg_stats(out, sp.kind, sp.threshold, sp.weight, h.mask(out.device), st["scale"])
+            if not self._replay:
+                value = pen.sum()
+                h.last, h.rows = (sums, value), out.shape[0] * out.shape[1] * out.shape[2]
+                st["terms"].append((h, value))
+            res.append((sp, coef))
+        return res if want else None
+
+    @staticmethod
+    def _inject(coefs, out: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+        """d + the gradient of every penalty on `out`: a new tensor (no bf16 image attached)"""
+        for sp, coef in coefs:
+            d = ops.actreg_inject(out, d, sp.kind, sp.threshold, coef)
+        return d
+
     def _grad_point(self, m, out: torch.Tensor, tape):
         """behind the backward closure(s) `m`'s forward has just appended (the tape is LIFO: this one runs first and receives
-        exactly dL/d out): only with a gradient tracker on m, a recording tape, and that gradient going to be computed"""
+        exactly dL/d out): only with a gradient tracker or a penalty on m, a recording tape, and that gradient going to be
+        computed.  A penalty's gradient is added first, so a tracker sees the total."""
         sinks = self._gtracked(m)
-        if not sinks or tape is None or not self._live:
+        pens = self._penalised(m)
+        want = tape is not None and self._live
+        coefs = self._pen_forward(pens, out, want) if pens else None
+        if not want or not (sinks or coefs):
             return
 
         def emit(d):
             if d is not None:
-                self._emit_grad(sinks, out, d)
+                if coefs:
+                    d = self._inject(coefs, out, d)
+                if sinks:
+                    self._emit_grad(sinks, out, d)
             return d
         tape.append(emit)
 
@@ -382,7 +492,8 @@ class Engine:
         sinks = self._tracked(m, "output")
         mts = self._mtracked(m, "output")
         gts = self._gtracked(m)
-        fuse_res = res is not None and not m._forward_hooks and not sinks and not mts and not gts
+        pens = self._penalised(m)
+        fuse_res = res is not None and not m._forward_hooks and not sinks and not mts and not gts and not pens
         tb = None
         if sinks:
             ho, wo = ops.out_hw(kind, x.shape[1], x.shape[2])
@@ -409,11 +520,12 @@ class Engine:
             self._emit(mts, y)
         if m._forward_hooks:
             self._post(m, make_in, y, tracked_already=True)
-        if gts and self._rec:  # kept with the input, which the backward closure holds: _conv_bwd finds it there
+        coefs = self._pen_forward(pens, y, self._rec) if pens else None
+        if (gts or coefs) and self._rec:  # kept with the input, which the backward closure holds: _conv_bwd finds it there
             kept = getattr(x, "_gy", None)
             if kept is None:
                 kept = x._gy = {}
-            kept[id(m)] = y
+            kept[id(m)] = (y, coefs)
         if res is not None and not fuse_res:
             y = ops.add(y, res)
         return y
@@ -431,10 +543,12 @@ class Engine:
         as if dx were wanted), so a trainable parameter's gradient does not depend on what else is frozen."""
         kind = getattr(m, "kind", "c1")
         gts = self._gtracked(m)
-        if gts and dy is not None:
+        if (gts or self._pen is not None) and dy is not None:
             kept = getattr(x, "_gy", None)
-            y = kept.pop(id(m), None) if kept else None
-            if y is not None:
+            y, coefs = (kept.pop(id(m), None) if kept else None) or (None, None)
+            if coefs:  # a penalty on this output: its gradient joins dy before anything reads it (a new tensor, no bf16 image)
+                dy = self._inject(coefs, y, dy)
+            if gts and y is not None:
                 self._emit_grad(gts, y, dy)
         need_dw = self._trains(m)
         want_dx = need_dx and want_dx
@@ -723,10 +837,21 @@ class Engine:
         recon_loss: a vaehip.losses.ReconLoss; None or the default spec is the reference's MSE through the calls the step always
         made, anything else goes through ops.recon_loss and scalars[0] is pixel + ssim_weight * (1 - ssim).
         Returns dict(scalars[3]=rec,kl,total on device, loss_terms[2]=pixel term, SSIM index (None on the default path),
-        drecon = the seed grad_scale * d rec / d reconstruction, reconstruction, moments, latents) as NHWC buffers."""
+        drecon = the seed grad_scale * d rec / d reconstruction, reconstruction, moments, latents) as NHWC buffers.
+        With activation penalties registered (add_activation_penalty) the sum of their values is added to scalars[2] on the
+        device and returned as activation_penalty (a float64 device scalar, grad_scale not applied; None with none registered),
+        activation_penalty_terms lists (handle, value) in forward order, and their gradients join the backward."""
         self._require_gpu()
         spec = as_spec(recon_loss)
         pv = pixel_values.contiguous()
+        if self._penalties:
+            self._pen = {"scale": float(grad_scale), "terms": []}
+        try:
+            return self._forward_backward(pv, eps, kl_weight, sample_posterior, generator, grad_scale, spec)
+        finally:
+            self._pen = None
+
+    def _forward_backward(self, pv, eps, kl_weight, sample_posterior, generator, grad_scale, spec):
         with self._mode():
             x4 = ops.nchw_to_nhwc(pv, 4)
             tgt = ops.nchw_to_nhwc(pv, 3)
@@ -748,6 +873,12 @@ class Engine:
                 drec = ops.mse_bwd(recon, tgt, grad_scale)
             else:
                 scalars, terms, drec = ops.recon_loss(recon, tgt, klp, kl_weight, spec, grad_scale)
+            penalty = pterms = None
+            if self._pen is not None:
+                pterms = list(self._pen["terms"])
+                penalty = (torch.stack([v for _, v in pterms]).sum() if pterms
+                           else torch.zeros((), device=scalars.device, dtype=torch.float64))
+                scalars[2:3].add_(penalty.to(scalars.dtype))
             self.arena.attach_grads()
             dz = self.run_tape(td, drec, self.arena.grad)
             if enc_live:
@@ -756,7 +887,7 @@ class Engine:
         if self.reducer is not None:
             self.reducer.ready(0)
         return {"scalars": scalars, "loss_terms": terms, "drecon": drec, "reconstruction": recon, "moments": mom, "latents": z,
-                "kl_partial": klp}
+                "kl_partial": klp, "activation_penalty": penalty, "activation_penalty_terms": pterms}
 
     @torch.no_grad()
     def forward_eval(self, pixel_values: torch.Tensor, eps: Optional[torch.Tensor] = None, sample_posterior: bool = False,
@@ -789,12 +920,20 @@ class Engine:
         return ops.nchw_to_nhwc(eps.to(mom.device).contiguous())
 
     # ------------------------------------------------------------------ autograd-compatible path
+    def _no_penalty_autograd(self, what: str):
+        if self._penalties and torch.is_grad_enabled():
+            raise NotImplementedError(f"{what}: an activation penalty is registered (Engine.add_activation_penalty), and its term "
+                                      "exists only in the loss that forward_backward composes; the autograd pair cannot carry "
+                                      "it.  Train through HipTrainer / forward_backward, or remove the penalty's handle")
+
     def encode_autograd(self, x: torch.Tensor) -> torch.Tensor:
         self._require_gpu()
+        self._no_penalty_autograd("encode_autograd")
         return _EncodeFn.apply(self, torch.is_grad_enabled(), x, *self._params_of(self.vae.encoder, self.vae.quant_conv))
 
     def decode_autograd(self, z: torch.Tensor) -> torch.Tensor:
         self._require_gpu()
+        self._no_penalty_autograd("decode_autograd")
         return _DecodeFn.apply(self, torch.is_grad_enabled(), z, *self._params_of(self.vae.post_quant_conv, self.vae.decoder))
 
     @staticmethod

@@ -1010,6 +1010,96 @@ def changrad(a: torch.Tensor, g: torch.Tensor):
     return sums, absmax
 
 
+ACTREG_KINDS = ("ceiling", "floor")  # the C ABI's kind 0 / 1
+
+
+def actreg_chunks(B: int, HW: int, Cc: int) -> int:
+    """pixel chunks per image of actreg_stats(): the rule of changrad_chunks (one operand instead of two changes nothing in it):
+    B * nchunk * (tiles of 256 channels) workgroups near _GN_TARGET, a chunk no shorter than 16 pixels per pixel row of a
+    workgroup, and every chunk non-empty"""
+    return changrad_chunks(B, HW, Cc)
+
+
+def _actreg_kind(who: str, kind: str, threshold: float) -> int:
+    if kind not in ACTREG_KINDS:
+        raise ValueError(f"{who}: kind {kind!r} is not one of {ACTREG_KINDS}")
+    t = float(threshold)
+    if not (t > 0.0 and t < float("inf")):
+        raise ValueError(f"{who}: threshold {threshold!r} is not a finite number > 0")
+    return ACTREG_KINDS.index(kind)
+
+
+def _actreg_act(who: str, name: str, t: torch.Tensor):
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):
+        what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name}: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {what}")
+
+
+def actreg_stats(a: torch.Tensor, kind: str, threshold: float, weight: float, mask: Optional[torch.Tensor] = None,
+                 grad_scale: float = 1.0):
+    """statistics of an activation penalty (vaehip.actreg.ActivationPenalty) on a module output `a` in one read of it:
+    (sums float64 [3, C], pen float64 [C], coef fp32 [C]) on the device.  sums[0] = sum relu(|a| - threshold)^2, sums[1] =
+    sum |a|, sums[2] = the number of elements over the threshold (a NaN counts), each per channel over the N = B * H * W pixel
+    rows.  pen[c] is the channel's share of the penalty P, pen.sum() is P:
+        ceiling: P = weight / (N C) sum_c w_c sum relu(|a| - threshold)^2
+        floor:   P = weight / C sum_c w_c relu(threshold - m_c)^2, m_c = sums[1, c] / N
+    coef[c] = k_c with dP/da * grad_scale = k_c psi(a), what actreg_inject adds to a gradient.  mask: fp32 [C] of w_c (0 or 1),
+    None for all ones; weight * w_c == 0 gives pen and coef exactly 0.  a: 4-D NHWC fp32 or bf16, channels contiguous, pixel
+    stride >= C (a channel-prefix view is read in place).  The threshold is compared in fp32; differences and squares are rounded
+    once and summed in fp32 inside a workgroup (csrc/actreg.hip), everything after is float64 in a fixed order: two calls agree
+    bitwise.  Nothing synchronises the host."""
+    k = _actreg_kind("actreg_stats", kind, threshold)
+    _actreg_act("actreg_stats", "a", a)
+    w = float(weight)
+    if not (w >= 0.0 and w < float("inf")):
+        raise ValueError(f"actreg_stats: weight {weight!r} is not a finite number >= 0")
+    gs = float(grad_scale)
+    if not abs(gs) < float("inf"):
+        raise ValueError(f"actreg_stats: grad_scale {grad_scale!r} is not finite")
+    lda = _nhwc_ld("actreg_stats", a)
+    B, H, W, Cc = a.shape
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or mask.device != a.device
+                             or tuple(mask.shape) != (Cc,) or not mask.is_contiguous()):
+        what = f"{tuple(mask.shape)} {mask.dtype} on {mask.device}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise ValueError(f"actreg_stats: mask: expected a contiguous fp32 [{Cc}] tensor on {a.device}, got {what}")
+    HW = H * W
+    nch = actreg_chunks(B, HW, Cc)
+    dev = a.device
+    n = C.c_int64(0)
+    lib.call("vae_actreg_workspace", B, HW, Cc, nch, C.byref(n))
+    ws = torch.empty((n.value,), device=dev, dtype=torch.int32)
+    sums = torch.empty((3, Cc), device=dev, dtype=torch.float64)
+    pen = torch.empty((Cc,), device=dev, dtype=torch.float64)
+    coef = torch.empty((Cc,), device=dev, dtype=torch.float32)
+    lib.call("vae_actreg_partial", _p(a), _b16(a), lda, B, HW, Cc, nch, float(threshold), _p(ws), _stream())
+    lib.call("vae_actreg_final", _p(ws), B, HW, Cc, nch, k, float(threshold), w, _p(mask), gs, _p(sums), _p(pen), _p(coef), _stream())
+    return sums, pen, coef
+
+
+def actreg_inject(a: torch.Tensor, g: torch.Tensor, kind: str, threshold: float, coef: torch.Tensor) -> torch.Tensor:
+    """g + coef[c] * psi(a) as a new contiguous tensor with the dtype of g: the gradient of an activation penalty added to the
+    gradient g of a module output a.  psi(a) = a - clamp(a, -threshold, threshold) for the ceiling, sign(a) for the floor
+    (sign(0) = 0); coef = actreg_stats(...)[2].  a and g: 4-D NHWC of one shape, each fp32 or bf16, each with its own pixel
+    stride.  fp32 arithmetic, the product and the sum rounded once each (a bf16 result once more); where the product is zero the
+    element of g is passed on bit for bit (a zero coefficient leaves g as it is wherever a is finite; a non-finite a makes its own
+    element NaN).  Nothing synchronises the host."""
+    k = _actreg_kind("actreg_inject", kind, threshold)
+    _actreg_act("actreg_inject", "a", a)
+    _actreg_act("actreg_inject", "g", g)
+    if tuple(a.shape) != tuple(g.shape) or a.device != g.device:
+        raise ValueError(f"actreg_inject: output {tuple(a.shape)} on {a.device} and gradient {tuple(g.shape)} on {g.device} differ")
+    lda, ldg = _nhwc_ld("actreg_inject", a), _nhwc_ld("actreg_inject", g)
+    B, H, W, Cc = a.shape
+    if (not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or coef.device != a.device or tuple(coef.shape) != (Cc,)
+            or not coef.is_contiguous()):
+        what = f"{tuple(coef.shape)} {coef.dtype} on {coef.device}" if isinstance(coef, torch.Tensor) else type(coef).__name__
+        raise ValueError(f"actreg_inject: coef: expected a contiguous fp32 [{Cc}] tensor on {a.device}, got {what}")
+    out = torch.empty((B, H, W, Cc), device=a.device, dtype=g.dtype)
+    lib.call("vae_actreg_inject", _p(a), _b16(a), lda, _p(g), _b16(g), ldg, _p(coef), B * H * W, Cc, k, float(threshold), _p(out),
+             _stream())
+    return out
+
+
 CHANCOV_WS_BYTES = 64 << 20  # ceiling of chancov()'s workspace
 
 

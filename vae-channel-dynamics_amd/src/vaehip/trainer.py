@@ -37,9 +37,12 @@ class HipTrainer:
                  bucket_mb: float = 64.0, generator: Optional[torch.Generator] = None, mixed_precision: str = "no",
                  gradient_accumulation_steps: int = 1, checkpoint_decoder: bool = False, time_comm: bool = False,
                  one_rank_exchange: bool = False, use_ema: bool = False, ema_decay: float = 0.9999, trainable=None,
-                 recon_loss=None):
+                 recon_loss=None, activation_penalties=None):
         """recon_loss: a vaehip.losses.ReconLoss (None: the reference's MSE), the reconstruction term of every train_step;
         eval_step keeps the reference's MSE.
+        activation_penalties: a list of (module name, vaehip.actreg.ActivationPenalty): loss terms on module outputs, registered
+        on the engine (Engine.add_activation_penalty) under names that resolve as tracking.target_layers names do (from the
+        wrapper, `vae.decoder...`; the wrapper's `vae.` may be left out).  eval_step ignores them.
         trainable: None (requires_grad as the user left it, read now), 'all', 'decoder', 'encoder' or a list of module-name
         prefixes (vaehip.trainable); change it later with set_trainable()."""
         self.wrapper = wrapper
@@ -78,6 +81,50 @@ class HipTrainer:
             broadcast_params(self.vae.arena.flat, 0, one_rank_exchange=self.one_rank_exchange)
         self.global_step = 0
         self.last = None
+        self.activation_penalties = []  # (name, handle) in the order given
+        for i, entry in enumerate(activation_penalties or []):
+            try:
+                name, spec = entry
+                handle = self.vae.engine.add_activation_penalty(self._resolve_module(name), spec)
+            except (TypeError, ValueError, AttributeError) as e:
+                for _, h in self.activation_penalties:  # a refused list leaves nothing registered
+                    h.remove()
+                which = entry[0] if isinstance(entry, (tuple, list)) and entry else entry
+                raise ValueError(f"activation_penalties[{i}] ({which!r}): {e}") from None
+            self.activation_penalties.append((name, handle))
+
+    def _resolve_module(self, dotted: str):
+        """a module by its name from the wrapper (`vae.decoder.mid_block`) or from the VAE (`decoder.mid_block`), through the
+        resolver of tracking.target_layers names (one rule for both)"""
+        from tracking.monitor import _resolve
+        if not isinstance(dotted, str) or not dotted:
+            raise ValueError(f"module name {dotted!r}: expected a dotted name")
+        root = self.wrapper if hasattr(self.wrapper, dotted.split(".")[0]) else self.vae
+        cur = _resolve(root, dotted)
+        if not isinstance(cur, torch.nn.Module):
+            raise ValueError(f"'{dotted}' is not a module")
+        return cur
+
+    def activation_penalty_report(self) -> Optional[torch.Tensor]:
+        """float64 [targets, 3] on the device, no host sync: per registered penalty, in order, its value in the last
+        train_step, the elements over its threshold and the channels whose mean |A| is under it (both over the channels the
+        penalty covers); NaN for a target whose module has not run.  None when no penalty is registered."""
+        if not self.activation_penalties:
+            return None
+        dev = self.vae.arena.flat.device
+        rows = []
+        for _, h in self.activation_penalties:
+            if h.last is None:
+                rows.append(torch.full((3,), float("nan"), device=dev, dtype=torch.float64))
+                continue
+            sums, value = h.last
+            m = h.mask(sums.device)
+            over = sums[2] if m is None else sums[2] * m
+            under = sums[1] < h.spec.threshold * h.rows
+            if m is not None:
+                under = under & (m > 0)
+            rows.append(torch.stack([value, over.sum(), under.sum().to(torch.float64)]))
+        return torch.stack(rows)
 
     @property
     def sync_gradients(self) -> bool:
