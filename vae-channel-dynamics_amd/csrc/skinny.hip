@@ -11,11 +11,21 @@
 // The WIDE side may be stored as bf16 (bf16 mode keeps the 128-channel activations / gradients as bf16): out_bf16 for
 // conv_smallk's output, y_bf16 / x_bf16 for wgrad_smallk's V, a_bf16 for conv_smalln's input; the narrow side, the weights
 // and the arithmetic are fp32.
+// wgrad_smallk's one-lane-per-channel loop is bound by issue, not by bytes (36 FMAs and nine LDS broadcasts per pixel: 0.52 and
+// 0.65 ms for the two full-resolution launches, whose 537 MB stream in 0.1 ms): a 3x3 layer with a wide side of >= 64 channels
+// runs on the matrix pipe instead, exact fp32 products (v_mfma_f32_16x16x4_f32; the padded 48 x 128 product is 0.08 ms of matrix
+// time per launch, inside the memory time, so no operand split), behind a grid-uniform branch of the same kernel
+// (wgrad_smallk_mfma below; -DVAE_THIN_F32_MFMA=0 builds the VALU bodies alone).  conv_smallk and conv_smalln keep their VALU bodies.
 // The tile shapes, the tile range of a split, the per-element transform, the slab protocol of the weight gradient and the host
 // predicates are in thin_common.h, shared with the matrix-pipe kernels of the same launches (conv_thin_bf16.hip,
 // wgrad_thin_bf16.hip).
 #include "thin_common.h"
 #include "launchers.h"
+
+// 0: the VALU bodies alone (the A/B arm of tools/thin_f32_ab.py: make thin_f32_valu)
+#ifndef VAE_THIN_F32_MFMA
+#define VAE_THIN_F32_MFMA 1
+#endif
 
 namespace {
 
@@ -98,12 +108,203 @@ __global__ __launch_bounds__(NT) void conv_smallk_kernel(vae_igemm_args p) {
   }
 }
 
+#if VAE_THIN_F32_MFMA
+// The 3x3 weight gradient with a wide side of >= 64 channels on the matrix pipe (v_mfma_f32_16x16x4_f32: exact fp32 products):
+//     out[(tap, s)][n] = sum_q T[q][(tap, s)] * V[q][n]        q = pixel (the contraction), n = wide channel
+// T = the im2col of the narrow tensor, gathered per 128-pixel tile into LDS planes [(tap, s)][pixel] (36 rows; SMALL_X: row 36
+// = ones, so row 36 of the product is the bias gradient; padded to 48 = three 16-row blocks), A operand = one ds_read_b128 per
+// row block and 16 pixels.  V goes from global memory straight into the B operand: a lane loads the 2 channels cq, cq + 1 of
+// pixel 16 h + 4 g + j (g = lane / 16; h, j = the k-step of a 32-pixel chunk) as one 8-byte load (128 contiguous bytes per
+// pixel and wave) and gives channel cq + e to the MFMAs of column block e -- the columns of a block are channels 2 apart, which
+// only relabels the output.  Wave w = the 32 channels 32 w .. 32 w + 31 over all the pixels (24 accumulator registers, no
+// reduction across waves: every sum runs in pixel order); V is prefetched one chunk ahead across tile boundaries, T one tile
+// ahead in registers; 4 workgroups per CU (128 registers), so the 1024 workgroups of a full-resolution launch are one round.
+constexpr int WM_LDT = TP + 4;                                  // floats per row of T: b128 reads of 16 rows conflict-free
+constexpr int WM_ROWS = 48;
+constexpr int WM_ITEMS = (TP * TAPS_MAX + NT - 1) / NT;         // (pixel, tap) gathers per thread and tile: 5
+constexpr int WG_SI = WM_ROWS * WM_LDT / 4;                     // (the sums of dY, 4 x 256 floats, reuse it at the end)
+static_assert(WG_SI >= TP * TAPS_MAX + 32 && WG_SI >= NT, "LDS of wgrad_smallk_kernel");
+
+// 3x3, a wide side of >= 64 channels read as pairs: even, its rows and its base 8-byte (bf16: 4-byte) aligned; with a fused
+// GroupNorm, tiles that lie inside one image (one scale / shift pair per lane and tile).  1x1 layers, the 4 -> 4 latent convs
+// and every other operand keep the VALU body.
+template <bool SMALL_X, int XF>
+__device__ __forceinline__ bool wgrad_mfma_serves(const vae_wgrad_args& p, const vae_conv_geom& gs) {
+  const int wide = SMALL_X ? p.M : p.N, ldv = SMALL_X ? p.ldy : p.g.Cs;
+  const bool vbf = (SMALL_X ? p.y_bf16 : p.x_bf16) != 0;
+  const uintptr_t v = reinterpret_cast<uintptr_t>(SMALL_X ? p.dY : p.X);
+  return gs.taps == TAPS_MAX && wide >= 64 && wide % 2 == 0 && ldv % 2 == 0 && (v & (vbf ? 3u : 7u)) == 0 &&
+         (XF == VAE_XF_NONE || (gs.Ho * gs.Wo) % TP == 0);
+}
+
+template <bool SMALL_X, int XF>
+__device__ __forceinline__ void wgrad_smallk_mfma(const vae_wgrad_args& p, const vae_conv_geom& gs, int ntiles, float* __restrict__ sT) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lc = lane & 15, lg = lane >> 4;
+  const int split = blockIdx.x;
+  const int wide = SMALL_X ? p.M : p.N, narrow = SMALL_X ? p.N : p.M;
+  const int cq = blockIdx.y * 128 + wave * 32 + lc * 2;  // this lane's two wide channels
+  const float* __restrict__ V = SMALL_X ? p.dY : p.X;
+  const float* __restrict__ S = SMALL_X ? p.X : p.dY;
+  const int ldv = SMALL_X ? p.ldy : p.g.Cs, lds_ = SMALL_X ? p.g.Cs : p.ldy;
+  const int npixv = gs.B * gs.Ho * gs.Wo, hwv = gs.Ho * gs.Wo;
+  const bool vbf = (SMALL_X ? p.y_bf16 : p.x_bf16) != 0;
+  const unsigned esV = vbf ? 2u : 4u;
+  const size_t vbytes = (size_t)npixv * ldv * esV;
+  const auto rsV = VAE_BUF_RSRC(V, vbytes < BUF_MAX ? vbytes : BUF_MAX);
+  const auto rsS = thin::narrow_rsrc(S, gs, lds_);
+
+  // rows 36 .. 47 of T never change: zeros, and (SMALL_X) row 36 = ones
+  for (int i = tid; i < (WM_ROWS - 36) * WM_LDT; i += NT) sT[36 * WM_LDT + i] = (SMALL_X && i < WM_LDT) ? 1.f : 0.f;
+
+  f32x4 acc[3][2];  // [row block][column block]: rows (tap = 4 mb + lg, s = r), column = channel cq + e
+#pragma unroll
+  for (int mb = 0; mb < 3; ++mb)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) acc[mb][e] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 ssum = {0.f, 0.f, 0.f, 0.f};  // !SMALL_X: this thread's share of sum_q dY[q][s]
+  float sc[2] = {0.f, 0.f}, sh[2] = {0.f, 0.f};
+  int xb = -1;
+
+  // this lane's eight pixels mb_ + 16 h + j of a chunk, as stored (an fp32 pair, or 2 bf16 in .x); a pixel past the grid or a
+  // channel pair past the wide side is not requested (zeros)
+  auto load_v = [&](uint2 (&rv)[8], int mb_) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int m = mb_ + 16 * (k >> 2) + (k & 3);
+      const int eoff = neg_unless(m < npixv && cq < wide, m * ldv + cq);
+      // one instruction for both storages (a bf16 pair brings the next pair along, unused), converted where it is consumed
+      rv[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rsV, eoff >= 0 ? (unsigned)eoff * esV : BUF_OOB, 0, 0));
+    }
+  };
+  // T: a thread gathers pixel `trow` of the tile at the taps 2 i + thalf (wave-uniform; consecutive lanes write consecutive LDS words)
+  const int trow = tid & (TP - 1), thalf = __builtin_amdgcn_readfirstlane(tid >> 7);
+  f32x4 rt[WM_ITEMS];
+  auto load_t = [&](int tile, bool valid) {
+    int m = tile * TP + trow;
+    asm volatile("" : "+v"(m));  // (the same for the gathers)
+#pragma unroll
+    for (int i = 0; i < WM_ITEMS; ++i) {
+      const int tap = 2 * i + thalf;
+      rt[i] = thin::gather4(gs, rsS, lds_, narrow, hwv, m, tap, valid && tap < TAPS_MAX && m < npixv);
+    }
+  };
+  auto store_t = [&]() {
+#pragma unroll
+    for (int i = 0; i < WM_ITEMS; ++i) {
+      const int tap = 2 * i + thalf;
+      if (tap < TAPS_MAX) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sT[(tap * 4 + s) * WM_LDT + trow] = rt[i][s];  // (s >= narrow: zeros)
+        if (!SMALL_X && tap == TAPS_MAX / 2) ssum += rt[i];  // centre tap: dY at this pixel itself
+      }
+    }
+  };
+  // the 32 pixels of chunk c (pixels 32 c + 16 h + 4 g + j of the tile)
+  auto chunk = [&](const uint2 (&rv)[8], int c) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 fa[3];
+#pragma unroll
+      for (int mb = 0; mb < 3; ++mb) fa[mb] = *reinterpret_cast<const f32x4*>(&sT[(mb * 16 + lc) * WM_LDT + c * 32 + h * 16 + 4 * lg]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint2 r = rv[h * 4 + j];
+        float v[2];
+        v[0] = __builtin_bit_cast(float, vbf ? r.x << 16 : r.x);
+        v[1] = __builtin_bit_cast(float, vbf ? r.x & 0xffff0000u : r.y);
+        if (XF != VAE_XF_NONE) {  // (whole tiles: no pixel of the wide tensor is padding)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) v[e] = thin::xform1<XF>(v[e], sc[e], sh[e], cq + e < wide);
+        }
+#pragma unroll
+        for (int mb = 0; mb < 3; ++mb)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) acc[mb][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[mb][j], v[e], acc[mb][e], 0, 0, 0);
+      }
+    }
+  };
+
+  const thin::TileRange tr = thin::tile_range(split, thin::tiles_per_part(ntiles, p.nsplit), ntiles);
+  const int pofs = 4 * lg;  // this lane's first pixel of a tile's chunk 0
+  uint2 rva[8], rvb[8];
+  if (tr.beg < tr.end) {
+    load_t(tr.beg, true);
+    load_v(rva, tr.beg * TP + pofs);
+  }
+  for (int tile = tr.beg; tile < tr.end; ++tile) {
+    int mb0 = tile * TP + pofs;
+    asm volatile("" : "+v"(mb0));  // (else hipcc keeps one induction register per load of the tile: 32 of them)
+    const bool more = tile + 1 < tr.end;
+    __syncthreads();  // the previous tile's reads of sT are done (first time round: the constant rows are in place)
+    store_t();
+    __syncthreads();
+    load_t(tile + 1, more);  // in flight under the MFMAs below
+    if (XF != VAE_XF_NONE) {
+      const int b = (tile * TP) / hwv;  // uniform: a tile lies inside one image (wgrad_mfma_serves)
+      if (b != xb) {
+        xb = b;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          sc[e] = (cq + e < wide) ? p.scale[(int64_t)b * p.g.Cs + cq + e] : 0.f;
+          sh[e] = (cq + e < wide) ? p.shift[(int64_t)b * p.g.Cs + cq + e] : 0.f;
+        }
+      }
+    }
+    load_v(rvb, mb0 + 32);
+    chunk(rva, 0);
+    load_v(rva, mb0 + 64);
+    chunk(rvb, 1);
+    load_v(rvb, mb0 + 96);
+    chunk(rva, 2);
+    load_v(rva, more ? mb0 + TP : npixv);
+    chunk(rvb, 3);
+  }
+
+  // slab of this split: lane (lc, lg) holds rows (tap = 4 mb + lg, s = r) of channels cq, cq + 1
+  const thin::Slab sl = thin::slab_of(p, split, TAPS_MAX);
+#pragma unroll
+  for (int mb = 0; mb < 3; ++mb)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = mb * 4 + lg, ch = cq + e;
+        if (ch < wide) {
+          if (t < TAPS_MAX && r < narrow) thin::slab_store<SMALL_X>(sl, ch, t, r, acc[mb][e][r]);
+          if (SMALL_X && mb == 2 && r == 0 && lg == 1 && p.bias_partial) thin::bias_partial_row(p, split)[ch] = acc[mb][e][r];  // row 36
+        }
+      }
+  if (!SMALL_X && p.bias_partial && blockIdx.y == 0) {  // sums of dY: 256 threads' shares, fixed order
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 4; ++s) sT[s * NT + tid] = ssum[s];
+    __syncthreads();
+    if (tid < p.M) {
+      float t = 0.f;
+      for (int i = 0; i < NT; ++i) t += sT[tid * NT + i];
+      thin::bias_partial_row(p, split)[tid] = t;
+    }
+  }
+}
+#define WG_BOUNDS __launch_bounds__(NT, 4)  // 128 registers: the 1024 workgroups of a full-resolution launch in one round
+#else
+constexpr int WG_SI = TP * TAPS_MAX + 32;
+#define WG_BOUNDS __launch_bounds__(NT)
+#endif
+
 // SMALL_X: the narrow side is X (N <= 4): V = dY over output pixels, S = X gathered with g, out[m = lane][tap][s]
 // else   : the narrow side is dY (M <= 4): V = XF(X) over INPUT pixels, S = dY gathered with the transposed geometry
 //          (the output pixel whose tap lands on this input pixel), out[s][tap][n = lane]
 template <bool SMALL_X, int XF>
-__global__ __launch_bounds__(NT) void wgrad_smallk_kernel(vae_wgrad_args p, vae_conv_geom gs, int ntiles) {
-  __shared__ f32x4 sI[TP * TAPS_MAX + 32];  // + 128 floats for the bias sums of the final reduction
+__global__ WG_BOUNDS void wgrad_smallk_kernel(vae_wgrad_args p, vae_conv_geom gs, int ntiles) {
+  __shared__ f32x4 sI[WG_SI];  // VALU body: [128 px][9 taps] + 128 floats for the bias sums of the final reduction
+#if VAE_THIN_F32_MFMA
+  if (wgrad_mfma_serves<SMALL_X, XF>(p, gs)) {  // uniform over the grid
+    wgrad_smallk_mfma<SMALL_X, XF>(p, gs, ntiles, reinterpret_cast<float*>(sI));
+    return;
+  }
+#endif
   const int tid = threadIdx.x, lane = tid & 127, half = tid >> 7;
   const int split = blockIdx.x;
   const int ch = blockIdx.y * 128 + lane;            // channel of the wide side
