@@ -299,6 +299,20 @@ int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* scale, cons
                          int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float tau, uint32_t* ws, void* stream);
 int vae_chanhist_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* hist, int64_t* nzero,
                        float* absmax, void* stream);
+/* per-(image, channel) sums of y = XF(x) in one read (monitor.py's group_variance_share_per_channel /
+ * normalized_rms_per_channel / group_dominance_per_group / active_sample_fraction_per_channel / sample_variation_per_channel),
+ * csrc/changroup.hip.  x, x_bf16, scale, shift, xf, ld, nchunk: exactly as vae_moments_partial.  B * HW must stay below 2^31.
+ * vae_changroup_workspace: *ndoubles = 64-bit words of ws for this shape (exactly what the partial pass writes); needs no GPU.
+ * partial: ws [B * nchunk][C][3] = per (b, chunk, c) the float64 sums of y, y^2 and |y| over the chunk's pixels: y is evaluated
+ * in fp32 and widened, its square is exact in float64, every addition is float64; plain stores.
+ * final: sums [B][C][3] = per (b, c) the chunks' partials added in chunk order.  Nothing reduces over the batch; a NaN or an
+ * infinity reaches the sums of its own (b, c) only.  No atomics, no zero-fill: repeated launches are bitwise identical.
+ * Bad shapes, a stride below C, an unknown xf, an xf without scale / shift, null or (workspace) unaligned pointers: VAE_EINVAL
+ * before anything is launched. */
+int vae_changroup_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* ndoubles);
+int vae_changroup_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
+                          int32_t HW, int32_t C, int32_t ld, int32_t nchunk, double* ws, void* stream);
+int vae_changroup_final(const double* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* sums, void* stream);
 /* per-channel gradient metrics of one backward pass in one read of the pair (a, g): a module's NHWC output a and the gradient g
  * of the loss with respect to it (monitor.py's mean_abs_gradient_per_channel / abs_max_gradient_per_channel /
  * gain_gradient_per_channel / taylor_saliency_per_channel), csrc/changrad.hip.  a and g: [B][HW] pixel rows of C contiguous

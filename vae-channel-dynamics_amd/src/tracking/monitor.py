@@ -55,6 +55,20 @@ engine module gets Engine.add_grad_tracker, whatever `device_metrics` says (no t
 ONE ops.changrad pass over the pair per backward.  step() takes the unweighted mean of the three sums over the buffered passes
 and the maximum of the maxima (a NaN stays); across ranks the sums are averaged and the maxima maxed on their bit patterns, with
 one host transfer per layer.
+
+Five metrics look at a channel the way GroupNorm does, per SAMPLE and per GROUP (CHANGROUP_METRICS, any layer, capture points
+`input` / `output`).  With n = H * W, cg = C / G, g(c) = c // cg, mu_bg the mean of group g in sample b, v_bc = sum_p (y - mu_bg)^2
+and V_bg = sum_{c in g} v_bc: `group_variance_share_per_channel` (mean over samples of v_bc / V_bg, 0 where V_bg is 0: 1 / cg
+means equal partners, near 1 the channel owns its group, near 0 it is squashed by a neighbour), `normalized_rms_per_channel` (mean of
+sqrt((v_bc / n) / (V_bg / (n cg) + eps)): the channel's RMS as the norm passes it on, before gamma), `group_dominance_per_group`
+([G], mean of max_{c in g} share), `active_sample_fraction_per_channel` (share of samples whose m_bc = mean_p |y| reaches
+`tracking.near_zero_threshold`) and `sample_variation_per_channel` (population std of m_bc over the samples divided by its mean,
+0 where the mean is 0: high for an input-selective channel, 0 for one that is equally active everywhere).  G and eps are the
+module's own on a GroupNorm, `tracking.group_count` (32) and `tracking.group_eps` (1e-6) elsewhere, a target's `groups:` over
+both; a target whose channels do not divide into G groups is refused if it names one of the first three.  All five derive from
+the per-(sample, channel) sums of y, y^2 and |y| (per_sample_sums in a hook, ONE ops.changroup pass on a device-served layer)
+through ops.changroup_metrics, whose result -- sums over the samples and the sample count -- is what a layer keeps: forwards
+and ranks combine by adding, exactly, whatever their batch sizes; step() makes one transfer per layer.
 """
 import logging
 from collections import defaultdict
@@ -86,6 +100,17 @@ SALIENCY_METRIC = "taylor_saliency_per_channel"
 # valid only at GRAD_POINT; one pass over (output, gradient) serves all (the first, third and fourth are the rows of its sums)
 CHANGRAD_METRICS = (MEANGRAD_METRIC, ABSMAXGRAD_METRIC, GAINGRAD_METRIC, SALIENCY_METRIC)
 GRAD_POINT = "output_grad"
+SHARE_METRIC = "group_variance_share_per_channel"
+NRMS_METRIC = "normalized_rms_per_channel"
+DOMINANCE_METRIC = "group_dominance_per_group"
+ACTIVE_METRIC = "active_sample_fraction_per_channel"
+VARIATION_METRIC = "sample_variation_per_channel"
+GROUP_METRICS = (SHARE_METRIC, NRMS_METRIC, DOMINANCE_METRIC)  # need C % G == 0
+SAMPLE_METRICS = (ACTIVE_METRIC, VARIATION_METRIC)
+CHANGROUP_METRICS = GROUP_METRICS + SAMPLE_METRICS  # accepted beside KNOWN_METRICS; one pass of per-sample sums serves all
+GROUP_COUNT = 32      # default of tracking.group_count (the VAE's GroupNorm(32))
+GROUP_EPS = 1e-6      # default of tracking.group_eps
+SQUASHED_SHARE = 0.1  # a channel whose variance share is below this fraction of the uniform share 1 / cg counts as squashed
 ZERO_GRADIENT_THRESHOLD = 0.0  # default of tracking.zero_gradient_threshold: a channel whose mean |g| is not above it got no gradient
 REDUNDANCY_THRESHOLD = 0.95  # default of tracking.redundancy_threshold: |rho| above it marks a redundant pair / channel
 
@@ -155,6 +180,29 @@ def channel_covariance(tensor: torch.Tensor) -> torch.Tensor:
     return torch.cov(yc).reshape(yc.shape[0], yc.shape[0])
 
 
+def per_sample_sums(tensor: torch.Tensor) -> torch.Tensor:
+    """what ops.changroup computes, with torch on the tensor's device: float64 [B, C, 3] = sum y, sum y^2, sum |y| over all
+    trailing axes of every (sample, channel).  Channel is dim 1; a tensor without a channel axis is one channel of one sample.
+    The stored values are widened exactly, so every square is exact and every sum float64."""
+    t = tensor.detach()
+    t3 = t.reshape(t.shape[0], t.shape[1], -1) if t.ndim >= 2 else t.reshape(1, 1, -1)
+    y = t3.double()
+    return torch.stack([y.sum(dim=2), (y * y).sum(dim=2), y.abs().sum(dim=2)], dim=2)
+
+
+def changroup_summary(chan: np.ndarray, grp: np.ndarray, samples: float) -> Dict[str, np.ndarray]:
+    """the five CHANGROUP_METRICS from the sufficient sums a layer keeps (ops.changroup_metrics, added over forwards and ranks):
+    chan float64 [5, C] = sums over the samples of share, nrms, m, m^2, [m >= tau]; grp [G] = sum of dom; in float64 on the host"""
+    chan, S = np.asarray(chan, dtype=np.float64), float(samples)
+    mean = chan[2] / S
+    with np.errstate(invalid="ignore", divide="ignore"):
+        var = np.where(chan[3] / S - mean * mean < 0.0, 0.0, chan[3] / S - mean * mean)  # (a NaN stays)
+        variation = np.where(mean == 0.0, 0.0, np.sqrt(var) / mean)
+    return {SHARE_METRIC: (chan[0] / S).astype(np.float32), NRMS_METRIC: (chan[1] / S).astype(np.float32),
+            DOMINANCE_METRIC: (np.asarray(grp, dtype=np.float64) / S).astype(np.float32),
+            ACTIVE_METRIC: (chan[4] / S).astype(np.float32), VARIATION_METRIC: variation.astype(np.float32)}
+
+
 def compute_grad_metrics(a: torch.Tensor, g: torch.Tensor):
     """what ops.changrad computes, with torch on the tensors' device: (sums float64 [3, C], absmax fp32 [C]); the rows of sums are
     mean |g| over batch and all trailing axes, the gain gradient sum_b sum_p a g and the saliency (1 / B) sum_b |sum_p a g|.
@@ -175,12 +223,15 @@ def compute_grad_metrics(a: torch.Tensor, g: torch.Tensor):
     return sums, absmax
 
 
-def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshold: float = NEAR_ZERO_THRESHOLD) -> Dict[str, Any]:
+def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshold: float = NEAR_ZERO_THRESHOLD,
+                    group: Optional[tuple] = None) -> Dict[str, Any]:
     """slow-path formulas, identical to monitor.py:56-80; the three CHANHIST_METRICS are what ops.chanhist computes.  Each of
     the CHANCOV_METRICS named gets the forward's float64 covariance (one tensor, shared, on the tensor's device): step()
-    derives the metric from the average over the forwards."""
+    derives the metric from the average over the forwards.  Each of the CHANGROUP_METRICS named gets the forward's
+    (chan, grp, samples) of ops.changroup_metrics on per_sample_sums(tensor) (one tuple, shared); group = (G or None, eps)."""
     out: Dict[str, Any] = {}
     cov = None
+    gsum, group_ok = None, True
     if not isinstance(tensor, torch.Tensor):
         logger.warning(f"Cannot calculate metrics for non-tensor type: {type(tensor)}")
         return out
@@ -190,6 +241,19 @@ def compute_metrics(tensor: torch.Tensor, metrics: List[str], near_zero_threshol
                 if cov is None:
                     cov = channel_covariance(tensor)
                 out[name] = cov
+            elif name in CHANGROUP_METRICS:
+                if gsum is None:  # once per tensor, whatever happens
+                    from vaehip.ops import changroup_metrics
+                    G, eps = group if group is not None else (GROUP_COUNT, GROUP_EPS)
+                    sums = per_sample_sums(tensor)
+                    hw = int(np.prod(tensor.shape[2:])) if tensor.ndim >= 2 else tensor.numel()
+                    if G is not None and sums.shape[1] % G:  # the sample metrics are still served
+                        logger.error(f"Metrics {[m for m in metrics if m in GROUP_METRICS]}: {sums.shape[1]} channels do not divide "
+                                     f"into {G} groups.")
+                        G, group_ok = None, False
+                    gsum = changroup_metrics(sums, hw, G, eps, near_zero_threshold)
+                if group_ok or name in SAMPLE_METRICS:
+                    out[name] = gsum
             elif name == HIST_METRIC:
                 yc = _per_channel(tensor)
                 idx = log2_bins(yc) + torch.arange(yc.shape[0], device=yc.device)[:, None] * HIST_BINS
@@ -269,6 +333,34 @@ class _CovSum:
         self.n += 1
 
 
+class _GroupSum:
+    """a layer's running sums of ops.changroup_metrics results -- chan float64 [5, C], grp float64 [G] and the sample count --
+    shared by the CHANGROUP_METRICS the layer tracks (resolved in step()); added over the ranks as well unless sync is off"""
+    __slots__ = ("chan", "grp", "samples", "forwards")
+
+    def __init__(self):
+        self.chan, self.grp, self.samples, self.forwards = None, None, 0, 0
+
+    def add(self, chan: torch.Tensor, grp: torch.Tensor, samples: int):
+        # copies: the engine shares one result among its trackers
+        self.chan = chan.clone() if self.chan is None else self.chan.add_(chan)
+        self.grp = grp.clone() if self.grp is None else self.grp.add_(grp)
+        self.samples += int(samples)
+        self.forwards += 1
+
+
+def _buffer_group(buf, name: str, res: tuple, seen: set):
+    """add a forward's (chan, grp, samples) to the layer's running sums (once per forward: `seen`) and list them under `name`"""
+    acc = next((buf[m][0] for m in CHANGROUP_METRICS if m in buf and buf[m]), None)
+    if acc is None:
+        acc = _GroupSum()
+    if id(acc) not in seen:
+        seen.add(id(acc))
+        acc.add(*res)
+    if not buf[name]:
+        buf[name].append(acc)
+
+
 def _buffer_cov(buf, name: str, cov: torch.Tensor, device_served: bool, seen: set):
     """add a forward's covariance to the layer's running sum (once per forward: `seen`) and list the sum under `name`"""
     acc = next((buf[m][0] for m in CHANCOV_METRICS if m in buf and buf[m]), None)
@@ -295,6 +387,10 @@ class ActivityMonitor:
         self.sync_across_ranks = bool(self.config.get("sync_across_ranks", True))
         self.near_zero_threshold = float(self.config.get("near_zero_threshold", NEAR_ZERO_THRESHOLD))
         self.redundancy_threshold = float(self.config.get("redundancy_threshold", REDUNDANCY_THRESHOLD))
+        self.group_count = int(self.config.get("group_count", GROUP_COUNT))
+        self.group_eps = float(self.config.get("group_eps", GROUP_EPS))
+        self._groups: Dict[str, tuple] = {}  # layer id -> (G or None, eps) of its CHANGROUP_METRICS
+        self._refused: set = set()  # layer ids dropped at their first forward: channels unknown at registration, C % G != 0
         self.zero_gradient_threshold = float(self.config.get("zero_gradient_threshold", ZERO_GRADIENT_THRESHOLD))
         if self.config.get("enabled", False):
             self._register_hooks()
@@ -313,10 +409,13 @@ class ActivityMonitor:
     def _device_sink(self, layer_id: str, metrics: List[str]) -> Callable:
         """engine sink of a device-served layer: buffers device tensors only, one entry per metric in config order (the
         order compute_metrics appends in); the moments vector and the histogram triple are shared by the metrics they serve,
-        the covariance goes into the layer's running sum"""
+        the covariance and the per-sample sums' metrics go into the layer's running sums"""
         def sink(mom: Optional[torch.Tensor], fmap: Optional[torch.Tensor], chanhist: Optional[tuple] = None,
-                 chancov: Optional[tuple] = None):
+                 chancov: Optional[tuple] = None, changroup: Optional[tuple] = None):
             buf = self.hook_collected_buffer[layer_id]
+            gres = None
+            if changroup is not None and self._undivided(layer_id, changroup[0].shape[1]):
+                return
             hist = _ChanHist(chanhist) if chanhist is not None else None
             seen: set = set()
             for name in metrics:
@@ -325,6 +424,12 @@ class ActivityMonitor:
                         buf[name].append(fmap)
                 elif name in CHANCOV_METRICS:
                     _buffer_cov(buf, name, chancov[0], True, seen)
+                elif name in CHANGROUP_METRICS:
+                    if gres is None:  # B * C numbers, torch ops on the device: nothing synchronises the host
+                        from vaehip.ops import changroup_metrics
+                        G, eps = self._groups[layer_id]
+                        gres = changroup_metrics(changroup[0], changroup[1], G, eps, self.near_zero_threshold)
+                    _buffer_group(buf, name, gres, seen)
                 elif name in CHANHIST_METRICS:
                     buf[name].append(hist)
                 else:
@@ -372,10 +477,14 @@ class ActivityMonitor:
             else:
                 t = hook_output
             if isinstance(t, torch.Tensor):
+                if layer_id in self._groups and self._undivided(layer_id, t.shape[1] if t.ndim >= 2 else 1):
+                    return
                 seen: set = set()
-                for k, v in compute_metrics(t, metrics, self.near_zero_threshold).items():
+                for k, v in compute_metrics(t, metrics, self.near_zero_threshold, self._groups.get(layer_id)).items():
                     if k in CHANCOV_METRICS:
                         _buffer_cov(self.hook_collected_buffer[layer_id], k, v, False, seen)
+                    elif k in CHANGROUP_METRICS:
+                        _buffer_group(self.hook_collected_buffer[layer_id], k, v, seen)
                     else:
                         self.hook_collected_buffer[layer_id][k].append(v)
         return fn
@@ -422,12 +531,19 @@ class ActivityMonitor:
                 if bad:
                     logger.error(f"Metrics {bad} of layer {name} need capture_point '{GRAD_POINT}', not '{point}'. Skipping.")
                     continue
+                if any(m in CHANGROUP_METRICS for m in metrics):
+                    try:
+                        self._groups[layer_id] = self._group_of(layer, point, conf, [m for m in metrics if m in GROUP_METRICS], engine)
+                    except ValueError as e:
+                        logger.error(f"Metrics {[m for m in metrics if m in GROUP_METRICS]} of layer {name} ({point}): {e} Skipping.")
+                        continue
                 if engine is not None and list(metrics) == [FUSED_METRIC]:
                     self.hooks.append(engine.add_tracker(layer, point, self._sink(layer_id)))
                     self.fused_layers.append(layer_id)
                     logger.info(f"Registered FUSED device tracker for layer: {name} ({point})")
                 elif self.device_metrics and engine is not None and metrics and \
-                        all(m in KNOWN_METRICS + CHANCOV_METRICS for m in metrics) and engine.metric_trackable(layer):
+                        all(m in KNOWN_METRICS + CHANCOV_METRICS + CHANGROUP_METRICS for m in metrics) and \
+                        engine.metric_trackable(layer):
                     mlist = list(dict.fromkeys(metrics))
                     extra = {"near_zero_threshold": self.near_zero_threshold} if any(m in CHANHIST_METRICS for m in mlist) else {}
                     self.hooks.append(engine.add_tracker(layer, point, self._device_sink(layer_id, mlist), metrics=mlist,
@@ -445,12 +561,53 @@ class ActivityMonitor:
             except Exception as e:
                 logger.error(f"Unexpected error registering hook for {layer_id}: {e}", exc_info=True)
 
+    def _group_of(self, layer, point: str, conf: Dict[str, Any], group_metrics: List[str], engine) -> tuple:
+        """(G, eps) of a target's CHANGROUP_METRICS: a `groups:` entry of the target, else the module's own on a GroupNorm, else
+        tracking.group_count; eps the GroupNorm's own or tracking.group_eps.  (None, eps) when only the sample metrics are asked
+        for.  ValueError: a group metric is asked for and G is not a positive integer, or the channels at the capture point do
+        not divide into G groups (the 3- and 4-channel ends, the 8-channel latent moments).  Channels are known for a GroupNorm,
+        a convolution and both ends of every engine module; for another torch module the first forward decides (_undivided)."""
+        is_norm = isinstance(layer, torch.nn.GroupNorm)
+        eps = float(layer.eps) if is_norm else self.group_eps
+        if not group_metrics:
+            return None, eps
+        G = conf.get("groups", layer.num_groups if is_norm else self.group_count)
+        if isinstance(G, bool) or not isinstance(G, int) or G < 1:
+            raise ValueError(f"groups must be a positive integer, not {G!r}.")
+        if is_norm:
+            channels = layer.num_channels
+        elif isinstance(layer, torch.nn.Conv2d):
+            channels = layer.in_channels if point == "input" else layer.out_channels
+        elif engine is not None and engine.metric_trackable(layer):
+            channels = engine._in_channels(layer) if point == "input" else engine._out_channels(layer)
+        else:
+            channels = None
+        if channels is not None and channels % G:
+            raise ValueError(f"{channels} channels do not divide into {G} GroupNorm groups.")
+        return G, eps
+
+    def _undivided(self, layer_id: str, channels: int) -> bool:
+        """at a forward: does a layer that tracks a group metric turn out to have channels that do not divide into its groups (a
+        plain torch module, whose channels registration could not know)?  Then the layer is dropped, as registration would have
+        dropped it, with ONE logged error; no exception leaves a forward"""
+        if layer_id in self._refused:
+            return True
+        G = self._groups.get(layer_id, (None,))[0]
+        if G is None or channels % G == 0:
+            return False
+        self._refused.add(layer_id)
+        self.hook_collected_buffer.pop(layer_id, None)
+        logger.error(f"Group metrics of layer {layer_id}: {channels} channels do not divide into {G} GroupNorm groups. "
+                     f"The layer is no longer tracked.")
+        return True
+
     def remove_hooks(self):
         for h in self.hooks:
             h.remove()
         self.hooks = []
         self.fused_layers = []
         self.device_layers = []
+        self._refused = set()
 
     # ------------------------------------------------------------------ aggregation
     def _world(self) -> int:
@@ -535,6 +692,25 @@ class ActivityMonitor:
                              MAXCORR_METRIC: summary["max_abs"].astype(np.float32),
                              RANK_METRIC: float(summary["effective_rank"])}[metric]
 
+    def _changroup_to_host(self, metric_data: Dict[str, list]):
+        """a layer's running per-sample sums -> per CHANGROUP metric the ONE host value step() stores, in place: fp32 [C] ([G]
+        for the dominance).  Forwards are already added; ranks are added here (sums and sample counts: exact whatever the ranks'
+        batch sizes).  ONE transfer: a float64 vector of 5 C + G + 1 numbers"""
+        acc = next((v for values in metric_data.values() for v in values if isinstance(v, _GroupSum)), None)
+        if acc is None:
+            return
+        Cc = acc.chan.shape[1]
+        flat = torch.cat([acc.chan.reshape(-1), acc.grp.reshape(-1),
+                          torch.tensor([float(acc.samples)], dtype=torch.float64, device=acc.chan.device)])
+        if self._world() > 1:
+            self._same_forward_count(acc.forwards, flat.device)
+            torch.distributed.all_reduce(flat)
+        host = flat.cpu().numpy()
+        summary = changroup_summary(host[:5 * Cc].reshape(5, Cc), host[5 * Cc:-1], host[-1])
+        for metric, values in metric_data.items():
+            if values and isinstance(values[0], _GroupSum):
+                values[0] = summary[metric]
+
     def _changrad_to_host(self, metric_data: Dict[str, list]):
         """the buffered (sums, absmax) pairs of a layer -> per backward pass the host vectors of each metric, in place: fp32 [C]
         each.  Across ranks the sums are averaged like the mean |A| vectors and the maxima maxed on their bit patterns.  ONE
@@ -615,6 +791,7 @@ class ActivityMonitor:
                 self._device_to_host(metric_data)
             self._chanhist_to_host(metric_data)
             self._chancov_to_host(metric_data)
+            self._changroup_to_host(metric_data)
             self._changrad_to_host(metric_data)
         for layer_id, metric_data in self.hook_collected_buffer.items():
             processed[layer_id] = {}
@@ -638,6 +815,21 @@ class ActivityMonitor:
                             log[key + "_overall_max"] = np.max(agg)
                         elif metric == RANK_METRIC:
                             log[key] = agg
+                    elif metric in CHANGROUP_METRICS:  # one value, of the sums over every sample since the last step()
+                        agg = values[0]
+                        if metric == SHARE_METRIC:
+                            G = self._groups.get(layer_id, (None,))[0] or 1  # uniform share 1 / cg = G / C
+                            log[key + "_squashed_channels"] = int(np.sum(agg < SQUASHED_SHARE * G / max(len(agg), 1)))
+                            log[key + "_overall_max"] = np.max(agg)
+                        elif metric == DOMINANCE_METRIC:
+                            log[key + "_overall_max"] = np.max(agg)
+                            log[key + "_most_dominated_group"] = int(np.argmax(agg))
+                        elif metric == NRMS_METRIC:
+                            log[key + "_overall_min"] = np.min(agg)
+                        elif metric == ACTIVE_METRIC:
+                            log[key + "_overall_min"] = np.min(agg)
+                        else:
+                            log[key + "_overall_max"] = np.max(agg)
                     elif metric == HIST_METRIC:  # summed over the buffered forwards
                         agg = np.sum(np.stack([np.asarray(v, dtype=np.int64) for v in values]), axis=0)
                         log[key + "_top_bin_share"] = float(agg[..., -1].sum()) / max(float(agg.sum()), 1.0)
@@ -724,6 +916,18 @@ class ActivityMonitor:
                         add("max_abs_correlation_overall_mean", float(np.mean(arr)))
                         add("max_abs_correlation_overall_max", float(np.max(arr)))
                         add("max_abs_correlation_redundant_channels", int(np.sum(arr > self.redundancy_threshold)))
+                    elif metric in CHANGROUP_METRICS:
+                        kind = metric[:-len("_per_channel")] if metric != DOMINANCE_METRIC else "group_dominance"
+                        add(kind + "_overall_mean", float(np.mean(arr)))
+                        add(kind + "_overall_min", float(np.min(arr)))
+                        add(kind + "_overall_max", float(np.max(arr)))
+                        if metric == SHARE_METRIC:  # channels below a tenth of the uniform share 1 / cg: squashed by a neighbour
+                            G = self._groups.get(layer_id, (None,))[0] or 1
+                            add(kind + "_squashed_channels", int(np.sum(arr < SQUASHED_SHARE * G / max(len(arr), 1))))
+                        elif metric == DOMINANCE_METRIC:
+                            add(kind + "_argmax_group", int(np.argmax(arr)))
+                        elif metric == ACTIVE_METRIC:  # channels no sample activates
+                            add(kind + "_silent_channels", int(np.sum(arr == 0.0)))
                     elif metric == HIST_METRIC:
                         total = arr.reshape(-1, arr.shape[-1]).sum(axis=0)  # the tensor's histogram: all channels together
                         rows = arr.reshape(-1, arr.shape[-1]).sum(axis=1)

@@ -11,7 +11,9 @@ device-side reductions instead (add_tracker), without any tensor or host sync.  
 subset of the ActivityMonitor metrics at a 4-D capture point the same way: one moments pass (ops.moments) and one
 histogram pass (ops.chanhist: magnitude histogram, near-zero count, max |A| per channel) per forward on the tensor a hook
 would have received, and one covariance pass (ops.chancov: the channel covariance behind the correlation, redundancy and
-effective-rank metrics), each only if a metric it serves is asked for, and a full-map snapshot only when the caller says one is due.
+effective-rank metrics) and one per-sample pass (ops.changroup: the per-(sample, channel) sums behind the GroupNorm group dynamics
+and per-sample activity metrics), each only if a metric it serves is asked for, and a full-map snapshot only when the caller says
+one is due.
 add_grad_tracker serves the backward pass: per backward of a module, one ops.changrad pass over (the output the forward kept, the
 gradient the tape carries to it) gives the per-channel gradient metrics (CHANGRAD_METRICS); it launches nothing unless registered.
 add_activation_penalty acts at the same points: one ops.actreg_stats pass over the output in the forward of forward_backward gives
@@ -38,7 +40,11 @@ MOMENT_METRICS = ("mean_abs_activation_per_channel", "mean_activation", "std_act
 CHANHIST_METRICS = ("log2_histogram_per_channel", "abs_max_activation_per_channel", "near_zero_fraction_per_channel")
 # one ops.chancov pass: (covariance, mean); the monitor derives the other three from the covariance
 CHANCOV_METRICS = ("channel_covariance_matrix", "channel_correlation_matrix", "max_abs_correlation_per_channel", "effective_rank")
+# one ops.changroup pass: float64 [B, C, 3] sums of y, y^2, |y| per (sample, channel); the monitor derives all five from them
+CHANGROUP_METRICS = ("group_variance_share_per_channel", "normalized_rms_per_channel", "group_dominance_per_group",
+                     "active_sample_fraction_per_channel", "sample_variation_per_channel")
 DEVICE_METRICS = MOMENT_METRICS + CHANHIST_METRICS + CHANCOV_METRICS + ("full_activation_map",)
+SERVED_METRICS = DEVICE_METRICS + CHANGROUP_METRICS  # everything add_tracker(metrics=...) serves
 # one ops.changrad pass over (output, gradient of the loss with respect to it) per backward: add_grad_tracker only
 CHANGRAD_METRICS = ("mean_abs_gradient_per_channel", "abs_max_gradient_per_channel", "gain_gradient_per_channel",
                     "taylor_saliency_per_channel")
@@ -84,12 +90,14 @@ class _PenaltyHandle:
 class _MetricTracker:
     """one add_tracker(metrics=...) registration: sink(moments or None, full map or None) per forward; a registration that
     names one of CHANHIST_METRICS gets sink(moments or None, full map or None, chanhist=(hist, nzero, absmax)) instead, one
-    that names one of CHANCOV_METRICS the keyword chancov=(cov, mean)"""
+    that names one of CHANCOV_METRICS the keyword chancov=(cov, mean), one that names one of CHANGROUP_METRICS the keyword
+    changroup=(sums, HW)"""
 
     def __init__(self, metrics, sink, map_due, tau=1e-3):
         self.moments = any(m in MOMENT_METRICS for m in metrics)
         self.chanhist = any(m in CHANHIST_METRICS for m in metrics)
         self.chancov = any(m in CHANCOV_METRICS for m in metrics)
+        self.changroup = any(m in CHANGROUP_METRICS for m in metrics)
         self.tau = float(tau)
         self.full_map = "full_activation_map" in metrics
         self.sink, self.map_due = sink, map_due
@@ -216,20 +224,21 @@ class Engine:
     def add_tracker(self, module: nn.Module, point: str, sink: Callable, metrics: Optional[List[str]] = None,
                     map_due: Optional[Callable[[], bool]] = None, near_zero_threshold: float = 1e-3):
         """metrics None: fused `mean_abs_activation_per_channel` for `module`'s input or output: sink(tensor[C]) per forward.
-        metrics: any subset of DEVICE_METRICS on a module that metric_trackable() accepts: sink(moments, fmap) per forward,
+        metrics: any subset of SERVED_METRICS on a module that metric_trackable() accepts: sink(moments, fmap) per forward,
         with moments = ops.moments(tensor) (None when only the full map is asked for) and fmap an fp32 NHWC copy of the
         tensor when `full_activation_map` is asked for and map_due() (default: always) says a snapshot is wanted, else None.
         When metrics names one of CHANHIST_METRICS the sink is called with a third, keyword argument as well:
         chanhist = ops.chanhist(tensor, tau=near_zero_threshold), the (hist, nzero, absmax) triple of that forward; when it
         names one of CHANCOV_METRICS, with the keyword argument chancov = ops.chancov(tensor), the forward's float64
-        (covariance [C, C], mean [C])."""
+        (covariance [C, C], mean [C]); when it names one of CHANGROUP_METRICS, with the keyword argument
+        changroup = (ops.changroup(tensor), H * W): the forward's float64 [B, C, 3] per-sample sums and their pixel count."""
         assert point in ("input", "output")
         if metrics is None:
             self._trackers.setdefault(id(module), {}).setdefault(point, []).append(sink)
             return _TrackHandle(self._trackers, id(module), point, sink)
-        bad = [m for m in metrics if m not in DEVICE_METRICS]
+        bad = [m for m in metrics if m not in SERVED_METRICS]
         if bad or not metrics:
-            raise ValueError(f"device trackers serve {DEVICE_METRICS}, not {list(metrics)}")
+            raise ValueError(f"device trackers serve {SERVED_METRICS}, not {list(metrics)}")
         if not self.metric_trackable(module):
             raise ValueError(f"{type(module).__name__}: no 4-D capture point the engine can reduce")
         t = _MetricTracker(metrics, sink, map_due, near_zero_threshold)
@@ -279,6 +288,24 @@ class Engine:
         elif isinstance(module, (A.Encoder, A.Decoder)):
             module = module.conv_out
         return module.weight.shape[0]
+
+    @staticmethod
+    def _in_channels(module: nn.Module) -> int:
+        """channels of the input of a module that metric_trackable() accepts"""
+        from . import autoencoder as A
+        if isinstance(module, A.HipGroupNorm):
+            return module.num_channels
+        if isinstance(module, A.ResnetBlock2D):
+            return module.norm1.num_channels
+        if isinstance(module, A.Attention):
+            return module.group_norm.num_channels
+        if isinstance(module, (A.UNetMidBlock2D, A.DownEncoderBlock2D, A.UpDecoderBlock2D)):
+            return module.resnets[0].norm1.num_channels
+        if isinstance(module, (A.Downsample2D, A.Upsample2D)):
+            module = module.conv
+        elif isinstance(module, (A.Encoder, A.Decoder)):
+            module = module.conv_in
+        return module.in_channels
 
     def add_activation_penalty(self, module: nn.Module, spec: ActivationPenalty) -> _PenaltyHandle:
         """a loss term on `module`'s output (vaehip.actreg.ActivationPenalty), for the modules add_grad_tracker accepts.  In the
@@ -376,12 +403,13 @@ class Engine:
     @staticmethod
     def _emit(ts: List[_MetricTracker], x: torch.Tensor, st: Optional[Stats] = None, xf: int = XF_NONE,
               make_map: Optional[Callable[[], torch.Tensor]] = None):
-        """serve device trackers from y = XF(x): one moments pass, one chanhist pass (per near-zero threshold) and one chancov
-        pass shared by all that ask for them; a full map only for those whose snapshot is due (make_map: the materialised y when xf is not
+        """serve device trackers from y = XF(x): one moments pass, one chanhist pass (per near-zero threshold), one chancov
+        pass and one changroup pass shared by all that ask for them; a full map only for those whose snapshot is due (make_map: the materialised y when xf is not
         XF_NONE, else a copy of x)"""
         mom = ops.moments(x, st, xf) if any(t.moments for t in ts) else None
         hists = {tau: ops.chanhist(x, st, xf, tau) for tau in dict.fromkeys(t.tau for t in ts if t.chanhist)}
         cov = ops.chancov(x, st, xf) if any(t.chancov for t in ts) else None
+        grp = (ops.changroup(x, st, xf), x.shape[1] * x.shape[2]) if any(t.changroup for t in ts) else None
         fmap = None
         for t in ts:
             f = None
@@ -396,6 +424,8 @@ class Engine:
                 kw["chanhist"] = hists[t.tau]
             if t.chancov:
                 kw["chancov"] = cov
+            if t.changroup:
+                kw["changroup"] = grp
             t.sink(mom if t.moments else None, f, **kw)
 
     def _mean_abs(self, t: torch.Tensor) -> torch.Tensor:

@@ -46,7 +46,7 @@ class WgradArgs(C.Structure):
 
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-EXPECTED_ABI = 24  # vae_abi_version() of the library these structures and signatures describe
+EXPECTED_ABI = 25  # vae_abi_version() of the library these structures and signatures describe
 
 # name -> argtypes (every function returns int); must list EVERY symbol of include/vaehip.h
 SIGNATURES = {
@@ -92,6 +92,9 @@ SIGNATURES = {
     "vae_chanhist_workspace": [i32, i32, i32, i32, C.POINTER(i64)],
     "vae_chanhist_partial": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp],
     "vae_chanhist_final": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+    "vae_changroup_workspace": [i32, i32, i32, i32, C.POINTER(i64)],
+    "vae_changroup_partial": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],
+    "vae_changroup_final": [vp, i32, i32, i32, i32, vp, vp],
     "vae_changrad_workspace": [i32, i32, i32, i32, C.POINTER(i64)],
     "vae_changrad_partial": [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "vae_changrad_final": [vp, i32, i32, i32, i32, vp, vp, vp],

@@ -963,6 +963,92 @@ def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, 
     return hist, nzero, absmax
 
 
+def changroup_chunks(B: int, HW: int, Cc: int) -> int:
+    """pixel chunks per image of changroup(): B * nchunk * (tiles of 256 channels) workgroups near _GN_TARGET, a chunk no shorter
+    than 16 pixels per pixel row of a workgroup, and every chunk non-empty (the rule of changrad_chunks: the two kernels share
+    their layout).  The workspace, 3 doubles per (image, chunk, channel), stays below chanhist()'s 50 words at every shape: a
+    tile twice as wide gives at most twice the chunks."""
+    return changrad_chunks(B, HW, Cc)
+
+
+def changroup(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE) -> torch.Tensor:
+    """per-(sample, channel) sums of y = XF(x) in one read of x, no tensor materialised: a float64 [B, C, 3] device tensor of
+    S1 = sum y, S2 = sum y^2 and A = sum |y| over the H * W pixels of every (b, c).  y is evaluated in fp32, every sum is float64
+    from the first addition on (csrc/changroup.hip), in a fixed order: two calls agree bitwise.  A NaN or an infinity reaches the
+    sums of its own (b, c) only.  x, stats and xf as in moments(); nothing synchronises the host.  changroup_metrics() turns the
+    sums into the GroupNorm group dynamics and per-sample activity figures of the ActivityMonitor."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"changroup: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"changroup: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    if (stats is None) != (xf == XF_NONE):
+        raise ValueError("changroup: a GroupNorm transform (xf) needs its stats and stats need an xf")
+    if stats is not None:
+        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
+            raise ValueError(f"changroup: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
+    HW = H * W
+    nch = changroup_chunks(B, HW, Cc)
+    dev = x.device
+    n = C.c_int64(0)
+    lib.call("vae_changroup_workspace", B, HW, Cc, nch, C.byref(n))
+    ws = torch.empty((n.value,), device=dev, dtype=torch.float64)
+    sums = torch.empty((B, Cc, 3), device=dev, dtype=torch.float64)
+    lib.call("vae_changroup_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
+             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_changroup_final", _p(ws), B, HW, Cc, nch, _p(sums), _stream())
+    return sums
+
+
+def changroup_metrics(sums: torch.Tensor, HW: int, groups: Optional[int], eps: float, tau: float):
+    """the per-sample arithmetic behind the ActivityMonitor's group and sample metrics, in float64 on the device of `sums`
+    ([B, C, 3] = sum y, sum y^2, sum |y| over the n = HW pixels of every (b, c): changroup(), or the same sums from torch).
+    With cg = C / groups and g(c) = c // cg:
+        mu_bg = sum_{c in g} S1_bc / (n cg)                   v_bc = max(0, S2_bc - 2 mu_bg S1_bc + n mu_bg^2)
+        V_bg = sum_{c in g} v_bc                              share_bc = v_bc / V_bg (0 where V_bg == 0)
+        nrms_bc = sqrt((v_bc / n) / (V_bg / (n cg) + eps))    dom_bg = max_{c in g} share_bc          m_bc = A_bc / n
+    Returns (chan float64 [5, C], grp float64 [G], B): the rows of chan are the sums over the B samples of share, nrms, m, m^2
+    and [m >= tau]; grp is the sum over the samples of dom.  groups None (no group metric asked for): the first two rows of chan
+    are zero and grp is empty.  Every monitor metric is a mean over samples of a per-sample quantity or a function of two such
+    means, so forwards and data-parallel ranks combine by adding these sums and the sample counts, whatever their batch sizes.
+    A NaN or an infinity in a (b, c) stays in the group figures of its (b, group) and in the sample figures of its channel."""
+    if sums.dim() != 3 or sums.shape[2] != 3 or sums.dtype != torch.float64:
+        raise ValueError(f"changroup_metrics: expected float64 [B, C, 3] sums, got {tuple(sums.shape)} {sums.dtype}")
+    B, Cc, _ = sums.shape
+    if not HW >= 1:
+        raise ValueError(f"changroup_metrics: HW = {HW}")
+    # n as a tensor: torch divides a device tensor by a Python number as a product with its rounded reciprocal, and a constant
+    # channel's v is exactly 0 only if mu is the correctly rounded quotient
+    n = torch.full((), float(HW), device=sums.device, dtype=torch.float64)
+    chan = torch.zeros((5, Cc), device=sums.device, dtype=torch.float64)
+    if groups is None:
+        grp = torch.zeros((0,), device=sums.device, dtype=torch.float64)
+    else:
+        G = int(groups)
+        if G < 1 or Cc % G:
+            raise ValueError(f"changroup_metrics: {Cc} channels do not divide into {groups} groups")
+        cg = Cc // G
+        S1 = sums[:, :, 0].reshape(B, G, cg)
+        S2 = sums[:, :, 1].reshape(B, G, cg)
+        ncg = n * float(cg)
+        mu = S1.sum(dim=2, keepdim=True) / ncg
+        v = S2 - 2.0 * mu * S1 + n * mu * mu
+        v = torch.where(v < 0.0, torch.zeros_like(v), v)  # (not clamp: a NaN stays)
+        V = v.sum(dim=2, keepdim=True)
+        share = torch.where(V == 0.0, torch.zeros_like(v), v / V)
+        nrms = torch.sqrt((v / n) / (V / ncg + float(eps)))
+        chan[0] = share.reshape(B, Cc).sum(dim=0)
+        chan[1] = nrms.reshape(B, Cc).sum(dim=0)
+        # the largest share of a group; a NaN in the group makes it NaN (amax propagates)
+        grp = share.amax(dim=2).sum(dim=0)
+    m = sums[:, :, 2] / n
+    chan[2] = m.sum(dim=0)
+    chan[3] = (m * m).sum(dim=0)
+    chan[4] = (m >= float(tau)).to(torch.float64).sum(dim=0)
+    return chan, grp, B
+
+
 def changrad_chunks(B: int, HW: int, Cc: int) -> int:
     """pixel chunks per image of changrad(): B * nchunk * (tiles of 256 channels) workgroups near _GN_TARGET, a chunk no shorter
     than 16 pixels per pixel row of a workgroup, and every chunk non-empty"""
