@@ -137,3 +137,30 @@ def check_within_bounds(hist, nzero, absmax, y, d, tau, n_rows):
     err = np.abs(absmax.astype(np.float64) - np.abs(y[k, cols]))
     assert (err <= d[k, cols]).all(), (err.max(), d[k, cols].min())
     return bd
+
+
+# The edges of the frame the statistics partial passes share (csrc/chanstat_common.h), as (C, B, H, W, layout): a narrow tile of 128
+# pixel rows whose four-in-flight loop and tail both run; a second channel tile of one unit of four channels (tiles of 256
+# channels: C = 260, chanhist's 128: C = 132 -- 33 units, 7 pixel rows, elsewhere); the scalar path; the view buf[..., :C] of a buffer
+# four channels wider; a base one element off, which puts C % 4 == 0 on the scalar path.
+FRAME_CASES = [(8, 2, 24, 24, "plain"), (260, 2, 9, 7, "plain"), (132, 2, 9, 7, "plain"), (3, 1, 5, 5, "plain"),
+               (8, 2, 24, 24, "prefix"), (8, 2, 24, 24, "offset")]
+
+
+def frame_params(xfs=(0,)):
+    """FRAME_CASES x storage x transform; a base one element off has no transform (the statistics' rows start at the buffer's)"""
+    return [c + (dt, xf) for c in FRAME_CASES for dt in (torch.float32, torch.bfloat16) for xf in xfs if not (xf and c[4] == "offset")]
+
+
+def frame_layout(t: torch.Tensor, layout: str) -> torch.Tensor:
+    """the values of t [B, H, W, C] in the layout of a FRAME_CASES entry; what lies around a view is 1e6"""
+    Cc = t.shape[3]
+    if layout == "prefix":
+        buf = torch.full(tuple(t.shape[:3]) + (Cc + 4,), 1e6, device=t.device, dtype=t.dtype)
+        buf[..., :Cc] = t
+        return buf[..., :Cc]
+    if layout == "offset":
+        flat = torch.full((t.numel() + 1,), 1e6, device=t.device, dtype=t.dtype)
+        flat[1:] = t.reshape(-1)
+        return flat[1:].view(t.shape)
+    return t

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import actreg_refs as R
+import chanhist_refs as HR
 from guarded import GuardedPool, guarded
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +122,18 @@ def test_offset_view_takes_the_scalar_path(cuda, kind, thr, weight, da, dg):
     c5 = torch.zeros(5, device=cuda)
     c5[1:] = ref[2]
     assert R.same_bits(ops.actreg_inject(a.contiguous(), g.contiguous(), kind, thr, c5[1:]), want)
+
+
+@pytest.mark.parametrize("kind,thr,weight", SPECS)
+@pytest.mark.parametrize("da", [F32, BF16])
+@pytest.mark.parametrize("Cc,B,H,W,layout", HR.FRAME_CASES)
+def test_at_the_edges_of_the_shared_frame(cuda, Cc, B, H, W, layout, da, kind, thr, weight):
+    """the statistics of an output in every layout; the gradient it is injected into is a plain tensor of the other storage"""
+    from vaehip import ops
+    a, g = R.draw((B, H, W, Cc), Cc * 131 + B * 7 + H)
+    a, g = HR.frame_layout(a.to(cuda).to(da), layout), g.to(cuda).to(BF16 if da == F32 else F32)
+    (sums, pen, coef), _ = _stats(a, kind, thr, weight)
+    R.check_inject(ops.actreg_inject(a, g, kind, thr, coef), a, g, kind, thr, coef)
 
 
 @pytest.mark.parametrize("da,dg", PAIRS)

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import changrad_refs as R
+import chanhist_refs as HR
 from guarded import GuardedPool, guarded
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +56,16 @@ def test_sweep_within_the_derived_bounds(cuda, Cc, da, dg, B, H, W):
     assert got[0].shape == (3, Cc) and got[0].dtype == torch.float64 and got[1].shape == (Cc,) and got[1].dtype == F32
     worst = _check(got, a, g)
     print(f"C={Cc} a={str(da)[6:]} g={str(dg)[6:]} {B}x{H}x{W}: worst error / bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("da,dg", PAIRS)
+@pytest.mark.parametrize("Cc,B,H,W,layout", HR.FRAME_CASES)
+def test_at_the_edges_of_the_shared_frame(cuda, Cc, B, H, W, layout, da, dg):
+    """the layout is that of the gradient; the output is a plain tensor (the operands' strides and alignments differ)"""
+    from vaehip import ops
+    a, g = R.draw((B, H, W, Cc), Cc * 131 + B * 7 + H)
+    a, g = a.to(cuda).to(da), HR.frame_layout(g.to(cuda).to(dg), layout)
+    _check(ops.changrad(a, g), a, g)
 
 
 @pytest.mark.parametrize("da,dg", PAIRS)

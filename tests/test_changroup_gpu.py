@@ -83,6 +83,14 @@ def test_sums_and_metrics_against_the_float64_references(cuda, Cc, dt, xf, B, H,
     _check(got, x, st, xf)
 
 
+@pytest.mark.parametrize("Cc,B,H,W,layout,dt,xf", R.HR.frame_params((0, 1, 2)))
+def test_at_the_edges_of_the_shared_frame(cuda, Cc, B, H, W, layout, dt, xf):
+    from vaehip import ops
+    x = R.HR.frame_layout(R.draw((B, H, W, Cc), Cc * 131 + xf * 7 + B * 3 + H).to(dt).to(cuda), layout)
+    st = _stats(B, x.stride(2), cuda, Cc + xf) if xf else None
+    _check(ops.changroup(x, st, xf), x, st, xf, vec=False if layout == "offset" else None)
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("B,H,W,Cc,G", [(3, 33, 31, 32, 8), (2, 16, 16, 64, 32), (1, 40, 40, 8, 2), (2, 33, 31, 132, 33)])
 def test_a_mean_a_thousand_sigma_keeps_its_variance(cuda, B, H, W, Cc, G, dt):

@@ -71,6 +71,20 @@ def test_exact_against_the_bit_pattern_reference(cuda, Cc, dt, B, H, W):
     _assert_exact(ops.chanhist(x, tau=TAU), x)
 
 
+@pytest.mark.parametrize("Cc,B,H,W,layout,dt,xf", R.frame_params((0, 1, 2)))
+def test_at_the_edges_of_the_shared_frame(cuda, Cc, B, H, W, layout, dt, xf):
+    """exact without a transform, inside the float64 bounds with one"""
+    from vaehip import ops
+    if xf == 0:
+        x = R.frame_layout(_wide((B, H, W, Cc), Cc * 131 + B * 7 + H).clamp(-6e4, 6e4).to(cuda).to(dt), layout)
+        _assert_exact(ops.chanhist(x, tau=TAU), x)
+    else:
+        g = torch.Generator(device="cpu").manual_seed(Cc * 131 + xf * 7 + B)
+        x = R.frame_layout((torch.randn((B, H, W, Cc), generator=g) * 1.3 + 0.4).to(cuda).to(dt), layout)
+        st = _stats(B, x.stride(2), cuda, Cc + xf)
+        _assert_bounded(ops.chanhist(x, st, xf, TAU), x, st, xf)
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 def test_exact_on_a_channel_prefix_view(cuda, dt):
     """the encoder's input: the 3-channel view x4[..., :3] of a 4-channel buffer, read in place; the pad channel must not leak"""

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import chanhist_refs as HR
+
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,6 +91,16 @@ def test_moments_against_float64(cuda, Cc, dt, xf, B, H, W):
     torch.cuda.synchronize()
     errs = _errors(got.cpu(), _ref(x, st, xf))
     _record(f"moments/C{Cc}/{str(dt)[6:]}/xf{xf}/{B}x{H}x{W}", errs)
+    assert max(errs) <= TOL, errs
+
+
+@pytest.mark.parametrize("Cc,B,H,W,layout,dt,xf", HR.frame_params((0, 1, 2)))
+def test_moments_at_the_edges_of_the_shared_frame(cuda, Cc, B, H, W, layout, dt, xf):
+    from vaehip import ops
+    g = torch.Generator(device="cpu").manual_seed(Cc * 131 + xf * 7 + B)
+    x = HR.frame_layout((torch.randn((B, H, W, Cc), generator=g) * 1.3 + 0.4).to(cuda).to(dt), layout)
+    st = _stats(B, x.stride(2), cuda, Cc + xf) if xf else None
+    errs = _errors(ops.moments(x, st, xf).cpu(), _ref(x, st, xf))
     assert max(errs) <= TOL, errs
 
 

@@ -42,10 +42,17 @@ status 1 otherwise).  Timed (--launches 0 skips it), one call of a C entry point
 points at the step's four shapes, fp32 storage at batch 16 and bf16 storage at batch 32, over a ring of operands larger than the
 memory-side cache, the moments passes, and the optimizer kernels, vae_sqnorm and the dead-weight scans at the arena's size; each case carries its own margin (twice |parent2 / parent - 1|, at least one rounding unit of the recorded medians).
 
-usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16|thin|stream]"""
+`--only chanstat`: the per-channel statistics kernels (csrc/track.hip's moments, chanhist.hip, chancov.hip, changrad.hip, changroup.hip,
+actreg.hip; what they share is csrc/chanstat_common.h), run like the streaming family.  A case is one call of an ops entry point
+(moments, chanhist, changroup, chancov, changrad, actreg_stats, actreg_inject) at the frame's edge shapes (tests/chanhist_refs.py
+FRAME_CASES) in every storage, transform and penalty kind; every tensor the call hands to the library -- operands, workspace,
+results -- is compared with the first arm's.  The timed cases are the same calls on rings of step-sized operands.
+
+usage: python tools/wino_seat_ab.py NEW.so PARENT.so [name=OTHER.so ...] [--launches 20] [--out FILE] [--only wino4|wino2|up|bf16|thin|stream|chanstat]"""
 import argparse
 import ctypes as C
 import functools
+import itertools
 import json
 import math
 import os
@@ -706,7 +713,101 @@ def stream_timed(dev):
     return cases
 
 
-def _stream_run(fn, dll, record):
+# ---- the per-channel statistics family (`--only chanstat`): one ops entry point per case, run like the streaming family
+def _w4(ptr, bf16, C, ld):  # vec4_ok of csrc/chanstat_common.h
+    return C % 4 == 0 and ld % 4 == 0 and (getattr(ptr, "value", 0) or 0) & (7 if bf16 else 15) == 0
+
+
+def _w_changrad(a):
+    return 4 if _w4(a[0], a[1], a[8], a[2]) and _w4(a[3], a[4], a[8], a[5]) else 1
+
+
+def _w_inject(a):
+    return 4 if (_w4(a[0], a[1], a[8], a[2]) and _w4(a[3], a[4], a[8], a[5]) and _w4(a[11], a[4], a[8], a[8]) and _w4(a[6], 0, 4, 4)) else 1
+
+
+CHANSTAT_KERNELS = {
+    "vae_moments_partial": STREAM_KERNELS["vae_moments_partial"], "vae_moments_final": STREAM_KERNELS["vae_moments_final"],
+    "vae_chanhist_partial": lambda a: [f"chanhist_partial_kernel<{_w_moments(a)},{_TF[a[1]]}>"], "vae_chanhist_final": lambda a: ["chanhist_final_kernel"],
+    "vae_changroup_partial": lambda a: [f"changroup_partial_kernel<{_w_moments(a)},{_TF[a[1]]}>"], "vae_changroup_final": lambda a: ["changroup_final_kernel"],
+    "vae_chancov_partial": lambda a: [f"chancov_partial_kernel<{_TF[_w_moments(a) == 4]},{_TF[a[1]]}>"], "vae_chancov_final": lambda a: ["chancov_final_kernel"],
+    "vae_changrad_partial": lambda a: [f"changrad_partial_kernel<{_w_changrad(a)},{_TF[a[1]]},{_TF[a[4]]}>"], "vae_changrad_final": lambda a: ["changrad_final_kernel"],
+    "vae_actreg_partial": lambda a: [f"actreg_partial_kernel<{4 if _w4(a[0], a[1], a[5], a[2]) else 1},{_TF[a[1]]}>"], "vae_actreg_final": lambda a: ["actreg_final_kernel"],
+    "vae_actreg_inject": lambda a: [f"actreg_inject_kernel<{a[9]},{_w_inject(a)},{_TF[a[1]]},{_TF[a[4]]}>"],
+}
+# every __global__ instantiation of track.hip's moments, chanhist.hip, chancov.hip, changrad.hip, changroup.hip and actreg.hip
+CHANSTAT_NAMES = ({f"{k}_partial_kernel<{w},{_TF[x]}>" for k in ("moments", "chanhist", "changroup", "actreg") for w in (1, 4) for x in (0, 1)}
+                  | {f"chancov_partial_kernel<{_TF[v]},{_TF[x]}>" for v in (0, 1) for x in (0, 1)}
+                  | {f"changrad_partial_kernel<{w},{_TF[x]},{_TF[g]}>" for w in (1, 4) for x in (0, 1) for g in (0, 1)}
+                  | {f"actreg_inject_kernel<{k},{w},{_TF[x]},{_TF[g]}>" for k in (0, 1) for w in (1, 4) for x in (0, 1) for g in (0, 1)}
+                  | {k + "_kernel" for k in ("moments_channel", "moments_total", "chanhist_final", "chancov_final", "changrad_final", "changroup_final", "actreg_final")})
+BF, F32 = torch.bfloat16, torch.float32
+
+
+def _chanstat_operands(dev, Cc, B, H, W, layout, dt, seed):
+    import chanhist_refs as HR
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    x = HR.frame_layout((torch.randn((B, H, W, Cc), generator=g) * 1.3 + 0.4).to(dev).to(dt), layout)
+    sc, sh = HR.stats_rows(B, x.stride(2), seed + 1)
+    return x, ops.Stats(None, None, sc.to(dev), sh.to(dev))
+
+
+def chanstat_small(dev):
+    """-> [(id, fn)]: fn() is one call of an ops entry point of the family: FRAME_CASES x storage x transform (both kinds for
+    actreg, the four storage pairs for changrad and actreg_inject)"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import chanhist_refs as HR
+    cases = []
+    for Cc, B, H, W, layout in HR.FRAME_CASES:
+        tag = f"C{Cc}/{B}x{H}x{W}/{layout}"
+        for dt in (F32, BF):
+            x, st = _chanstat_operands(dev, Cc, B, H, W, layout, dt, Cc * 131 + B)
+            sd = str(dt)[6:]
+            for xf in ((0,) if layout == "offset" else (0, ops.XF_AFFINE, ops.XF_AFFINE_SILU)):
+                for name in ("moments", "chanhist", "changroup", "chancov"):
+                    cases.append((f"{name}/{tag}/{sd}/xf{xf}", functools.partial(getattr(ops, name), x, st if xf else None, xf)))
+            for kind, thr in (("ceiling", 0.5), ("floor", 0.3)):
+                cases.append((f"actreg_stats/{kind}/{tag}/{sd}", functools.partial(ops.actreg_stats, x, kind, thr, 1.0)))
+            for dg in (F32, BF):
+                gr = _chanstat_operands(dev, Cc, B, H, W, layout if dg == dt else "plain", dg, Cc * 17 + B)[0]
+                cases.append((f"changrad/{tag}/a{sd}/g{str(dg)[6:]}", functools.partial(ops.changrad, x, gr)))
+                coef = torch.linspace(-0.5, 0.5, Cc, device=dev)
+                for kind, thr in (("ceiling", 0.5), ("floor", 0.3)):
+                    cases.append((f"actreg_inject/{kind}/{tag}/a{sd}/g{str(dg)[6:]}", functools.partial(ops.actreg_inject, x, gr, kind, thr, coef)))
+    return cases
+
+
+def chanstat_timed(dev):
+    """-> [(id, setup)]: one ops call per launch on a ring of operands at the widest GroupNorm of the 256^2 step and at its
+    narrowest tensor (the decoder's 3-channel output as the prefix view of a 4-channel buffer); an ops call allocates its
+    workspace and results from the caching allocator, which every arm does alike"""
+    cases = []
+    for (B, H, W, Cc, view), dt in itertools.product(((16, 256, 256, 128, False), (16, 32, 32, 512, False), (16, 256, 256, 3, True)), (F32, BF)):
+        tag = f"{B}x{H}x{W}x{Cc}/{'bf16' if dt == BF else 'f32'}"
+        ring = max(2, -(-RING_BYTES // (B * H * W * (Cc + view) * (2 if dt == BF else 4))))
+
+        def setup(name, ring=ring, B=B, H=H, W=W, Cc=Cc, view=view, dt=dt):
+            g = torch.Generator(device=dev).manual_seed(Cc + H)
+            xs = [(torch.randn((B, H, W, Cc + view), device=dev, generator=g) * 1.7 + 0.3).to(dt)[..., :Cc] for _ in range(ring)]
+            sc, sh = torch.rand((B, Cc + view), device=dev, generator=g) + 0.5, torch.randn((B, Cc + view), device=dev, generator=g) * 0.2
+            st = ops.Stats(None, None, sc, sh)
+            if name in ("moments", "chanhist", "changroup", "chancov"):
+                return ring, lambda i: getattr(ops, name)(xs[i], st, ops.XF_AFFINE_SILU)
+            if name == "actreg_stats":
+                return ring, lambda i: ops.actreg_stats(xs[i], "ceiling", 0.5, 1.0)
+            gs = [torch.randn((B, H, W, Cc), device=dev, generator=g).to(dt) for _ in range(2)]
+            if name == "changrad":
+                return ring, lambda i: ops.changrad(xs[i], gs[i % 2])
+            coef = torch.linspace(-0.5, 0.5, Cc, device=dev)
+            return ring, lambda i: ops.actreg_inject(xs[i], gs[i % 2], "ceiling", 0.5, coef)
+        for name in ("moments", "chanhist", "changroup", "chancov", "actreg_stats", "changrad", "actreg_inject"):
+            if name == "chancov" and Cc == 512 and dt == BF:
+                continue  # (ten tile pairs: the family's slowest case; fp32 storage times the same kernel body)
+            cases.append((f"{name}/{tag}", functools.partial(setup, name)))
+    return cases
+
+
+def _stream_run(fn, dll, record, kernels=STREAM_KERNELS):
     """one run of fn on library dll -> the tensors it handed to the library, in order; record: set of launched instantiations"""
     seen, order, p0, call0 = set(), [], ops._p, lib.call
 
@@ -717,9 +818,9 @@ def _stream_run(fn, dll, record):
         return p0(t)
 
     def call(name, *a):
-        if name in STREAM_KERNELS:
-            assert len(a) == len(SIGNATURES[name]), (name, len(a))  # (the argument positions STREAM_KERNELS reads are those of this signature)
-            record.update(STREAM_KERNELS[name](a))
+        if name in kernels:
+            assert len(a) == len(SIGNATURES[name]), (name, len(a))  # (the argument positions `kernels` reads are those of this signature)
+            record.update(kernels[name](a))
         return call0(name, *a)
     lib._dll, ops._p, lib.call = dll, p, call
     try:
@@ -731,7 +832,7 @@ def _stream_run(fn, dll, record):
     return order
 
 
-def stream_main(arg, names, paths):
+def stream_main(arg, names, paths, small=stream_small, timed_cases=stream_timed, kernels=STREAM_KERNELS, all_names=STREAM_NAMES):
     dev = torch.device("cuda:0")
     lib.load()
     home, dlls = lib._dll, []
@@ -743,10 +844,10 @@ def stream_main(arg, names, paths):
         dlls.append(d)
     rows, launched, all_equal = [], set(), True
     try:
-        for cid, fn in stream_small(dev):
+        for cid, fn in small(dev):
             first, eq, here = None, {}, set()
             for i, d in enumerate(dlls):
-                got = _stream_run(fn, d, here)
+                got = _stream_run(fn, d, here, kernels)
                 if i == 0:
                     first = got
                 else:
@@ -759,12 +860,12 @@ def stream_main(arg, names, paths):
             del first, got
             torch.cuda.empty_cache()
         timed = []
-        for cid, setup in ([] if arg.launches <= 0 else stream_timed(dev)):
+        for cid, setup in ([] if arg.launches <= 0 else timed_cases(dev)):
             lib._dll = home
             ring, fn = setup()
             here = set()
             for d in dlls:  # warm-up, and the instantiations the case launches
-                _stream_run(lambda: [fn(i) for i in range(min(ring, 2))], d, here)
+                _stream_run(lambda: [fn(i) for i in range(min(ring, 2))], d, here, kernels)
             ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(arg.launches)] for _ in dlls]
             for k in range(arg.launches):
                 for i in ((k + j) % len(dlls) for j in range(len(dlls))):  # (every arm takes every place in the round equally often)
@@ -789,7 +890,7 @@ def stream_main(arg, names, paths):
             torch.cuda.empty_cache()
     finally:
         lib._dll = home
-    missing = sorted(STREAM_NAMES - launched) + sorted("unknown: " + k for k in launched - STREAM_NAMES)
+    missing = sorted(all_names - launched) + sorted("unknown: " + k for k in launched - all_names)
     res = {"libs": dict(zip(names, [os.path.basename(s) for s in paths])), "launches_per_arm": arg.launches, "all_bitwise_equal": all_equal, "rows": rows,
            "timed": timed, "instantiations_not_launched": missing, "all_within_margin": all(r.get("within_margin", True) for r in timed)}
     print("instantiations not launched:", missing)
@@ -805,12 +906,14 @@ def main():
     ap.add_argument("libs", nargs="+", help="NEW.so PARENT.so [name=OTHER.so ...]")
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16", "thin", "stream"])
+    ap.add_argument("--only", default="", choices=["", "wino4", "wino2", "up", "bf16", "thin", "stream", "chanstat"])
     arg = ap.parse_args()
     assert len(arg.libs) >= 2, "two libraries: this build and the parent's"
     names = ["new", "parent"] + [s.split("=", 1)[0] for s in arg.libs[2:]]
     if arg.only == "stream":
         return stream_main(arg, names, [s.split("=", 1)[-1] for s in arg.libs])
+    if arg.only == "chanstat":
+        return stream_main(arg, names, [s.split("=", 1)[-1] for s in arg.libs], chanstat_small, chanstat_timed, CHANSTAT_KERNELS, CHANSTAT_NAMES)
     dlls = [_open(s.split("=", 1)[-1]) for s in arg.libs]
     dev = torch.device("cuda:0")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

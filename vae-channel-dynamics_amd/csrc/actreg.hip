@@ -4,8 +4,8 @@
 //   floor   (threshold t):  P = weight / C * sum_c w_c relu(t - m_c)^2, m_c = mean |a| dP/da = k_c psi(a), psi(a) = sign(a), sign(0) = 0
 // with k_c = 2 weight w_c grad_scale / (N C) for the ceiling and -2 weight w_c relu(t - m_c) grad_scale / (N C) for the floor.
 //
-// Statistics, partial pass: one read of a (fp32 or bf16, pixel stride ld >= C: a channel-prefix view is read in place), built as
-// changrad_partial_kernel: one workgroup per (pixel chunk, image, tile of 256 channels), lanes across channels and pixel rows down
+// Statistics, partial pass: one read of a (fp32 or bf16, pixel stride ld >= C: a channel-prefix view is read in place), on the
+// frame of chanstat_common.h: one workgroup per (pixel chunk, image, tile of 256 channels), lanes across channels and pixel rows down
 // the chunk, four pixel rows in flight per lane.  A lane keeps, per channel, in fp32 the sum of e^2 with e = |a| - t over the
 // elements with !(|a| <= t) (e rounded once, the square rounded once: the library is built with -ffp-contract=off) and the sum of
 // |a|, and the number of such elements as an exact 32-bit count.  A NaN counts as over the threshold and makes both sums of its
@@ -21,7 +21,7 @@
 // once, a bf16 result rounded once more.  An element whose product is zero passes g on as it is, so a zero coefficient (weight
 // 0, a masked channel, a floor that is met) and a ceiling nothing exceeds leave g bit for bit wherever a is finite (0 * inf and
 // 0 * NaN are NaN: a non-finite a makes its own element NaN whatever the coefficient).
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
@@ -29,41 +29,19 @@ constexpr int AR_CT = 256;    // channels of a full tile
 constexpr int AR_WORDS = 3;   // sum e^2, sum |a|, count
 constexpr int AR_CEILING = 0, AR_FLOOR = 1;
 
-// W consecutive channels of one pixel (as changrad.hip, which keeps its own copy: its compiled code stays as it is)
-template <int W, bool XBF>
-__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4) {
-    f32x4 q;
-    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
-    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
-  }
-}
-
 // ws: [C][B * nchunk][AR_WORDS] words
 template <int W, bool ABF>
 __global__ __launch_bounds__(256) void actreg_partial_kernel(const void* __restrict__ a, int HW, int C, int lda, int nchunk, float thr,
                                                              unsigned* __restrict__ ws) {
   __shared__ float red[2][W][256];
   __shared__ unsigned rcnt[W][256];
-  constexpr int UT = AR_CT / W;                  // channel units of a full tile
-  const int nu = C / W;                          // channel units of W channels
-  const int u0 = blockIdx.z * UT;
-  const int nut = min(UT, nu - u0);              // units of this workgroup
-  const Lay l = make_lay_q(nut);
-  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
-  const int c0 = (u0 + l.cq) * W;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
-  const int p0 = cr.p0, p1 = cr.p1;
+  const StatFrame f = stat_frame<AR_CT / W, W>(HW, C, nchunk);
+  const int c0 = f.c0, b = f.b;
   float se[W], sa[W];
   unsigned cnt[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) se[e] = sa[e] = 0.f, cnt[e] = 0u;
-  if (pr < PR) {
+  if (f.pr < f.PR) {
     const int64_t ab = (int64_t)b * HW * lda + c0;
     auto take = [&](const float (&va)[W]) {
 #pragma unroll
@@ -78,20 +56,7 @@ __global__ __launch_bounds__(256) void actreg_partial_kernel(const void* __restr
         }
       }
     };
-    int pix = p0 + pr;
-    // four pixel rows in flight per lane, then the same per-element order as the single-row tail
-    for (; pix + 3 * PR < p1; pix += 4 * PR) {
-      float va[4][W];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) load_units<W, ABF>(a, ab + (int64_t)(pix + k * PR) * lda, va[k]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) take(va[k]);
-    }
-    for (; pix < p1; pix += PR) {
-      float va[W];
-      load_units<W, ABF>(a, ab + (int64_t)pix * lda, va);
-      take(va);
-    }
+    for_rows<W, ABF>(a, ab, lda, f, take);
   }
 #pragma unroll
   for (int e = 0; e < W; ++e) {
@@ -100,19 +65,18 @@ __global__ __launch_bounds__(256) void actreg_partial_kernel(const void* __restr
     rcnt[e][threadIdx.x] = cnt[e];
   }
   __syncthreads();
-  if ((int)threadIdx.x < nut) {  // pr == 0: c0 is this thread's first channel
+  if ((int)threadIdx.x < f.nut) {  // pr == 0: c0 is this thread's first channel
     const int64_t rows = (int64_t)gridDim.y * nchunk;
-    const int64_t row = (int64_t)b * nchunk + chunk;
+    const int64_t row = (int64_t)b * nchunk + f.chunk;
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       float te = 0.f, ta = 0.f;
       unsigned tc = 0u;
-      for (int r = 0; r < PR; ++r) {
-        const int i = r * nut + threadIdx.x;
+      fold_rows(f, [&](int i) {
         te += red[0][e][i];
         ta += red[1][e][i];
         tc += rcnt[e][i];
-      }
+      });
       unsigned* dst = ws + ((int64_t)(c0 + e) * rows + row) * AR_WORDS;
       dst[0] = __builtin_bit_cast(unsigned, te);
       dst[1] = __builtin_bit_cast(unsigned, ta);
@@ -253,18 +217,6 @@ __global__ __launch_bounds__(256) void actreg_inject_kernel(const void* __restri
   }
 }
 
-// what the statistics passes (and the size query) ask of a shape
-int check_shape(const char* who, int32_t B, int32_t HW, int32_t C, int32_t nchunk) {
-  VAE_CHECK(B > 0 && HW > 0 && C > 0 && nchunk > 0, "%s: bad args (B=%d HW=%d C=%d nchunk=%d)", who, B, HW, C, nchunk);
-  VAE_CHECK((int64_t)B * HW < ((int64_t)1 << 31), "%s: B * HW = %lld: 2^31 elements per channel or more", who,
-            (long long)((int64_t)B * HW));
-  const int per = (HW + nchunk - 1) / nchunk;
-  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
-            "%s: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", who, nchunk, HW);
-  VAE_CHECK((int64_t)B * nchunk < ((int64_t)1 << 31), "%s: B * nchunk = %lld rows per channel", who, (long long)((int64_t)B * nchunk));
-  return VAE_OK;
-}
-
 int check_kind(const char* who, int32_t kind, double threshold) {
   VAE_CHECK(kind == AR_CEILING || kind == AR_FLOOR, "%s: kind=%d (0 = ceiling, 1 = floor)", who, kind);
   VAE_CHECK(threshold > 0.0 && threshold <= 3.0e38, "%s: threshold %g is not a finite positive number", who, threshold);
@@ -275,7 +227,7 @@ int check_kind(const char* who, int32_t kind, double threshold) {
 
 extern "C" int vae_actreg_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords) {
   VAE_CHECK(nwords, "actreg_workspace: null args");
-  if (int rc = check_shape("actreg_workspace", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("actreg_workspace", B, HW, C, nchunk)) return rc;
   *nwords = (int64_t)B * nchunk * C * AR_WORDS;
   return VAE_OK;
 }
@@ -283,12 +235,11 @@ extern "C" int vae_actreg_workspace(int32_t B, int32_t HW, int32_t C, int32_t nc
 extern "C" int vae_actreg_partial(const void* a, int32_t a_bf16, int32_t lda, int32_t B, int32_t HW, int32_t C, int32_t nchunk,
                                   float threshold, uint32_t* ws, void* stream) {
   VAE_CHECK(a && ws, "actreg_partial: null args");
-  if (int rc = check_shape("actreg_partial", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("actreg_partial", B, HW, C, nchunk)) return rc;
   VAE_CHECK(threshold > 0.f && threshold <= 3.0e38f, "actreg_partial: threshold %g is not a finite positive number", (double)threshold);
   VAE_CHECK(lda >= C, "actreg_partial: pixel stride lda=%d below C=%d", lda, C);
   VAE_CHECK(aligned16(ws), "actreg_partial: unaligned workspace");
-  // four channels per lane where the rows allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
-  const bool vec = C % 4 == 0 && lda % 4 == 0 && (((uintptr_t)a) & (a_bf16 ? 7u : 15u)) == 0;
+  const bool vec = vec4_ok(a, a_bf16, C, lda);
   const int tiles = (C + AR_CT - 1) / AR_CT;  // C / W units in tiles of AR_CT / W
   VAE_CHECK(tiles <= 65535, "actreg_partial: C=%d: too many channel tiles", C);
   const dim3 grid(nchunk, B, tiles);
@@ -307,7 +258,7 @@ extern "C" int vae_actreg_final(const uint32_t* ws, int32_t B, int32_t HW, int32
                                 double weight, const float* mask, double grad_scale, double* sums, double* pen, float* coef,
                                 void* stream) {
   VAE_CHECK(ws && sums && pen && coef, "actreg_final: null args");
-  if (int rc = check_shape("actreg_final", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("actreg_final", B, HW, C, nchunk)) return rc;
   if (int rc = check_kind("actreg_final", kind, threshold)) return rc;
   VAE_CHECK(weight >= 0.0 && weight <= 1.0e300, "actreg_final: weight %g is not a finite number >= 0", weight);
   VAE_CHECK(grad_scale == grad_scale && grad_scale >= -1.0e300 && grad_scale <= 1.0e300, "actreg_final: grad_scale %g is not finite",
@@ -327,9 +278,8 @@ extern "C" int vae_actreg_inject(const void* a, int32_t a_bf16, int32_t lda, con
   if (int rc = check_kind("actreg_inject", kind, (double)threshold)) return rc;
   VAE_CHECK(lda >= C && ldg >= C, "actreg_inject: pixel stride lda=%d or ldg=%d below C=%d", lda, ldg, C);
   VAE_CHECK(out != a && out != g, "actreg_inject: out of place only");
-  const uintptr_t amask = a_bf16 ? 7u : 15u, gmask = g_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && lda % 4 == 0 && ldg % 4 == 0 && (((uintptr_t)a) & amask) == 0 && (((uintptr_t)g) & gmask) == 0 &&
-                   (((uintptr_t)out) & gmask) == 0 && aligned16(coef);
+  // (out is contiguous: its pixel stride is C)
+  const bool vec = vec4_ok(a, a_bf16, C, lda) && vec4_ok(g, g_bf16, C, ldg) && vec4_ok(out, g_bf16, C, C) && aligned16(coef);
   const int nu = vec ? C / 4 : C;
   const dim3 grid(ew_blocks(rows * nu));
   hipStream_t s = (hipStream_t)stream;

@@ -21,7 +21,7 @@
 //               K  [tiles][128]
 // Final pass: sums S and d over the B * nchunk rows in float64 in a fixed order (16 row lanes, then 0..15) and writes
 // cov = (S - d d^T / N) / (N - 1) (upper triangle computed, mirrored: bitwise symmetric) and mean = K + d / N.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
@@ -249,15 +249,10 @@ __global__ __launch_bounds__(FIN_W * FIN_R) void chancov_final_kernel(const floa
   }
 }
 
-// what both passes (and the size query) ask of a shape
+// what both passes (and the size query) ask of a shape: the family's checks and two of its own
 int check_shape(const char* who, int32_t B, int32_t HW, int32_t C, int32_t nchunk) {
-  VAE_CHECK(B > 0 && HW > 0 && C > 0 && nchunk > 0, "%s: bad args (B=%d HW=%d C=%d nchunk=%d)", who, B, HW, C, nchunk);
-  VAE_CHECK((int64_t)B * HW < ((int64_t)1 << 31), "%s: B * HW = %lld: 2^31 elements per channel or more", who,
-            (long long)((int64_t)B * HW));
+  if (int rc = stat_check_shape(who, B, HW, C, nchunk)) return rc;
   VAE_CHECK((int64_t)B * HW >= 2, "%s: B * HW = %lld: a covariance needs two rows", who, (long long)((int64_t)B * HW));
-  const int per = (HW + nchunk - 1) / nchunk;
-  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
-            "%s: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", who, nchunk, HW);
   const int64_t tiles = ((int64_t)C + CC_T - 1) / CC_T;
   VAE_CHECK(tiles * (tiles + 1) / 2 <= 65535, "%s: C=%d: too many channel tile pairs", who, C);
   return VAE_OK;
@@ -278,13 +273,9 @@ extern "C" int vae_chancov_partial(const void* x, int32_t x_bf16, const float* s
                                    int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float* ws, void* stream) {
   VAE_CHECK(x && ws, "chancov_partial: null args");
   if (int rc = check_shape("chancov_partial", B, HW, C, nchunk)) return rc;
-  VAE_CHECK(ld >= C, "chancov_partial: pixel stride ld=%d below C=%d", ld, C);
-  VAE_CHECK(xf == VAE_XF_NONE || xf == VAE_XF_AFFINE || xf == VAE_XF_AFFINE_SILU, "chancov_partial: xf=%d", xf);
-  VAE_CHECK(xf == VAE_XF_NONE || (scale && shift), "chancov_partial: xf needs scale and shift");
+  if (int rc = stat_check_xf("chancov_partial", xf, scale, shift, ld, C)) return rc;
   VAE_CHECK(aligned16(ws), "chancov_partial: unaligned workspace");
-  // four channels per load where the rows allow a 16 B (fp32) / 8 B (bf16) load, single elements otherwise
-  const uintptr_t amask = x_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & amask) == 0;
+  const bool vec = vec4_ok(x, x_bf16, C, ld);  // (single elements otherwise)
   const int tiles = (C + CC_T - 1) / CC_T;
   const dim3 grid(nchunk, B, tiles * (tiles + 1) / 2);
   hipStream_t s = (hipStream_t)stream;
@@ -302,7 +293,6 @@ extern "C" int vae_chancov_final(const float* ws, int32_t B, int32_t HW, int32_t
                                  void* stream) {
   VAE_CHECK(ws && cov && mean, "chancov_final: null args");
   if (int rc = check_shape("chancov_final", B, HW, C, nchunk)) return rc;
-  VAE_CHECK((int64_t)B * nchunk <= 0x7fffffff, "chancov_final: B * nchunk = %lld rows", (long long)((int64_t)B * nchunk));
   VAE_CHECK(aligned16(ws), "chancov_final: unaligned workspace");
   const int tiles = (C + CC_T - 1) / CC_T;
   hipStream_t s = (hipStream_t)stream;

@@ -15,26 +15,12 @@
 // largest power of two <= min(256, nchunk)): a chunk lane adds its chunks of an image in order, an LDS tree over the chunk
 // lanes gives the image's P[b] = sum a g and its sum |g|; the image lane adds P, |P| and sum |g| over its images in order, and
 // a last LDS tree over all threads gives the channel's values.  No atomics anywhere: repeated launches are bitwise identical.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
 constexpr int CG_CT = 256;  // channels of a full tile
 constexpr int CG_WORDS = 3;  // sum |g|, sum a g, max |g| bits
-
-// W consecutive channels of one pixel (as track.hip and chanhist.hip, which keep their own copies: their compiled code stays as it is)
-template <int W, bool XBF>
-__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4) {
-    f32x4 q;
-    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
-    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
-  }
-}
 
 // ws: [C][B * nchunk][CG_WORDS] words
 template <int W, bool ABF, bool GBF>
@@ -42,21 +28,13 @@ __global__ __launch_bounds__(256) void changrad_partial_kernel(const void* __res
                                                                int lda, int ldg, int nchunk, unsigned* __restrict__ ws) {
   __shared__ float red[2][W][256];
   __shared__ unsigned rmax[W][256];
-  constexpr int UT = CG_CT / W;                  // channel units of a full tile
-  const int nu = C / W;                          // channel units of W channels
-  const int u0 = blockIdx.z * UT;
-  const int nut = min(UT, nu - u0);              // units of this workgroup
-  const Lay l = make_lay_q(nut);
-  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
-  const int c0 = (u0 + l.cq) * W;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
-  const int p0 = cr.p0, p1 = cr.p1;
+  const StatFrame f = stat_frame<CG_CT / W, W>(HW, C, nchunk);
+  const int c0 = f.c0, b = f.b;
   float sg[W], sp[W];
   unsigned amax[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) sg[e] = sp[e] = 0.f, amax[e] = 0u;
-  if (pr < PR) {
+  if (f.pr < f.PR) {
     const int64_t ab = (int64_t)b * HW * lda + c0;
     const int64_t gb = (int64_t)b * HW * ldg + c0;
     auto take = [&](const float (&va)[W], const float (&vg)[W]) {
@@ -69,8 +47,9 @@ __global__ __launch_bounds__(256) void changrad_partial_kernel(const void* __res
         sp[e] += prod;
       }
     };
-    int pix = p0 + pr;
-    // four pixel rows of both streams in flight per lane, then the same per-element order as the single-row tail
+    const int PR = f.PR, p1 = f.p1;
+    int pix = f.p0 + f.pr;
+    // four pixel rows of both streams in flight per lane, then the single-row tail: the order of for_rows (chanstat_common.h)
     for (; pix + 3 * PR < p1; pix += 4 * PR) {
       float va[4][W], vg[4][W];
 #pragma unroll
@@ -95,19 +74,18 @@ __global__ __launch_bounds__(256) void changrad_partial_kernel(const void* __res
     rmax[e][threadIdx.x] = amax[e];
   }
   __syncthreads();
-  if ((int)threadIdx.x < nut) {  // pr == 0: c0 is this thread's first channel
+  if ((int)threadIdx.x < f.nut) {  // pr == 0: c0 is this thread's first channel
     const int64_t rows = (int64_t)gridDim.y * nchunk;
-    const int64_t row = (int64_t)b * nchunk + chunk;
+    const int64_t row = (int64_t)b * nchunk + f.chunk;
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       float tg = 0.f, tp = 0.f;
       unsigned tm = 0u;
-      for (int r = 0; r < PR; ++r) {
-        const int i = r * nut + threadIdx.x;
+      fold_rows(f, [&](int i) {
         tg += red[0][e][i];
         tp += red[1][e][i];
         tm = max(tm, rmax[e][i]);
-      }
+      });
       unsigned* dst = ws + ((int64_t)(c0 + e) * rows + row) * CG_WORDS;
       dst[0] = __builtin_bit_cast(unsigned, tg);
       dst[1] = __builtin_bit_cast(unsigned, tp);
@@ -175,26 +153,15 @@ __global__ __launch_bounds__(256) void changrad_final_kernel(const unsigned* __r
     sums[(int64_t)C + c] = sh[1][0];
     sums[2 * (int64_t)C + c] = sh[2][0] / nb;
     const unsigned mx = shm[0];
-    absmax[c] = mx > 0x7f800000u ? __builtin_bit_cast(float, 0x7fc00000u) : __builtin_bit_cast(float, mx);
+    absmax[c] = absmax_of(mx);
   }
-}
-
-// what both passes (and the size query) ask of a shape
-int check_shape(const char* who, int32_t B, int32_t HW, int32_t C, int32_t nchunk) {
-  VAE_CHECK(B > 0 && HW > 0 && C > 0 && nchunk > 0, "%s: bad args (B=%d HW=%d C=%d nchunk=%d)", who, B, HW, C, nchunk);
-  VAE_CHECK((int64_t)B * HW < ((int64_t)1 << 31), "%s: B * HW = %lld: 2^31 elements per channel or more", who,
-            (long long)((int64_t)B * HW));
-  const int per = (HW + nchunk - 1) / nchunk;
-  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
-            "%s: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", who, nchunk, HW);
-  return VAE_OK;
 }
 
 }  // namespace
 
 extern "C" int vae_changrad_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords) {
   VAE_CHECK(nwords, "changrad_workspace: null args");
-  if (int rc = check_shape("changrad_workspace", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("changrad_workspace", B, HW, C, nchunk)) return rc;
   *nwords = (int64_t)B * nchunk * C * CG_WORDS;
   return VAE_OK;
 }
@@ -202,12 +169,10 @@ extern "C" int vae_changrad_workspace(int32_t B, int32_t HW, int32_t C, int32_t 
 extern "C" int vae_changrad_partial(const void* a, int32_t a_bf16, int32_t lda, const void* g, int32_t g_bf16, int32_t ldg, int32_t B,
                                     int32_t HW, int32_t C, int32_t nchunk, uint32_t* ws, void* stream) {
   VAE_CHECK(a && g && ws, "changrad_partial: null args");
-  if (int rc = check_shape("changrad_partial", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("changrad_partial", B, HW, C, nchunk)) return rc;
   VAE_CHECK(lda >= C && ldg >= C, "changrad_partial: pixel stride lda=%d or ldg=%d below C=%d", lda, ldg, C);
   VAE_CHECK(aligned16(ws), "changrad_partial: unaligned workspace");
-  // four channels per lane where the rows of both operands allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
-  const uintptr_t amask = a_bf16 ? 7u : 15u, gmask = g_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && lda % 4 == 0 && ldg % 4 == 0 && (((uintptr_t)a) & amask) == 0 && (((uintptr_t)g) & gmask) == 0;
+  const bool vec = vec4_ok(a, a_bf16, C, lda) && vec4_ok(g, g_bf16, C, ldg);
   const int tiles = (C + CG_CT - 1) / CG_CT;  // C / W units in tiles of CG_CT / W
   VAE_CHECK(tiles <= 65535, "changrad_partial: C=%d: too many channel tiles", C);
   const dim3 grid(nchunk, B, tiles);
@@ -227,7 +192,7 @@ extern "C" int vae_changrad_partial(const void* a, int32_t a_bf16, int32_t lda, 
 extern "C" int vae_changrad_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* sums, float* absmax,
                                   void* stream) {
   VAE_CHECK(ws && sums && absmax, "changrad_final: null args");
-  if (int rc = check_shape("changrad_final", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("changrad_final", B, HW, C, nchunk)) return rc;
   VAE_CHECK(aligned16(ws), "changrad_final: unaligned workspace");
   int CL = 1;
   while (CL * 2 <= nchunk && CL < 256) CL *= 2;

@@ -3,7 +3,7 @@
 // NHWC activation: the inputs of vae_moments_partial (fp32 or bf16 storage, any pixel stride ld >= C, the optional runtime
 // GroupNorm(+SiLU) transform applied on the fly).  Nothing here reduces over the batch: that is what the metrics are about.
 //
-// Partial pass: built as actreg_partial_kernel: one workgroup per (pixel chunk, image, tile of 256 channels), lanes across
+// Partial pass: on the frame of chanstat_common.h: one workgroup per (pixel chunk, image, tile of 256 channels), lanes across
 // channels and pixel rows down the chunk, four pixel rows in flight per lane.  y is evaluated in fp32 (exactly the stored value
 // without a transform) and widened; a lane keeps its three sums per channel in FLOAT64: the square of an fp32 value is exact in
 // float64, so the only roundings are those of the additions, 2^-53 each.  The group metrics subtract n mu^2 from sum y^2, which
@@ -14,26 +14,12 @@
 //
 // Final pass: one thread per (image, channel, sum) adds the nchunk partials of its word in chunk order.  No atomics anywhere,
 // no zero-fill: repeated launches are bitwise identical.  A NaN or an infinity reaches the sums of its own (b, c) only.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
 constexpr int CG_CT = 256;   // channels of a full tile
 constexpr int CG_WORDS = 3;  // sum y, sum y^2, sum |y|
-
-// W consecutive channels of one pixel (as actreg.hip, which keeps its own copy: its compiled code stays as it is)
-template <int W, bool XBF>
-__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4) {
-    f32x4 q;
-    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
-    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
-  }
-}
 
 // ws: [B * nchunk][C][CG_WORDS] doubles
 template <int W, bool XBF>
@@ -41,20 +27,12 @@ __global__ __launch_bounds__(256) void changroup_partial_kernel(const void* __re
                                                                 const float* __restrict__ shift, int xf, int HW, int C, int ld,
                                                                 int nchunk, double* __restrict__ ws) {
   __shared__ double red[CG_WORDS][W][256];
-  constexpr int UT = CG_CT / W;                  // channel units of a full tile
-  const int nu = C / W;                          // channel units of W channels
-  const int u0 = blockIdx.z * UT;
-  const int nut = min(UT, nu - u0);              // units of this workgroup
-  const Lay l = make_lay_q(nut);
-  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
-  const int c0 = (u0 + l.cq) * W;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
-  const int p0 = cr.p0, p1 = cr.p1;
+  const StatFrame f = stat_frame<CG_CT / W, W>(HW, C, nchunk);
+  const int c0 = f.c0, b = f.b;
   double s1[W], s2[W], sa[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) s1[e] = s2[e] = sa[e] = 0.0;
-  if (pr < PR) {
+  if (f.pr < f.PR) {
     float sc[W], sh[W];
 #pragma unroll
     for (int e = 0; e < W; ++e) {
@@ -73,20 +51,7 @@ __global__ __launch_bounds__(256) void changroup_partial_kernel(const void* __re
         sa[e] += __builtin_fabs(d);
       }
     };
-    int pix = p0 + pr;
-    // four pixel rows in flight per lane, then the same per-element order as the single-row tail
-    for (; pix + 3 * PR < p1; pix += 4 * PR) {
-      float v[4][W];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) load_units<W, XBF>(x, xb + (int64_t)(pix + k * PR) * ld, v[k]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) take(v[k]);
-    }
-    for (; pix < p1; pix += PR) {
-      float v[W];
-      load_units<W, XBF>(x, xb + (int64_t)pix * ld, v);
-      take(v);
-    }
+    for_rows<W, XBF>(x, xb, ld, f, take);
   }
 #pragma unroll
   for (int e = 0; e < W; ++e) {
@@ -95,17 +60,16 @@ __global__ __launch_bounds__(256) void changroup_partial_kernel(const void* __re
     red[2][e][threadIdx.x] = sa[e];
   }
   __syncthreads();
-  if ((int)threadIdx.x < nut) {  // pr == 0: c0 is this thread's first channel
-    const int64_t row = (int64_t)b * nchunk + chunk;
+  if ((int)threadIdx.x < f.nut) {  // pr == 0: c0 is this thread's first channel
+    const int64_t row = (int64_t)b * nchunk + f.chunk;
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       double t1 = 0.0, t2 = 0.0, ta = 0.0;
-      for (int r = 0; r < PR; ++r) {
-        const int i = r * nut + threadIdx.x;
+      fold_rows(f, [&](int i) {
         t1 += red[0][e][i];
         t2 += red[1][e][i];
         ta += red[2][e][i];
-      }
+      });
       double* dst = ws + (row * C + (c0 + e)) * CG_WORDS;
       dst[0] = t1;
       dst[1] = t2;
@@ -135,23 +99,11 @@ __global__ __launch_bounds__(256) void changroup_final_kernel(const double* __re
   sums[(int64_t)b * nw + w] = acc;
 }
 
-// what both passes (and the size query) ask of a shape
-int check_shape(const char* who, int32_t B, int32_t HW, int32_t C, int32_t nchunk) {
-  VAE_CHECK(B > 0 && HW > 0 && C > 0 && nchunk > 0, "%s: bad args (B=%d HW=%d C=%d nchunk=%d)", who, B, HW, C, nchunk);
-  VAE_CHECK((int64_t)B * HW < ((int64_t)1 << 31), "%s: B * HW = %lld: 2^31 elements per channel or more", who,
-            (long long)((int64_t)B * HW));
-  const int per = (HW + nchunk - 1) / nchunk;
-  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
-            "%s: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", who, nchunk, HW);
-  VAE_CHECK((int64_t)B * nchunk < ((int64_t)1 << 31), "%s: B * nchunk = %lld rows", who, (long long)((int64_t)B * nchunk));
-  return VAE_OK;
-}
-
 }  // namespace
 
 extern "C" int vae_changroup_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* ndoubles) {
   VAE_CHECK(ndoubles, "changroup_workspace: null args");
-  if (int rc = check_shape("changroup_workspace", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("changroup_workspace", B, HW, C, nchunk)) return rc;
   *ndoubles = (int64_t)B * nchunk * C * CG_WORDS;
   return VAE_OK;
 }
@@ -159,14 +111,10 @@ extern "C" int vae_changroup_workspace(int32_t B, int32_t HW, int32_t C, int32_t
 extern "C" int vae_changroup_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
                                      int32_t HW, int32_t C, int32_t ld, int32_t nchunk, double* ws, void* stream) {
   VAE_CHECK(x && ws, "changroup_partial: null args");
-  if (int rc = check_shape("changroup_partial", B, HW, C, nchunk)) return rc;
-  VAE_CHECK(ld >= C, "changroup_partial: pixel stride ld=%d below C=%d", ld, C);
-  VAE_CHECK(xf == VAE_XF_NONE || xf == VAE_XF_AFFINE || xf == VAE_XF_AFFINE_SILU, "changroup_partial: xf=%d", xf);
-  VAE_CHECK(xf == VAE_XF_NONE || (scale && shift), "changroup_partial: xf needs scale and shift");
+  if (int rc = stat_check_shape("changroup_partial", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_xf("changroup_partial", xf, scale, shift, ld, C)) return rc;
   VAE_CHECK(aligned16(ws), "changroup_partial: unaligned workspace");
-  // four channels per lane where the rows allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
-  const uintptr_t amask = x_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & amask) == 0;
+  const bool vec = vec4_ok(x, x_bf16, C, ld);
   const int tiles = (C + CG_CT - 1) / CG_CT;  // C / W units in tiles of CG_CT / W
   VAE_CHECK(tiles <= 65535, "changroup_partial: C=%d: too many channel tiles", C);
   const dim3 grid(nchunk, B, tiles);
@@ -183,7 +131,7 @@ extern "C" int vae_changroup_partial(const void* x, int32_t x_bf16, const float*
 
 extern "C" int vae_changroup_final(const double* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, double* sums, void* stream) {
   VAE_CHECK(ws && sums, "changroup_final: null args");
-  if (int rc = check_shape("changroup_final", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("changroup_final", B, HW, C, nchunk)) return rc;
   VAE_CHECK(aligned16(ws), "changroup_final: unaligned workspace");
   const int64_t nw = (int64_t)C * CG_WORDS;
   const int64_t blocks = (nw + 255) / 256;

@@ -18,7 +18,7 @@
 //
 // Across workgroups nothing is atomic: each workgroup stores its 50 words per channel to ws [B * nchunk][C][50] with plain
 // stores, and the final pass sums (row 49: maximises) them per word.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
@@ -26,20 +26,6 @@ constexpr int CH_BINS = 48;
 constexpr int CH_ROWS = CH_BINS + 2;  // bins, near-zero count, max |y| bits
 constexpr int CH_NZ = CH_BINS, CH_MAX = CH_BINS + 1;
 constexpr int CH_CT = 128;            // counter columns of a workgroup's table = channels of a full tile
-
-// W consecutive channels of one pixel (as track.hip, which keeps its own copy: its compiled code stays as it is)
-template <int W, bool XBF>
-__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4) {
-    f32x4 q;
-    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
-    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
-  }
-}
 
 __device__ __forceinline__ int bin_of(unsigned a /* bits of |y| */) { return min(max((int)(a >> 23) - 96, 0), CH_BINS - 1); }
 
@@ -50,21 +36,14 @@ __global__ __launch_bounds__(256) void chanhist_partial_kernel(const void* __res
                                                                int nchunk, float tau, unsigned* __restrict__ ws) {
   __shared__ __attribute__((aligned(16))) unsigned tab[CH_ROWS][CH_CT];
   constexpr int UT = CH_CT / W;                  // channel units of a full tile
-  const int nu = C / W;                          // channel units of W channels
-  const int u0 = blockIdx.z * UT;
-  const int nut = min(UT, nu - u0);              // units of this workgroup
-  const Lay l = make_lay_q(nut);
-  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
-  const int R = min(PR, UT / nut);               // private copies of each channel's counters
+  const StatFrame f = stat_frame<UT, W>(HW, C, nchunk);
+  const int nut = f.nut, c0 = f.c0, b = f.b;
+  const int R = min(f.PR, UT / nut);             // private copies of each channel's counters
   const int QR = nut * R;
   const int col = threadIdx.x % QR;              // (pr % R) * nut + cq
-  const int c0 = (u0 + l.cq) * W;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
-  const int p0 = cr.p0, p1 = cr.p1;
   for (int i = threadIdx.x; i < CH_ROWS * CH_CT / 4; i += 256) reinterpret_cast<uint4*>(&tab[0][0])[i] = uint4{0u, 0u, 0u, 0u};
   __syncthreads();
-  if (pr < PR) {
+  if (f.pr < f.PR) {
     float sc[W], sh[W];
 #pragma unroll
     for (int e = 0; e < W; ++e) {
@@ -85,20 +64,7 @@ __global__ __launch_bounds__(256) void chanhist_partial_kernel(const void* __res
         atomicAdd(&tab[bin_of(a)][e * QR + col], 1u);
       }
     };
-    int pix = p0 + pr;
-    // four loads in flight per lane
-    for (; pix + 3 * PR < p1; pix += 4 * PR) {
-      float v[4][W];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) load_units<W, XBF>(x, xb + (int64_t)(pix + k * PR) * ld, v[k]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) count(v[k]);
-    }
-    for (; pix < p1; pix += PR) {
-      float v[W];
-      load_units<W, XBF>(x, xb + (int64_t)pix * ld, v);
-      count(v);
-    }
+    for_rows<W, XBF>(x, xb, ld, f, count);
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       atomicAdd(&tab[CH_NZ][e * QR + col], nz[e]);
@@ -107,8 +73,8 @@ __global__ __launch_bounds__(256) void chanhist_partial_kernel(const void* __res
   }
   __syncthreads();
   // the tile's channels are consecutive in ws: word w = (local channel, row), the private copies folded on the way out
-  const int64_t row = (int64_t)b * nchunk + chunk;
-  unsigned* dst = ws + (row * C + (int64_t)u0 * W) * CH_ROWS;
+  const int64_t row = (int64_t)b * nchunk + f.chunk;
+  unsigned* dst = ws + (row * C + (int64_t)f.u0 * W) * CH_ROWS;
   for (int w = threadIdx.x; w < nut * W * CH_ROWS; w += 256) {
     const int cl = w / CH_ROWS, j = w - cl * CH_ROWS;
     const int base = (cl % W) * QR + cl / W;
@@ -165,19 +131,8 @@ __global__ __launch_bounds__(FIN_W * FIN_R) void chanhist_final_kernel(const uns
     const int c = (int)(w / CH_ROWS), j = (int)(w - (int64_t)c * CH_ROWS);
     if (j < CH_BINS) hist[(int64_t)c * CH_BINS + j] = (int64_t)sum;
     else if (j == CH_NZ) nzero[c] = (int64_t)sum;
-    else absmax[c] = mx > 0x7f800000u ? __builtin_bit_cast(float, 0x7fc00000u) : __builtin_bit_cast(float, mx);
+    else absmax[c] = absmax_of(mx);
   }
-}
-
-// what both passes (and the size query) ask of a shape
-int check_shape(const char* who, int32_t B, int32_t HW, int32_t C, int32_t nchunk) {
-  VAE_CHECK(B > 0 && HW > 0 && C > 0 && nchunk > 0, "%s: bad args (B=%d HW=%d C=%d nchunk=%d)", who, B, HW, C, nchunk);
-  VAE_CHECK((int64_t)B * HW < ((int64_t)1 << 31), "%s: B * HW = %lld: 2^31 elements per channel or more", who,
-            (long long)((int64_t)B * HW));
-  const int per = (HW + nchunk - 1) / nchunk;
-  VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
-            "%s: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", who, nchunk, HW);
-  return VAE_OK;
 }
 
 }  // namespace
@@ -186,7 +141,7 @@ extern "C" int vae_chanhist_bins(void) { return CH_BINS; }
 
 extern "C" int vae_chanhist_workspace(int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* nwords) {
   VAE_CHECK(nwords, "chanhist_workspace: null args");
-  if (int rc = check_shape("chanhist_workspace", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_shape("chanhist_workspace", B, HW, C, nchunk)) return rc;
   *nwords = (int64_t)B * nchunk * C * CH_ROWS;
   return VAE_OK;
 }
@@ -194,16 +149,11 @@ extern "C" int vae_chanhist_workspace(int32_t B, int32_t HW, int32_t C, int32_t 
 extern "C" int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
                                     int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float tau, uint32_t* ws, void* stream) {
   VAE_CHECK(x && ws, "chanhist_partial: null args");
-  if (int rc = check_shape("chanhist_partial", B, HW, C, nchunk)) return rc;
-  VAE_CHECK(ld >= C, "chanhist_partial: pixel stride ld=%d below C=%d", ld, C);
-  VAE_CHECK(xf == VAE_XF_NONE || xf == VAE_XF_AFFINE || xf == VAE_XF_AFFINE_SILU, "chanhist_partial: xf=%d", xf);
-  VAE_CHECK(xf == VAE_XF_NONE || (scale && shift), "chanhist_partial: xf needs scale and shift");
+  if (int rc = stat_check_shape("chanhist_partial", B, HW, C, nchunk)) return rc;
+  if (int rc = stat_check_xf("chanhist_partial", xf, scale, shift, ld, C)) return rc;
   VAE_CHECK(tau >= 0.f, "chanhist_partial: near-zero threshold tau=%g is negative or NaN", (double)tau);
   VAE_CHECK(aligned16(ws), "chanhist_partial: unaligned workspace");
-  // four channels per lane where the rows allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
-  const uintptr_t amask = x_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & amask) == 0;
-  const int W = vec ? 4 : 1;
+  const bool vec = vec4_ok(x, x_bf16, C, ld);
   const int tiles = (C + CH_CT - 1) / CH_CT;  // C / W units in tiles of CH_CT / W
   VAE_CHECK(tiles <= 65535, "chanhist_partial: C=%d: too many channel tiles", C);
   const dim3 grid(nchunk, B, tiles);
@@ -221,8 +171,7 @@ extern "C" int vae_chanhist_partial(const void* x, int32_t x_bf16, const float* 
 extern "C" int vae_chanhist_final(const uint32_t* ws, int32_t B, int32_t HW, int32_t C, int32_t nchunk, int64_t* hist, int64_t* nzero,
                                   float* absmax, void* stream) {
   VAE_CHECK(ws && hist && nzero && absmax, "chanhist_final: null args");
-  if (int rc = check_shape("chanhist_final", B, HW, C, nchunk)) return rc;
-  VAE_CHECK((int64_t)B * nchunk <= 0x7fffffff, "chanhist_final: B * nchunk = %lld rows", (long long)((int64_t)B * nchunk));
+  if (int rc = stat_check_shape("chanhist_final", B, HW, C, nchunk)) return rc;
   VAE_CHECK(aligned16(ws), "chanhist_final: unaligned workspace");
   const int64_t blocks = ((int64_t)C * CH_ROWS + FIN_W - 1) / FIN_W;
   VAE_CHECK(blocks <= 0x7fffffff, "chanhist_final: C=%d: too many words", C);

@@ -8,23 +8,9 @@
 // sum(y^2) - n mean^2 is ever formed in fp32.  Final pass: the cells of each channel are turned into (mean, M2) and merged in fp64
 // with Chan's formula (one workgroup per channel), then the channels are merged the same way (one workgroup).  Every reduction is
 // a fixed-order loop or LDS tree: no atomics, repeated launches are bitwise identical.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
-
-// W consecutive channels of one pixel
-template <int W, bool XBF>
-__device__ __forceinline__ void load_units(const void* base, int64_t off, float (&v)[W]) {
-  if constexpr (W == 4) {
-    f32x4 q;  // (an element offset, not a quad index: off is a multiple of 4 only where the host chose W = 4)
-    if constexpr (XBF) q = unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const u16*>(base) + off));
-    else q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[e] = load1(base, off + e, XBF);
-  }
-}
 
 template <int W>
 __device__ __forceinline__ void apply_xf(float (&v)[W], const float (&sc)[W], const float (&sh)[W], int xf) {
@@ -39,15 +25,8 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const void* __rest
                                                               const float* __restrict__ shift, int xf, int HW, int C, int ld,
                                                               int nchunk, float* __restrict__ ws) {
   __shared__ float red[3][W][256];
-  const int nu = C / W;                          // channel units of W channels
-  const int u0 = blockIdx.z * 256;
-  const int nut = min(256, nu - u0);             // units of this workgroup
-  const Lay l = make_lay_q(nut);
-  const int PR = l.PR, pr = l.pr;                // pixel rows of the workgroup
-  const int c0 = (u0 + l.cq) * W;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const ChunkRange cr = chunk_range(HW, nchunk, chunk);  // p0 < HW: the host makes every chunk non-empty
-  const int p0 = cr.p0, p1 = cr.p1;
+  const StatFrame f = stat_frame<256, W>(HW, C, nchunk);  // tiles of 256 units, whatever W
+  const int PR = f.PR, c0 = f.c0, b = f.b, p0 = f.p0, p1 = f.p1;
   float sc[W], sh[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) {
@@ -61,9 +40,9 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const void* __rest
   float sa[W], s1[W], s2[W];
 #pragma unroll
   for (int e = 0; e < W; ++e) sa[e] = s1[e] = s2[e] = 0.f;
-  if (pr < PR) {
-    int pix = p0 + pr;
-    // four loads in flight per lane, then the same per-element order as the single-pixel tail
+  if (f.pr < PR) {
+    int pix = p0 + f.pr;
+    // four loads in flight per lane, then the single-pixel tail: the order of for_rows (chanstat_common.h), spelled out here
     for (; pix + 3 * PR < p1; pix += 4 * PR) {
       float v[4][W];
 #pragma unroll
@@ -100,18 +79,17 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const void* __rest
     red[2][e][threadIdx.x] = s2[e];
   }
   __syncthreads();
-  if ((int)threadIdx.x < nut) {
+  if ((int)threadIdx.x < f.nut) {
     const int64_t rows = (int64_t)gridDim.y * nchunk;
-    const int64_t row = (int64_t)b * nchunk + chunk;
+    const int64_t row = (int64_t)b * nchunk + f.chunk;
 #pragma unroll
     for (int e = 0; e < W; ++e) {
       f32x4 t = {0.f, 0.f, 0.f, K[e]};
-      for (int r = 0; r < PR; ++r) {
-        const int i = r * nut + threadIdx.x;
+      fold_rows(f, [&](int i) {
         t[0] += red[0][e][i];
         t[1] += red[1][e][i];
         t[2] += red[2][e][i];
-      }
+      });
       store4<false>(ws, (int64_t)(c0 + e) * rows + row, t);
     }
   }
@@ -195,15 +173,12 @@ __global__ __launch_bounds__(256) void moments_total_kernel(const double* __rest
 extern "C" int vae_moments_partial(const void* x, int32_t x_bf16, const float* scale, const float* shift, int32_t xf, int32_t B,
                                    int32_t HW, int32_t C, int32_t ld, int32_t nchunk, float* ws, void* stream) {
   VAE_CHECK(x && ws && B > 0 && HW > 0 && C > 0 && ld >= C && nchunk > 0, "moments_partial: bad args");
-  VAE_CHECK(xf == VAE_XF_NONE || xf == VAE_XF_AFFINE || xf == VAE_XF_AFFINE_SILU, "moments_partial: xf=%d", xf);
-  VAE_CHECK(xf == VAE_XF_NONE || (scale && shift), "moments_partial: xf needs scale and shift");
+  if (int rc = stat_check_xf("moments_partial", xf, scale, shift, ld, C)) return rc;
   const int per = (HW + nchunk - 1) / nchunk;
   VAE_CHECK(nchunk <= 65535 && B <= 65535 && (int64_t)(nchunk - 1) * per < HW,
             "moments_partial: nchunk=%d for HW=%d leaves an empty chunk (or too many workgroups)", nchunk, HW);
   VAE_CHECK(aligned16(ws), "moments_partial: unaligned workspace");
-  // four channels per lane where the rows allow a 16 B (fp32) / 8 B (bf16) load, one otherwise
-  const uintptr_t amask = x_bf16 ? 7u : 15u;
-  const bool vec = C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & amask) == 0;
+  const bool vec = vec4_ok(x, x_bf16, C, ld);
   const int W = vec ? 4 : 1;
   const int tiles = (C / W + 255) / 256;
   const dim3 grid(nchunk, B, tiles);

@@ -26,7 +26,7 @@
 // max |w| travels as a bit pattern (for |w| the unsigned order of the patterns is the order of the values, NaN above infinity)
 // and comes out exact, NaN if the slice holds one.  No atomics, nothing cleared: repeated launches are bitwise identical.
 // Nothing outside the table's tensors is read, no arena is written.
-#include "stream_common.h"
+#include "chanstat_common.h"
 
 namespace {
 
@@ -52,7 +52,6 @@ struct OpMaxU {
 __device__ __forceinline__ unsigned fbits(float f) { return __builtin_bit_cast(unsigned, f); }
 __device__ __forceinline__ float bitsf(unsigned u) { return __builtin_bit_cast(float, u); }
 __device__ __forceinline__ bool wd_has(int mode, int word) { return word == 0 || word == 6 || (word <= 2 ? mode >= 1 : mode >= 2); }
-__device__ __forceinline__ float absmax_of(unsigned b) { return b > 0x7f800000u ? bitsf(0x7fc00000u) : bitsf(b); }
 
 // the six products of one element (those of the mode)
 template <int MODE>

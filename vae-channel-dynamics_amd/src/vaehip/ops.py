@@ -889,35 +889,60 @@ def gn_track(x: torch.Tensor, st: Stats) -> torch.Tensor:
     return out
 
 
+def _nhwc_ld(who: str, x: torch.Tensor) -> int:
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError(f"{who}: expected NHWC rows with contiguous channels, strides {x.stride()}")
+    return ld
+
+
+def _stat_operand(who: str, x: torch.Tensor, stats: Optional[Stats], xf: int):
+    """the NHWC operand of a statistics pass and the GroupNorm transform applied to it on the fly
+    -> (B, H * W, C, pixel stride, scale, shift); scale and shift are None without a transform"""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    ld = _nhwc_ld(who, x)
+    B, H, W, Cc = x.shape
+    if (stats is None) != (xf == XF_NONE):
+        raise ValueError(f"{who}: a GroupNorm transform (xf) needs its stats and stats need an xf")
+    if stats is None:
+        return B, H * W, Cc, ld, None, None
+    if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
+        raise ValueError(f"{who}: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
+    return B, H * W, Cc, ld, stats.scale, stats.shift
+
+
+# a workgroup's channel tile in units of (four channels, one channel): _stat_chunks' vec_tile and scalar_tile
+_MOMENTS_TILE = (256, 256)   # moments(): 256 units, whatever the unit
+_CHANHIST_TILE = (32, 128)   # chanhist(): 128 channels
+_CHANGRAD_TILE = (64, 256)   # changrad(), changroup(), actreg_stats(): 256 channels
+
+
+def _stat_chunks(B: int, HW: int, Cc: int, vec_tile: int, scalar_tile: int) -> int:
+    """pixel chunks per image of a statistics partial pass whose workgroup takes a tile of vec_tile units of four channels (C a
+    multiple of 4) or of scalar_tile single channels: B * nchunk * tiles workgroups near _GN_TARGET, a chunk no shorter than 16
+    pixels per pixel row of a workgroup, and every chunk non-empty"""
+    units, tile = (Cc // 4, vec_tile) if Cc % 4 == 0 else (Cc, scalar_tile)
+    pr = max(1, 256 // min(tile, units))
+    tiles = (units + tile - 1) // tile
+    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
+    per = (HW + nch - 1) // nch
+    return (HW + per - 1) // per
+
+
 def moments(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE) -> torch.Tensor:
     """the other ActivityMonitor metrics of y = XF(x) in one read of x, no tensor materialised: a device vector of C + 2 fp32
     values, [per-channel mean |y| (as gn_track), mean of y, unbiased std of y (torch.Tensor.std)].  x: NHWC, fp32 or bf16
     storage, channels contiguous; a channel-prefix view of a wider buffer (x4[..., :3]) is read in place.  stats: the
     GroupNorm whose per-(b, c) scale / shift XF applies (rows as wide as the buffer's pixel stride)."""
-    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"moments: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError(f"moments: expected NHWC rows with contiguous channels, strides {x.stride()}")
-    if (stats is None) != (xf == XF_NONE):
-        raise ValueError("moments: a GroupNorm transform (xf) needs its stats and stats need an xf")
-    if stats is not None:
-        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
-            raise ValueError(f"moments: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
-    HW = H * W
-    units = Cc // 4 if Cc % 4 == 0 else Cc
-    pr = max(1, 256 // min(256, units))
-    tiles = (units + 255) // 256
-    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
-    per = (HW + nch - 1) // nch
-    nch = (HW + per - 1) // per  # every chunk non-empty
+    B, HW, Cc, ld, scale, shift = _stat_operand("moments", x, stats, xf)
+    nch = _stat_chunks(B, HW, Cc, *_MOMENTS_TILE)
     dev = x.device
     ws = torch.empty((Cc, B * nch, 4), device=dev, dtype=torch.float32)
     chan = torch.empty((Cc, 2), device=dev, dtype=torch.float64)
     out = torch.empty((Cc + 2,), device=dev, dtype=torch.float32)
-    lib.call("vae_moments_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
-             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_moments_partial", _p(x), _b16(x), _p(scale), _p(shift), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
     lib.call("vae_moments_final", _p(ws), B, HW, Cc, nch, _p(chan), _p(out), _stream())
     return out
 
@@ -931,25 +956,8 @@ def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, 
     k = clamp(floor(log2 |y|) + 31, 0, 47) (bin 0: |y| < 2^-30 with zeros and denormals, bin 47: |y| >= 2^16, inf, NaN); every
     row sums to B * H * W.  nzero[c] counts |y| < tau (compared in fp32; NaN is not below), absmax[c] is max |y| (NaN if the
     channel holds one).  x, stats and xf as in moments(); nothing synchronises the host."""
-    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"chanhist: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError(f"chanhist: expected NHWC rows with contiguous channels, strides {x.stride()}")
-    if (stats is None) != (xf == XF_NONE):
-        raise ValueError("chanhist: a GroupNorm transform (xf) needs its stats and stats need an xf")
-    if stats is not None:
-        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
-            raise ValueError(f"chanhist: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
-    HW = H * W
-    # as moments(), for this kernel's tile of 128 channels (32 units of four channels, or 128 single channels)
-    units, tile = (Cc // 4, 32) if Cc % 4 == 0 else (Cc, 128)
-    pr = max(1, 256 // min(tile, units))
-    tiles = (units + tile - 1) // tile
-    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
-    per = (HW + nch - 1) // nch
-    nch = (HW + per - 1) // per  # every chunk non-empty
+    B, HW, Cc, ld, scale, shift = _stat_operand("chanhist", x, stats, xf)
+    nch = _stat_chunks(B, HW, Cc, *_CHANHIST_TILE)
     dev = x.device
     n = C.c_int64(0)
     lib.call("vae_chanhist_workspace", B, HW, Cc, nch, C.byref(n))
@@ -957,8 +965,7 @@ def chanhist(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE, 
     hist = torch.empty((Cc, CHANHIST_BINS), device=dev, dtype=torch.int64)
     nzero = torch.empty((Cc,), device=dev, dtype=torch.int64)
     absmax = torch.empty((Cc,), device=dev, dtype=torch.float32)
-    lib.call("vae_chanhist_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
-             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, float(tau), _p(ws), _stream())
+    lib.call("vae_chanhist_partial", _p(x), _b16(x), _p(scale), _p(shift), xf, B, HW, Cc, ld, nch, float(tau), _p(ws), _stream())
     lib.call("vae_chanhist_final", _p(ws), B, HW, Cc, nch, _p(hist), _p(nzero), _p(absmax), _stream())
     return hist, nzero, absmax
 
@@ -977,26 +984,14 @@ def changroup(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE)
     from the first addition on (csrc/changroup.hip), in a fixed order: two calls agree bitwise.  A NaN or an infinity reaches the
     sums of its own (b, c) only.  x, stats and xf as in moments(); nothing synchronises the host.  changroup_metrics() turns the
     sums into the GroupNorm group dynamics and per-sample activity figures of the ActivityMonitor."""
-    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"changroup: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError(f"changroup: expected NHWC rows with contiguous channels, strides {x.stride()}")
-    if (stats is None) != (xf == XF_NONE):
-        raise ValueError("changroup: a GroupNorm transform (xf) needs its stats and stats need an xf")
-    if stats is not None:
-        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
-            raise ValueError(f"changroup: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
-    HW = H * W
+    B, HW, Cc, ld, scale, shift = _stat_operand("changroup", x, stats, xf)
     nch = changroup_chunks(B, HW, Cc)
     dev = x.device
     n = C.c_int64(0)
     lib.call("vae_changroup_workspace", B, HW, Cc, nch, C.byref(n))
     ws = torch.empty((n.value,), device=dev, dtype=torch.float64)
     sums = torch.empty((B, Cc, 3), device=dev, dtype=torch.float64)
-    lib.call("vae_changroup_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
-             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_changroup_partial", _p(x), _b16(x), _p(scale), _p(shift), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
     lib.call("vae_changroup_final", _p(ws), B, HW, Cc, nch, _p(sums), _stream())
     return sums
 
@@ -1052,20 +1047,7 @@ def changroup_metrics(sums: torch.Tensor, HW: int, groups: Optional[int], eps: f
 def changrad_chunks(B: int, HW: int, Cc: int) -> int:
     """pixel chunks per image of changrad(): B * nchunk * (tiles of 256 channels) workgroups near _GN_TARGET, a chunk no shorter
     than 16 pixels per pixel row of a workgroup, and every chunk non-empty"""
-    units, tile = (Cc // 4, 64) if Cc % 4 == 0 else (Cc, 256)
-    pr = max(1, 256 // min(tile, units))
-    tiles = (units + tile - 1) // tile
-    nch = max(1, min(_GN_TARGET // max(B * tiles, 1), HW // (16 * pr)))
-    per = (HW + nch - 1) // nch
-    return (HW + per - 1) // per
-
-
-def _nhwc_ld(who: str, x: torch.Tensor) -> int:
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError(f"{who}: expected NHWC rows with contiguous channels, strides {x.stride()}")
-    return ld
+    return _stat_chunks(B, HW, Cc, *_CHANGRAD_TILE)
 
 
 def changrad(a: torch.Tensor, g: torch.Tensor):
@@ -1208,18 +1190,7 @@ def chancov(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE):
     sigma costs no digits; products are split-bf16 on the matrix pipe (csrc/chancov.hip), the merge is float64 in a fixed order:
     two calls agree bitwise.  x, stats and xf as in moments().  The workspace rule is chancov_chunks(): at most 64 MB at every
     shape of the shipped model (tools/launch_shapes.py).  Nothing synchronises the host."""
-    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"chancov: expected a 4-D NHWC fp32 / bf16 CUDA tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError(f"chancov: expected NHWC rows with contiguous channels, strides {x.stride()}")
-    if (stats is None) != (xf == XF_NONE):
-        raise ValueError("chancov: a GroupNorm transform (xf) needs its stats and stats need an xf")
-    if stats is not None:
-        if tuple(stats.scale.shape) != (B, ld) or not stats.scale.is_contiguous() or x.storage_offset() % ld:
-            raise ValueError(f"chancov: stats rows {tuple(stats.scale.shape)} do not describe this tensor's channels")
-    HW = H * W
+    B, HW, Cc, ld, scale, shift = _stat_operand("chancov", x, stats, xf)
     if B * HW < 2:
         raise ValueError(f"chancov: a covariance needs at least two rows, got B * H * W = {B * HW}")
     nch = chancov_chunks(B, HW, Cc)
@@ -1229,8 +1200,7 @@ def chancov(x: torch.Tensor, stats: Optional[Stats] = None, xf: int = XF_NONE):
     ws = torch.empty((n.value,), device=dev, dtype=torch.float32)
     cov = torch.empty((Cc, Cc), device=dev, dtype=torch.float64)
     mean = torch.empty((Cc,), device=dev, dtype=torch.float64)
-    lib.call("vae_chancov_partial", _p(x), _b16(x), _p(stats.scale if stats is not None else None),
-             _p(stats.shift if stats is not None else None), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
+    lib.call("vae_chancov_partial", _p(x), _b16(x), _p(scale), _p(shift), xf, B, HW, Cc, ld, nch, _p(ws), _stream())
     lib.call("vae_chancov_final", _p(ws), B, HW, Cc, nch, _p(cov), _p(mean), _stream())
     return cov, mean
 
